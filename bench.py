@@ -8,10 +8,12 @@ Inputs and weights are resident in HBM before the timed region.  With N > 1 rank
 rank processes its own batch (weak scaling, samples are independent) and the warped frames
 of each step are all-gathered over RCCL on a side stream, overlapped with the next step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see the keys below); a per-layer table goes to stderr.
+Prints ONE JSON line on rank 0 (see the keys below).  A plain run sets up, warms up, times the K steps and prints the
+headline figure; --full adds everything else the line can carry (per-launch events and the two rooflines, with a per-layer
+table on stderr; the CPU baseline and flow_err; the secondary rows; the all-gather cost of N > 1 runs).
 """
 import argparse
 import json
@@ -107,6 +109,32 @@ def cpu_baseline(feats, frame, weights, seconds_budget=20.0):
                           "cores_box = logical CPUs the host reports",
             "sample": f"{len(times)} timed passes of the first {nb} samples of the timed GPU batch ({H}x{W}x{Cin}: "
                       f"network + flow glue + warp), torch-CPU fp32 restatement of the TF graph"}, ref
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname, budget=DUMP_BYTES):
+    """What the timed path returned in its last step -- the five flows, the output-resolution flow and the warped frame -- as
+    DIR/<name>.npy in float32.  Past `budget` bytes in all, each array keeps its share as a fixed sample of its flattened
+    elements (every stride-th from a seeded offset), so that runs with the same arguments write the same elements."""
+    flows, outflow, warped = out
+    arrays = {}
+    for k, t in flows.items():
+        if not any(t is u for u in arrays.values()):      # "flow" is predict_flow2 under a second name
+            arrays[k] = t
+    if outflow is not None:
+        arrays["outflow"] = outflow
+    arrays["warped"] = warped
+    total = sum(t.numel() * 4 for t in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(0)
+    stride = -(-total // (budget - 4 * len(arrays)))          # sum of ceil(numel / stride) * 4 B stays within budget
+    for name, t in arrays.items():
+        t = t.detach()
+        if stride > 1:
+            t = t.reshape(-1)[int(rng.integers(stride))::stride]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 EPS32 = 1.1920929e-07
@@ -266,7 +294,14 @@ def main():
                     help="vstab_set_plan_batch: pin the arithmetic-changing plan decisions to this batch (0 = plan for --batch itself)")
     ap.add_argument("--vgg16", action="store_true",
                     help="BASELINE config 5: also run the VGG16 trunk (preprocess + 13 conv + 5 pool) on the warped frames")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (rank 0's) as DIR/<name>.npy in float32, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-launch events and the rooflines, the CPU "
+                         "baseline and flow_err, the secondary rows, the all-gather cost of N > 1 runs (each subject to its --no-* option)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N without a launcher: start the N ranks ourselves as a CHILD job, before anything touches the GPU
     # (VSTAB_FORCE_DIST=1 rehearses the same launcher + RCCL path with however many ranks --gpus names, also 1)
@@ -348,23 +383,26 @@ def main():
         from coupe.optical_flow_based_deep_video_stabilization_amd import vgg16 as vvgg
         vgg = vvgg.Vgg16(seed=7, reuse_outputs=True)
 
-    # the spatial-transformer leg (--st-warp: inside the step; otherwise a few launches after the timed region for roofline_hbm.other_rows)
-    from coupe.optical_flow_based_deep_video_stabilization_amd import spatial_transformer as vst, warp as vwarp
-    import math
-    import types
-    st_rows = []
-    for _ in range(B):            # what a stabiliser applies: +-2 degrees, +-3 % scale, +-3 % shift, per sample
-        r = torch.rand(4, generator=g)
-        a, sc = math.radians(float(r[0]) * 4 - 2), 1 + (float(r[1]) - 0.5) * 0.06
-        st_rows.append([sc * math.cos(a), -sc * math.sin(a), (float(r[2]) - 0.5) * 0.06, sc * math.sin(a), sc * math.cos(a), (float(r[3]) - 0.5) * 0.06])
-    th6 = torch.tensor(st_rows, dtype=torch.float32).cuda()
-    th8 = torch.cat([th6, (torch.rand(B, 2, generator=g).cuda() - 0.5) * 0.02], 1)
-    st_aff, st_proj = vst.AffineTransformer((H, W)), vst.ProjectiveTransformer((H, W))
-    st_cfg = types.SimpleNamespace(warpType="homography", warpApprox=20, batch_size=B, height=H, width=W,
-                                   refMtrx=torch.tensor([[(W - 1) / 2, 0, (W - 1) / 2], [0, (H - 1) / 2, (H - 1) / 2], [0, 0, 1.0]]).cuda())
-    st_M = torch.cat([th8, torch.ones(B, 1, device="cuda")], 1).reshape(B, 3, 3)
-    st_fns = {"affine": lambda im: st_aff.transform(im, th6), "projective": lambda im: st_proj.transform(im, th8),
-              "homography": lambda im: vwarp.transformImage(st_cfg, im, st_M)}
+    # the spatial-transformer leg (--st-warp: inside the step; with --full also a few launches after the timed region for
+    # roofline_hbm.other_rows)
+    st_fns = {}
+    if args.full or args.st_warp != "none":
+        from coupe.optical_flow_based_deep_video_stabilization_amd import spatial_transformer as vst, warp as vwarp
+        import math
+        import types
+        st_rows = []
+        for _ in range(B):            # what a stabiliser applies: +-2 degrees, +-3 % scale, +-3 % shift, per sample
+            r = torch.rand(4, generator=g)
+            a, sc = math.radians(float(r[0]) * 4 - 2), 1 + (float(r[1]) - 0.5) * 0.06
+            st_rows.append([sc * math.cos(a), -sc * math.sin(a), (float(r[2]) - 0.5) * 0.06, sc * math.sin(a), sc * math.cos(a), (float(r[3]) - 0.5) * 0.06])
+        th6 = torch.tensor(st_rows, dtype=torch.float32).cuda()
+        th8 = torch.cat([th6, (torch.rand(B, 2, generator=g).cuda() - 0.5) * 0.02], 1)
+        st_aff, st_proj = vst.AffineTransformer((H, W)), vst.ProjectiveTransformer((H, W))
+        st_cfg = types.SimpleNamespace(warpType="homography", warpApprox=20, batch_size=B, height=H, width=W,
+                                       refMtrx=torch.tensor([[(W - 1) / 2, 0, (W - 1) / 2], [0, (H - 1) / 2, (H - 1) / 2], [0, 0, 1.0]]).cuda())
+        st_M = torch.cat([th8, torch.ones(B, 1, device="cuda")], 1).reshape(B, 3, 3)
+        st_fns = {"affine": lambda im: st_aff.transform(im, th6), "projective": lambda im: st_proj.transform(im, th8),
+                  "homography": lambda im: vwarp.transformImage(st_cfg, im, st_M)}
 
     nstep = [0]
     gather_on = [True]          # the second timed region of an N > 1 run (the same steps without the reassembly) clears it
@@ -405,7 +443,7 @@ def main():
         step = lambda: (graph.replay(), graph_out)[1]
 
     from coupe.optical_flow_based_deep_video_stabilization_amd import benchloop
-    use_events = not args.no_kernel_events
+    use_events = args.full and not args.no_kernel_events        # the per-launch events feed the rooflines alone
     ev_every = max(1, min(args.event_every, max(1, args.steps // 2)))
     n_event_steps = 0
 
@@ -426,11 +464,13 @@ def main():
     elapsed, out = benchloop.timed_region(timed_step, args.steps, args.warmup, torch.cuda.synchronize, dist=dist,
                                           drain=flush_and_drain if (gather is not None or grouped is not None) else None, before_timed=profilers_on,
                                           device="cpu" if args.backend == "gloo" else "cuda", prime=profilers_on if use_events else None)
+    if args.dump_outputs and rank == 0:      # before any later leg runs the path again into the same output buffers
+        dump_outputs(out, args.dump_outputs)
 
     # ---- N > 1: what the reassembly costs.  The SAME ranks run the same K steps again with the collective (and the uint8 staging
     # launch that feeds it) switched off; exposed = with - without.  After the timed region, never part of `value`.
     gather_cost = None
-    if (gather is not None or grouped is not None):
+    if args.full and (gather is not None or grouped is not None):
         gather_on[0] = False
         if use_events:
             ctx.profile_set(False)
@@ -449,7 +489,7 @@ def main():
     # the last timed step's outputs (first --err-samples samples), copied now: later legs reuse the workspace and the output buffers
     err_nb = max(1, min(B, args.err_samples))
     err_out = None
-    if rank == 0 and not args.no_flow_err and args.st_warp == "none":
+    if rank == 0 and args.full and not args.no_flow_err and args.st_warp == "none":
         fl_, of_, wf_ = out
         err_out = ({k: v[:err_nb].clone() for k, v in fl_.items()}, of_[:err_nb].clone() if of_ is not None else None, wf_[:err_nb].clone())
         torch.cuda.synchronize()
@@ -633,6 +673,7 @@ def main():
                    "gflop_per_sample": round(netspec.gflop_per_sample(H, W, Cin), 2),
                    "all_gather": (("fp32" if args.gather_fp32 else "uint8") + " warped frames, async over " + ("gloo (host memory; rehearsal)" if host else "RCCL") + ", schedule " + args.gather_schedule + f", one collective per {G} step(s)") if (gather is not None or grouped is not None) else False,
                    "vgg16_trunk": bool(args.vgg16), "st_warp": args.st_warp, "plan_flags": args.plan_flags, "plan_batch": args.plan_batch,
+                   "full": bool(args.full),
                    "host_calls_per_step": "1 (vstab_stabilise_originalsize, outputs pre-allocated)" if stab is not None else "2 + 7 allocations"},
         "roofline": roofline,
         "roofline_hbm": roofline_hbm,
@@ -640,13 +681,13 @@ def main():
     }
     # ---- secondary rows, AFTER the timed region and never part of `value`: what bench_clip.py (BASELINE configs[3]) and
     # bench_train.py measure at length, in short form, so that a driver that only runs bench.py sees them
-    if rank == 0 and world == 1 and dist is None and not args.no_secondary and graph is None:
+    if rank == 0 and args.full and world == 1 and dist is None and not args.no_secondary and graph is None:
         res["secondary"] = secondary_rows(vs, runtime, log)
     if rank == 0:
         nb = err_nb
-        feats_h, frame_h = feats[:nb].cpu().numpy(), frame[:nb].cpu().numpy()
+        feats_h, frame_h = (feats[:nb].cpu().numpy(), frame[:nb].cpu().numpy()) if args.full else (None, None)
         ref32 = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 res["cpu_baseline"], ref32 = cpu_baseline(feats_h, frame_h, weights, args.cpu_seconds)
             except Exception as e:   # the baseline must never take the GPU number down with it

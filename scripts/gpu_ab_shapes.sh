@@ -7,7 +7,7 @@ for s in "--batch 8 --height 512 --width 512 --steps 100 --warmup 10" "--batch 1
   for i in $(seq 1 $R); do
     for v in "$A" "$B"; do
       if [ "$v" = "-" ]; then unset VSTAB_LIB; else export VSTAB_LIB=$v; fi
-      out=$(python3 bench.py $s --no-cpu-baseline --no-secondary 2>/tmp/x.err) || { tail -3 /tmp/x.err; exit 1; }
+      out=$(python3 bench.py $s --full --no-cpu-baseline --no-secondary 2>/tmp/x.err) || { tail -3 /tmp/x.err; exit 1; }
       echo "$(echo $s | cut -c1-40) [$v] $(echo "$out" | python3 -c "import json,sys; print(json.loads(sys.stdin.read())['ms_per_step'])") $(grep '^conv1 ' /tmp/x.err | awk '{print $2, $5}')"
     done
   done

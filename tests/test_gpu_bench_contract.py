@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_contract_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-                        "--cpu-seconds", "3", "--no-secondary"], capture_output=True, text=True, timeout=600)
+                        "--full", "--cpu-seconds", "3", "--no-secondary"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -50,12 +50,49 @@ def test_bench_prints_one_contract_line():
     assert d["config"]["host_calls_per_step"].startswith("1 ")
 
 
+def test_plain_bench_run_times_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line carries the headline figure alone, and --dump-outputs writes what the timed path returned in its
+    last step: the same arrays the library computes for bench.py's seeded inputs (He-normal weights of seed 1, rank 0's batch)."""
+    import numpy as np
+    import torch
+    import coupe.optical_flow_based_deep_video_stabilization_amd as vs
+    from coupe.optical_flow_based_deep_video_stabilization_amd import runtime
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "stabilised frame-pairs/sec @512x512" and d["unit"] == "frame-pairs/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["full"] is False
+    assert abs(d["value"] - 8 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-3
+    assert d["roofline"] is None and d["roofline_hbm"] is None and d["cpu_baseline"] is None and d["flow_err"] is None
+    assert "secondary" not in d and d["all_gather"] is None
+
+    names = ("predict_flow6", "predict_flow5", "predict_flow4", "predict_flow3", "predict_flow2", "outflow", "warped")
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    runtime.reset()
+    vs.initialize_global_variables(seed=1, cin=27)
+    g = torch.Generator().manual_seed(1000)
+    feats = torch.rand(8, 512, 512, 27, generator=g).cuda()
+    frame = torch.rand(8, 512, 512, 3, generator=g).cuda()
+    flows, outflow, warped = vs.OriginalSizeStabiliser(8, 512, 512, 27, 512, 512)(feats, frame)
+    want = dict(flows, outflow=outflow, warped=warped)
+    for n in names:
+        assert got[n].shape == tuple(want[n].shape), n
+        assert np.array_equal(got[n], want[n].cpu().numpy()), n
+    assert float(np.abs(got["predict_flow2"]).max()) > 0.5         # a real flow field, not zeros
+
+
 def test_bench_self_launched_rccl_rank_prints_exactly_one_line():
     """The N > 1 path with one rank: the parent starts a torch.distributed.run child (no port picked ahead of time), the rank
     initialises RCCL -- which prints its version banner to file descriptor 1 on these boxes -- and all-gathers its uint8 frames;
     stdout must still be exactly the one JSON line."""
     env = dict(os.environ, VSTAB_FORCE_DIST="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "self-launch:" in r.stderr and "--rdzv-endpoint=127.0.0.1:0" in r.stderr and "--master-port" not in r.stderr
@@ -76,7 +113,7 @@ def test_bench_self_launches_two_ranks_rehearsal():
     side (sharing this box's one GPU, frames reassembled through gloo / host memory: --backend gloo is a control-flow rehearsal,
     its throughput means nothing) and rank 0 alone prints the line, with the whole job's aggregate."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--batch", "2", "--height", "128", "--width", "128"], capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--batch", "2", "--height", "128", "--width", "128"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "self-launch:" in r.stderr and "--nproc-per-node=2" in r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -13,7 +13,12 @@ def test_host_tests_under_asan_ubsan():
     from coupe.optical_flow_based_deep_video_stabilization_amd import build
     lib = build.build_sanitized()
     env = dict(os.environ)
-    env.update({"VSTAB_LIB": lib, "LD_PRELOAD": build.asan_runtime(),
+    preload = os.environ.get("LD_PRELOAD")
+    env.update({"VSTAB_LIB": lib,
+                "LD_PRELOAD": build.asan_runtime() + (":" + preload if preload else ""),      # the sanitizer runtime must come first
+                # host code only: on a machine with a GPU the child must not see it, or the HIP runtime's device-memory pools
+                # are allocated through the sanitizer's interceptors (which fail them); the host tests need no device
+                "ROCR_VISIBLE_DEVICES": "",
                 "ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0:detect_odr_violation=0",
                 "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
