@@ -1,9 +1,11 @@
 // C ABI of libvstab_hip.so (include/vstab.h): context, weight packing/upload, the
 // FlowNetS-pyramid forward schedule (model.py:786-893) and the glue/warp entry points.
+#include <cmath>
 #include <cstdlib>
 #include <map>
 #include <memory>
 #include <new>
+#include <vector>
 
 #include "api_internal.h"
 
@@ -1502,6 +1504,100 @@ extern "C" int vstab_transform_image(const float *img, int B, int Hi, int Wi, in
     if (!img || !ref || !pM || !out) return fail(nullptr, VSTAB_E_STATE, "transform_image: NULL buffer");
     if (B < 1 || Hi < 1 || Wi < 1 || C < 1 || oh < 1 || ow < 1) return fail(nullptr, VSTAB_E_SHAPE, "transform_image: bad shape");
     HIP_TRY(nullptr, launch_homography_warp(img, B, Hi, Wi, C, pM, out, oh, ow, (hipStream_t)stream, ref));
+    return VSTAB_OK;
+}
+
+// the rest of spatial_transformer.py's 2-D samplers: bicubic_interp, the symmetric-pad transformers, ElasticTransformer
+static bool stx_shape_ok(int B, int H, int W, int C, int oh, int ow)
+{
+    return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 1 && oh >= 1 && ow >= 1 && (long long)oh * ow <= 0x7fffffffLL / 4 &&
+           (long long)H * W <= 0x7fffffffLL;
+}
+
+extern "C" int vstab_st_bicubic_interp(const float *img, int B, int H, int W, int C, const float *x, const float *y, int oh, int ow,
+                                       float *out, void *stream)
+{
+    if (!img || !x || !y || !out) return fail(nullptr, VSTAB_E_STATE, "st_bicubic_interp: NULL buffer");
+    if (!stx_shape_ok(B, H, W, C, oh, ow)) return fail(nullptr, VSTAB_E_SHAPE, "st_bicubic_interp: bad shape");
+    HIP_TRY(nullptr, launch_st_bicubic_interp(img, B, H, W, C, x, y, oh, ow, out, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st_transform_interp(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim, int interp,
+                                         float *out, int oh, int ow, void *stream)
+{
+    if (!img || !theta || !out) return fail(nullptr, VSTAB_E_STATE, "st_transform_interp: NULL buffer");
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || (theta_dim != 6 && theta_dim != 8))
+        return fail(nullptr, VSTAB_E_SHAPE, "st_transform_interp: bad shape (theta must be [B,6] or [B,8])");
+    if (interp != VSTAB_INTERP_BILINEAR && interp != VSTAB_INTERP_BICUBIC) return fail(nullptr, VSTAB_E_SHAPE, "st_transform_interp: unknown interp %d", interp);
+    HIP_TRY(nullptr, launch_st_transform_interp(img, B, H, W, C, theta, theta_dim, interp, out, oh, ow, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st_symmetry_transform(const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
+                                           float *out, int oh, int ow, void *stream)
+{
+    if (!img || !theta || !out) return fail(nullptr, VSTAB_E_STATE, "st_symmetry_transform: NULL buffer");
+    if (oh < 1 || ow < 1 || oh > (1 << 20) || ow > (1 << 20) || !stx_shape_ok(B, H, W, C, oh + 200, ow + 200))
+        return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform: bad shape");
+    if (H < 100 || W < 100)          // tf.pad SYMMETRIC of 100 px needs H, W >= 100
+        return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform: the 100-pixel symmetric pad needs H, W >= 100 (got %dx%d)", H, W);
+    if (kind != VSTAB_SYM_AFFINE && kind != VSTAB_SYM_PROJECTIVE && kind != VSTAB_SYM_SIMILARITY)
+        return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform: unknown kind %d", kind);
+    if (interp != VSTAB_INTERP_BILINEAR && interp != VSTAB_INTERP_BICUBIC) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform: unknown interp %d", interp);
+    HIP_TRY(nullptr, launch_st_symmetry_transform(img, B, H, W, C, theta, kind, interp, out, oh, ow, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+// ElasticTransformer._initialize_tps (ST:187-225) in double: L (K+3)x(K+3) from the fp32 linspace control points, inverted by
+// Gauss-Jordan with partial pivoting, transpose(L_inv[:,3:]) rounded to fp32 into linv_t [K, K+3]
+extern "C" int vstab_host_tps_linv(int g, float *linv_t, int cap)
+{
+    if (!linv_t) return fail(nullptr, VSTAB_E_STATE, "host_tps_linv: linv_t is NULL");
+    if (g < 2 || g > VSTAB_TPS_GMAX) return fail(nullptr, VSTAB_E_SHAPE, "host_tps_linv: grid side %d outside [2, %d] (g = 1 makes L singular)", g, VSTAB_TPS_GMAX);
+    const int K = g * g, N = K + 3;
+    if (cap < K * N) return fail(nullptr, VSTAB_E_NOMEM, "host_tps_linv: need %d floats", K * N);
+    std::vector<double> px(K), py(K);
+    const float step = 2.0f / (float)(g - 1);          // tf.linspace(-1, 1, g) in fp32
+    for (int k = 0; k < K; ++k) { px[k] = (double)(-1.0f + (float)(k % g) * step); py[k] = (double)(-1.0f + (float)(k / g) * step); }
+    std::vector<double> A((size_t)N * 2 * N, 0.0);     // [L | I]
+    auto L = [&](int r, int c) -> double & { return A[(size_t)r * 2 * N + c]; };
+    for (int k = 0; k < K; ++k) { L(0, 3 + k) = px[k]; L(1, 3 + k) = py[k]; }
+    for (int c = 2; c < N; ++c) L(2, c) = 1.0;         // row 2: [0, 0, 1, ..., 1] (ST:208)
+    for (int i = 0; i < K; ++i) {
+        L(3 + i, 0) = px[i]; L(3 + i, 1) = py[i]; L(3 + i, 2) = 1.0;
+        for (int j = 0; j < K; ++j) {
+            const double dx = px[i] - px[j], dy = py[i] - py[j], r2 = dx * dx + dy * dy;
+            L(3 + i, 3 + j) = r2 == 0.0 ? 0.0 : r2 * std::log(r2);
+        }
+    }
+    for (int r = 0; r < N; ++r) L(r, N + r) = 1.0;
+    for (int c = 0; c < N; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < N; ++r) if (std::fabs(L(r, c)) > std::fabs(L(piv, c))) piv = r;
+        if (std::fabs(L(piv, c)) < 1e-300) return fail(nullptr, VSTAB_E_SHAPE, "host_tps_linv: L is singular");
+        if (piv != c) for (int k = 0; k < 2 * N; ++k) std::swap(L(c, k), L(piv, k));
+        const double d = L(c, c);
+        for (int k = 0; k < 2 * N; ++k) L(c, k) /= d;
+        for (int r = 0; r < N; ++r) {
+            if (r == c || L(r, c) == 0.0) continue;
+            const double f = L(r, c);
+            for (int k = 0; k < 2 * N; ++k) L(r, k) -= f * L(c, k);
+        }
+    }
+    for (int k = 0; k < K; ++k)                          // linv_t[k, j] = L_inv[j, 3 + k]
+        for (int j = 0; j < N; ++j) linv_t[(size_t)k * N + j] = (float)L(j, N + 3 + k);
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
+                                          int interp, float *out, int oh, int ow, void *stream)
+{
+    if (!img || !theta || !linv_t || !out) return fail(nullptr, VSTAB_E_STATE, "st_elastic_transform: NULL buffer");
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || g < 2 || g > VSTAB_TPS_GMAX)
+        return fail(nullptr, VSTAB_E_SHAPE, "st_elastic_transform: bad shape (grid side must be in [2, %d])", VSTAB_TPS_GMAX);
+    if (interp != VSTAB_INTERP_BILINEAR && interp != VSTAB_INTERP_BICUBIC) return fail(nullptr, VSTAB_E_SHAPE, "st_elastic_transform: unknown interp %d", interp);
+    HIP_TRY(nullptr, launch_st_elastic_transform(img, B, H, W, C, theta, g, linv_t, interp, out, oh, ow, (hipStream_t)stream));
     return VSTAB_OK;
 }
 

@@ -419,4 +419,403 @@ hipError_t launch_vec2mtrx(const float *p, int B, int dim, int approx, float *ou
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------
+// The rest of spatial_transformer.py's 2-D samplers: bicubic_interp (ST:966-1072), the symmetric-pad transformers
+// (SimilarityTransformer ST:311-371, AffineSymmetryTransformer ST:454-517, ProjectiveSymmetryTransformer ST:611-716) and
+// ElasticTransformer's thin-plate spline (ST:40-224).  One family of kernels, templated on where a pixel's source coordinates
+// come from (XS_*) and on the sampler (XI_*): stx3_tile_kernel for 3-channel frames (st3_tile_kernel's tile, tap gathers and
+// 16-byte row stores), stx_pixel_kernel (one thread per pixel, one sample per workgroup row of the grid) for other channel counts.
+// Bilinear sampling is st_taps / st_blend statement for statement; the existing kernels above are not touched.
+//   XS_COORDS  explicit x, y [B*oh*ow]                       (bicubic_interp)
+//   XS_THETA   Affine/ProjectiveTransformer's theta . grid   (interp_method='bicubic'; bilinear stays on st_transform)
+//   XS_SYM     the symmetric-pad transformers: the image padded by 100 px per side in SYMMETRIC mode is never materialised (a
+//              padded index p reads refl(p - 100)); the (oh+200) x (ow+200) grid is sampled only where
+//              resize_image_with_crop_or_pad keeps it, the pixels it pads are written as zeros
+//   XS_TPS     ElasticTransformer: coeff [2, K+3] = (source points + theta) . L_inv^T once per workgroup into LDS, then per
+//              pixel x_s = coeff_x . [x_t, y_t, 1, U_1..U_K] with U_k = r^2 ln r^2 evaluated in-kernel (no (K+1) x N table)
+// ---------------------------------------------------------------------------------
+enum { XS_COORDS = 0, XS_THETA = 1, XS_SYM = 2, XS_TPS = 3 };
+enum { XI_BILINEAR = 0, XI_BICUBIC = 1 };
+constexpr int STX_TPS_KMAX = 256;                    // g <= 16 control points per side (api.cpp)
+
+struct StxSrc {
+    const float *x, *y;            // XS_COORDS
+    const float *theta;            // XS_THETA [B,tdim]; XS_SYM [B,6|8|4]; XS_TPS [B,2K]
+    const float *linv_t;           // XS_TPS: transpose(L_inv[:,3:]) [K, K+3]
+    int tdim, kind, g, B;          // kind: XS_SYM's VSTAB_SYM_* (0 affine, 1 projective, 2 similarity); g: TPS grid side
+    int gh, gw;                    // the linspace sampling grid
+    float sx, sy;                  // its steps 2/(n-1), divided once on the host (lin11's quotient)
+    int Hs, Ws;                    // extent the sampler sees: (H+200, W+200) for XS_SYM, (H, W) otherwise
+    int pady, cropy, leny, padx, cropx, lenx;        // crop-or-pad: final i reads grid i - pad + crop when 0 <= i - pad < len
+};
+
+// np.pad(mode='symmetric') index map for one reflection (|u| stays within one image size: H, W >= 100 on the host)
+__device__ __forceinline__ int refl(int u, int n) { return u < 0 ? -u - 1 : (u >= n ? 2 * n - 1 - u : u); }
+
+// the sample's 2x3 / 3x3 matrix, theta pre-maps included, every product and sum its own fp32 operation
+template <int SRC>
+__device__ __forceinline__ void stx_matrix(const StxSrc &S, int n, float *th)
+{
+    if (SRC == XS_THETA) {
+        const float *tp = S.theta + (long long)n * S.tdim;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) th[k] = k < S.tdim ? tp[k] : 1.0f;
+    } else if (SRC == XS_SYM && S.kind == 0) {           // theta * [[.1,0,.2],[.1,0,.2]] * 0 + I (ST:503-505): NaN / inf survive
+        const float c[6] = {0.1f, 0.0f, 0.2f, 0.1f, 0.0f, 0.2f}, I[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+        const float *tp = S.theta + (long long)n * 6;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) th[k] = (tp[k] * c[k]) * 0.0f + I[k];
+        th[6] = th[7] = 0.f; th[8] = 1.f;
+    } else if (SRC == XS_SYM && S.kind == 1) {           // [theta, 1] * P + [[1,0,0],[0,1,0],[0,0,0]] (ST:692-699)
+        const float P[9] = {0.01f, 0.005f, 0.01f, 0.01f, 0.005f, 0.01f, 0.01f, 0.01f, 1.0f}, A[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f};
+        const float *tp = S.theta + (long long)n * 8;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) th[k] = (k < 8 ? tp[k] : 1.0f) * P[k] + A[k];
+    } else if (SRC == XS_SYM) {                          // SimilarityTransformer (ST:356-360)
+        // six [B] vectors concatenated on axis 0 and reshaped to [B,2,3]: sample n's entry k is vector (6n+k)/B at batch index
+        // (6n+k)%B -- for B > 1 the matrices interleave across samples ("BatchSize Should be One", ST:355), restated as is
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const int f = 6 * n + k, v = f / S.B, b = f - v * S.B;
+            const float *tp = S.theta + (long long)b * 4;
+            const float a = tp[0] * (float)(3.14 / 6) + 0.0f, s = tp[1] * 0.1f + 1.0f;
+            float e;
+            if (v == 0 || v == 4) e = s * cosf(a);
+            else if (v == 1) e = s * sinf(a);
+            else if (v == 3) e = (-s) * sinf(a);
+            else if (v == 2) e = tp[2] * 0.2f + 0.0f;
+            else e = tp[3] * 0.2f + 0.0f;
+            th[k] = e;
+        }
+        th[6] = th[7] = 0.f; th[8] = 1.f;
+    }
+}
+
+// stx_matrix for a whole workgroup: SimilarityTransformer's six entries (cos / sin, the interleave's divisions) are computed by
+// six threads into LDS instead of by every thread; the others as stx_matrix.  Every thread of the workgroup calls it.
+template <int SRC>
+__device__ __forceinline__ void stx_matrix_wg(const StxSrc &S, int n, float *th, float *sm)
+{
+    if (SRC == XS_SYM && S.kind == 2) {
+        if (threadIdx.x == 0) {
+            float m[9];
+            stx_matrix<SRC>(S, n, m);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) sm[k] = m[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 6; ++k) th[k] = sm[k];
+        th[6] = th[7] = 0.f; th[8] = 1.f;
+    } else if (SRC == XS_THETA || SRC == XS_SYM) {
+        stx_matrix<SRC>(S, n, th);
+    }
+}
+
+// TPS coefficients of sample n into LDS: cf[r*(K+3) + j] = sum_k (src_r[k] + theta[n, r*K+k]) * linv_t[k, j] (ST:108, 145-147), in
+// k order, and the control points (lin11 of k % g, k / g) after them for the per-pixel loop.  All threads of the workgroup take
+// part; the caller synchronises.
+__device__ __forceinline__ void stx_tps_coeff(const StxSrc &S, int n, float *cf)
+{
+    const int K = S.g * S.g, K3 = K + 3;
+    const float *tp = S.theta + (long long)n * 2 * K;
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {          // control points after the coefficients: cp_x[K], cp_y[K]
+        cf[2 * K3 + k] = lin11(k % S.g, S.g);
+        cf[2 * K3 + K + k] = lin11(k / S.g, S.g);
+    }
+    for (int e = threadIdx.x; e < 2 * K3; e += blockDim.x) {
+        const int r = e / K3, j = e - r * K3;
+        float acc = 0.0f;
+        for (int k = 0; k < K; ++k) {
+            const float src = r == 0 ? lin11(k % S.g, S.g) : lin11(k / S.g, S.g);
+            acc = acc + (src + tp[r * K + k]) * S.linv_t[(long long)k * K3 + j];
+        }
+        cf[e] = acc;
+    }
+}
+
+// normalised source coordinates of grid point (gx, gy) of sample n
+template <int SRC>
+__device__ __forceinline__ void stx_coords(const StxSrc &S, const float *th, const float *cf, int n, int gx, int gy, float &xs, float &ys)
+{
+    if (SRC == XS_COORDS) {
+        const long long i = ((long long)n * S.gh + gy) * S.gw + gx;
+        xs = S.x[i]; ys = S.y[i];
+        return;
+    }
+    const float xt = -1.0f + (float)gx * S.sx, yt = -1.0f + (float)gy * S.sy;
+    if (SRC == XS_TPS) {
+        const int K = S.g * S.g, K3 = K + 3;
+        float ax = (cf[0] * xt + cf[1] * yt) + cf[2];
+        float ay = (cf[K3] * xt + cf[K3 + 1] * yt) + cf[K3 + 2];
+        const float *cpx = cf + 2 * K3, *cpy = cpx + K;
+        for (int k = 0; k < K; ++k) {
+            const float dx = xt - cpx[k], dy = yt - cpy[k];
+            const float r2 = dx * dx + dy * dy;
+            const float U = r2 == 0.0f ? 0.0f : r2 * logf(r2);          // log 0 = -inf is replaced by 0 (ST:166-168)
+            ax = ax + cf[3 + k] * U;
+            ay = ay + cf[K3 + 3 + k] * U;
+        }
+        xs = ax; ys = ay;
+        return;
+    }
+    xs = (th[0] * xt + th[1] * yt) + th[2];
+    ys = (th[3] * xt + th[4] * yt) + th[5];
+    if (SRC == XS_THETA && S.tdim == 8) {                // ProjectiveTransformer: safe_z (ST:598)
+        float zs = (th[6] * xt + th[7] * yt) + 1.0f;
+        if (zs == 0.0f) zs = zs + 1e-8f;
+        xs = xs / zs;
+        ys = ys / zs;
+    } else if (SRC == XS_SYM && S.kind == 1) {           // ProjectiveSymmetryTransformer divides by z as is (ST:710-711)
+        const float zs = (th[6] * xt + th[7] * yt) + th[8];
+        xs = xs / zs;
+        ys = ys / zs;
+    }
+}
+
+// bicubic_interp's taps and weights along one axis (ST:988-1050): clip to [-1,1] first (NaN -> -1), scale, x0 = floor, taps in
+// the reference's order [x0, max(x0-1,0), min(x0+1,n-1), min(x0+2,n-1)] (edges replicate: no zero border), alpha = -0.75 weights
+// w_i = ((c_i0 + c_i1 t) + c_i2 t^2) + c_i3 t^3
+__device__ __forceinline__ void cubic_axis(float v, int n, int *ix, float *w)
+{
+    const float nf = (float)n;
+    v = fminf(fmaxf(v, -1.0f), 1.0f);
+    v = (v + 1.0f) / 2.0f * (nf - 1.0f);
+    const float v0f = floorf(v);
+    const int v0 = (int)v0f;
+    ix[0] = v0; ix[1] = max(v0 - 1, 0); ix[2] = min(v0 + 1, n - 1); ix[3] = min(v0 + 2, n - 1);
+    const float t = v - v0f, t2 = t * t, t3 = t2 * t;
+    w[0] = ((1.0f + 0.0f * t) + -2.25f * t2) + 1.25f * t3;
+    w[1] = ((0.0f + -0.75f * t) + 1.5f * t2) + -0.75f * t3;
+    w[2] = ((0.0f + 0.75f * t) + 1.5f * t2) + -1.25f * t3;
+    w[3] = ((0.0f + 0.0f * t) + -0.75f * t2) + 0.75f * t3;
+}
+
+struct Cubic { int x[4], y[4]; float wx[4], wy[4]; };
+
+// a sampled-extent index to an image index: the symmetric pad for XS_SYM, the identity otherwise
+template <int SRC>
+__device__ __forceinline__ int stx_src(int p, int n) { return SRC == XS_SYM ? refl(p - 100, n) : p; }
+
+// one output pixel, any channel count; `live` false writes zeros (the crop-or-pad padding)
+template <int SRC, int INTERP>
+__device__ __forceinline__ void stx_sample_pixel(const float *__restrict__ b, int H, int W, int C, const StxSrc &S, float xs, float ys,
+                                                 bool live, float *__restrict__ o)
+{
+    if (!live) {
+        for (int c = 0; c < C; ++c) o[c] = 0.0f;
+        return;
+    }
+    if (INTERP == XI_BILINEAR) {
+        const Taps t = st_taps(xs, ys, S.Hs, S.Ws);
+        const long long i00 = ((long long)stx_src<SRC>(t.ya, H) * W + stx_src<SRC>(t.xa, W)) * C;
+        const long long i01 = ((long long)stx_src<SRC>(t.ya, H) * W + stx_src<SRC>(t.xb, W)) * C;
+        const long long i10 = ((long long)stx_src<SRC>(t.yb, H) * W + stx_src<SRC>(t.xa, W)) * C;
+        const long long i11 = ((long long)stx_src<SRC>(t.yb, H) * W + stx_src<SRC>(t.xb, W)) * C;
+        const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+        for (int c = 0; c < C; ++c)
+            o[c] = st_blend<FAM_ST_THETA>(t, v00 ? b[i00 + c] : 0.f, v01 ? b[i01 + c] : 0.f, v10 ? b[i10 + c] : 0.f, v11 ? b[i11 + c] : 0.f);
+    } else {
+        Cubic q;
+        cubic_axis(xs, S.Ws, q.x, q.wx);
+        cubic_axis(ys, S.Hs, q.y, q.wy);
+        long long row[4], col[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { row[i] = (long long)stx_src<SRC>(q.y[i], H) * W; col[i] = stx_src<SRC>(q.x[i], W); }
+        for (int c = 0; c < C; ++c) {
+            float r[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                r[i] = ((q.wx[0] * b[(row[i] + col[0]) * C + c] + q.wx[1] * b[(row[i] + col[1]) * C + c]) + q.wx[2] * b[(row[i] + col[2]) * C + c])
+                       + q.wx[3] * b[(row[i] + col[3]) * C + c];
+            o[c] = ((q.wy[0] * r[0] + q.wy[1] * r[1]) + q.wy[2] * r[2]) + q.wy[3] * r[3];
+        }
+    }
+}
+
+// final pixel (fx, fy) -> grid point and whether the crop keeps it
+__device__ __forceinline__ bool stx_grid_pos(const StxSrc &S, int fx, int fy, int &gx, int &gy)
+{
+    const int uy = fy - S.pady, ux = fx - S.padx;
+    gy = min(max(uy + S.cropy, 0), S.gh - 1);
+    gx = min(max(ux + S.cropx, 0), S.gw - 1);
+    return uy >= 0 && uy < S.leny && ux >= 0 && ux < S.lenx;
+}
+
+// any channel count: grid (pixel blocks, B), one sample per workgroup so the TPS coefficients are computed once per workgroup
+template <int SRC, int INTERP>
+__global__ __launch_bounds__(256) void stx_pixel_kernel(const float *__restrict__ img, int H, int W, int C, StxSrc S,
+                                                        float *__restrict__ out, int FH, int FW)
+{
+    __shared__ float cf[SRC == XS_TPS ? 2 * (STX_TPS_KMAX + 3) + 2 * STX_TPS_KMAX : 8];
+    const int n = blockIdx.y;
+    if (SRC == XS_TPS) {
+        stx_tps_coeff(S, n, cf);
+        __syncthreads();
+    }
+    float th[9];
+    stx_matrix_wg<SRC>(S, n, th, cf);
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long long)FH * FW) return;
+    const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+    int gx, gy;
+    const bool live = stx_grid_pos(S, fx, fy, gx, gy);
+    float xs, ys;
+    stx_coords<SRC>(S, th, cf, n, gx, gy, xs, ys);
+    stx_sample_pixel<SRC, INTERP>(img + (long long)n * H * W * C, H, W, C, S, xs, ys, live, out + ((long long)n * FH * FW + p) * C);
+}
+
+// 3-channel frames: st3_tile_kernel's 16 x 32 tile of one sample, XCD-contiguous tile order, one 3-dword load per tap and rows
+// leaving through LDS as 16-byte stores.  Bicubic gathers 16 taps per pixel, row by row in tap order.
+template <int SRC, int INTERP, bool STAGE>
+__global__ __launch_bounds__(256) void stx3_tile_kernel(const float *__restrict__ img, int H, int W, StxSrc S,
+                                                        float *__restrict__ out, int FH, int FW, int tiles_x, int tiles_y)
+{
+    constexpr int TW = ST_TW, TH = ST_TH, PPT = ST_PPT, WW = ST_WW, WH = ST_WH, PPR = ST_PPR;
+    __shared__ __attribute__((aligned(16))) float lds[STAGE ? ST_TH * ST_TW * 3 : 4];
+    __shared__ float cf[SRC == XS_TPS ? 2 * (STX_TPS_KMAX + 3) + 2 * STX_TPS_KMAX : 8];
+    unsigned bx, by, bz;
+    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
+    const int tpi = tiles_x * tiles_y;
+    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
+    const int ty0 = (trem / tiles_x) * TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (SRC == XS_TPS) {
+        stx_tps_coeff(S, n, cf);
+        __syncthreads();
+    }
+    float th[9];
+    stx_matrix_wg<SRC>(S, n, th, cf);
+    const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + (long long)n * H * W;     // 3 B H W < 2^31 (host)
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        const int q = j * 4 + wave;
+        const int y = ty0 + (q / PPR) * WH + lane / WW, x = tx0 + (q % PPR) * WW + lane % WW;
+        const bool ok = y < FH && x < FW;
+        const int yy = min(y, FH - 1), xx = min(x, FW - 1);
+        int gx, gy;
+        const bool live = stx_grid_pos(S, xx, yy, gx, gy);
+        float xs, ys;
+        stx_coords<SRC>(S, th, cf, n, gx, gy, xs, ys);
+        rgb3 r;
+        if (INTERP == XI_BILINEAR) {
+            const Taps t = st_taps(xs, ys, S.Hs, S.Ws);
+            const int ya = stx_src<SRC>(t.ya, H) * W, yb = stx_src<SRC>(t.yb, H) * W, xa = stx_src<SRC>(t.xa, W), xb = stx_src<SRC>(t.xb, W);
+            const rgb3 I00 = b[ya + xa], I01 = b[ya + xb], I10 = b[yb + xa], I11 = b[yb + xb];
+            const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+            r.r = st_blend<FAM_ST_THETA>(t, v00 ? I00.r : 0.f, v01 ? I01.r : 0.f, v10 ? I10.r : 0.f, v11 ? I11.r : 0.f);
+            r.g = st_blend<FAM_ST_THETA>(t, v00 ? I00.g : 0.f, v01 ? I01.g : 0.f, v10 ? I10.g : 0.f, v11 ? I11.g : 0.f);
+            r.b = st_blend<FAM_ST_THETA>(t, v00 ? I00.b : 0.f, v01 ? I01.b : 0.f, v10 ? I10.b : 0.f, v11 ? I11.b : 0.f);
+        } else {
+            Cubic c;
+            cubic_axis(xs, S.Ws, c.x, c.wx);
+            cubic_axis(ys, S.Hs, c.y, c.wy);
+            int col[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) col[i] = stx_src<SRC>(c.x[i], W);
+            rgb3 rw[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int ro = stx_src<SRC>(c.y[i], H) * W;
+                const rgb3 I0 = b[ro + col[0]], I1 = b[ro + col[1]], I2 = b[ro + col[2]], I3 = b[ro + col[3]];
+                rw[i].r = ((c.wx[0] * I0.r + c.wx[1] * I1.r) + c.wx[2] * I2.r) + c.wx[3] * I3.r;
+                rw[i].g = ((c.wx[0] * I0.g + c.wx[1] * I1.g) + c.wx[2] * I2.g) + c.wx[3] * I3.g;
+                rw[i].b = ((c.wx[0] * I0.b + c.wx[1] * I1.b) + c.wx[2] * I2.b) + c.wx[3] * I3.b;
+            }
+            r.r = ((c.wy[0] * rw[0].r + c.wy[1] * rw[1].r) + c.wy[2] * rw[2].r) + c.wy[3] * rw[3].r;
+            r.g = ((c.wy[0] * rw[0].g + c.wy[1] * rw[1].g) + c.wy[2] * rw[2].g) + c.wy[3] * rw[3].g;
+            r.b = ((c.wy[0] * rw[0].b + c.wy[1] * rw[1].b) + c.wy[2] * rw[2].b) + c.wy[3] * rw[3].b;
+        }
+        if (!live) r.r = r.g = r.b = 0.0f;
+        if (STAGE) {
+            *reinterpret_cast<rgb3 *>(lds + (((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW) * 3) = r;
+        } else if (ok) {
+            reinterpret_cast<rgb3 *>(out)[((long long)n * FH + yy) * FW + xx] = r;
+        }
+    }
+    if (STAGE) {       // FW % 4 == 0 (host): a tile row is TW*12 bytes from a 16-byte aligned address
+        __syncthreads();
+        constexpr int R4 = TW * 3 / 4;
+        const int vw3 = min(TW, FW - tx0) * 3;
+        for (int e = threadIdx.x; e < TH * R4; e += 256) {
+            const int row = e / R4, c4 = e - row * R4;
+            if (ty0 + row >= FH || c4 * 4 >= vw3) continue;
+            float *o = out + (((long long)n * FH + ty0 + row) * FW + tx0) * 3 + c4 * 4;
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(lds + row * TW * 3 + c4 * 4);
+            if (c4 * 4 + 4 <= vw3) *reinterpret_cast<f32x4 *>(o) = v;
+            else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = v[i];
+        }
+    }
+}
+
+template <int SRC, int INTERP>
+static hipError_t launch_stx(const float *img, int B, int H, int W, int C, StxSrc S, float *out, int FH, int FW, hipStream_t stream)
+{
+    S.B = B;
+    S.sx = S.gw > 1 ? 2.0f / (float)(S.gw - 1) : 0.0f;
+    S.sy = S.gh > 1 ? 2.0f / (float)(S.gh - 1) : 0.0f;
+    if (C == 3) {
+        const long long tx = (FW + ST_TW - 1) / ST_TW, ty = (FH + ST_TH - 1) / ST_TH, tiles = tx * ty * B;
+        if (tiles < (1ll << 31) && (long long)B * H * W * 3 < (1ll << 31) && (long long)B * FH * FW * 3 < (1ll << 31)) {
+            const dim3 grid((unsigned)tiles), block(256);
+            if ((FW & 3) == 0 && ((uintptr_t)out & 15) == 0)
+                stx3_tile_kernel<SRC, INTERP, true><<<grid, block, 0, stream>>>(img, H, W, S, out, FH, FW, (int)tx, (int)ty);
+            else
+                stx3_tile_kernel<SRC, INTERP, false><<<grid, block, 0, stream>>>(img, H, W, S, out, FH, FW, (int)tx, (int)ty);
+            return hipGetLastError();
+        }
+    }
+    const long long blocks = ((long long)FH * FW + 255) / 256;
+    if (blocks >= (1ll << 31) || B > 65535) return hipErrorInvalidValue;
+    stx_pixel_kernel<SRC, INTERP><<<dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, stream>>>(img, H, W, C, S, out, FH, FW);
+    return hipGetLastError();
+}
+
+static StxSrc stx_plain(int oh, int ow)
+{
+    StxSrc S{};
+    S.gh = oh; S.gw = ow; S.leny = oh; S.lenx = ow;
+    return S;
+}
+
+hipError_t launch_st_bicubic_interp(const float *img, int B, int H, int W, int C, const float *x, const float *y, int oh, int ow,
+                                    float *out, hipStream_t stream)
+{
+    StxSrc S = stx_plain(oh, ow);
+    S.x = x; S.y = y; S.Hs = H; S.Ws = W;
+    return launch_stx<XS_COORDS, XI_BICUBIC>(img, B, H, W, C, S, out, oh, ow, stream);
+}
+
+hipError_t launch_st_transform_interp(const float *img, int B, int H, int W, int C, const float *theta, int tdim, int interp,
+                                      float *out, int oh, int ow, hipStream_t stream)
+{
+    if (interp == XI_BILINEAR) return launch_st_transform(img, B, H, W, C, theta, tdim, out, oh, ow, stream);
+    StxSrc S = stx_plain(oh, ow);
+    S.theta = theta; S.tdim = tdim; S.Hs = H; S.Ws = W;
+    return launch_stx<XS_THETA, XI_BICUBIC>(img, B, H, W, C, S, out, oh, ow, stream);
+}
+
+hipError_t launch_st_symmetry_transform(const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
+                                        float *out, int oh, int ow, hipStream_t stream)
+{
+    StxSrc S{};
+    S.theta = theta; S.kind = kind;
+    S.gh = oh + 200; S.gw = ow + 200; S.Hs = H + 200; S.Ws = W + 200;
+    // resize_image_with_crop_or_pad(out, ow, oh) (ST:343, 488, 682): target height ow, width oh -- swapped
+    const int th = ow, tw = oh;
+    S.cropy = max((S.gh - th) / 2, 0); S.pady = max((th - S.gh) / 2, 0); S.leny = min(S.gh, th);
+    S.cropx = max((S.gw - tw) / 2, 0); S.padx = max((tw - S.gw) / 2, 0); S.lenx = min(S.gw, tw);
+    if (interp == XI_BILINEAR) return launch_stx<XS_SYM, XI_BILINEAR>(img, B, H, W, C, S, out, th, tw, stream);
+    return launch_stx<XS_SYM, XI_BICUBIC>(img, B, H, W, C, S, out, th, tw, stream);
+}
+
+hipError_t launch_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
+                                       int interp, float *out, int oh, int ow, hipStream_t stream)
+{
+    StxSrc S = stx_plain(oh, ow);
+    S.theta = theta; S.g = g; S.linv_t = linv_t; S.Hs = H; S.Ws = W;
+    if (interp == XI_BILINEAR) return launch_stx<XS_TPS, XI_BILINEAR>(img, B, H, W, C, S, out, oh, ow, stream);
+    return launch_stx<XS_TPS, XI_BICUBIC>(img, B, H, W, C, S, out, oh, ow, stream);
+}
+
 }  // namespace vstab

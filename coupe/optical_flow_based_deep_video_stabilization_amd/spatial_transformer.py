@@ -1,13 +1,20 @@
-"""Drop-ins for the samplers of the reference's `spatial_transformer.py` that BASELINE.json's
-north_star names: `transformer` (:34-38), `AffineTransformer` (:373-452), `ProjectiveTransformer`
-(:519-608), `_meshgrid` (:755-779), `_repeat` (:782-785), `_interpolate` (:787-792) and
-`bilinear_interp` (:902-964).  None of them is executed by the reference's runnable scripts (they
-are only imported, main:4); the arithmetic runs in HIP kernels (csrc/sampler_ops.hip)."""
+"""Drop-ins for the 2-D samplers of the reference's `spatial_transformer.py`: `transformer` (:34-38),
+`ElasticTransformer` (:40-224), `SimilarityTransformer` (:311-371), `AffineTransformer` (:373-452),
+`AffineSymmetryTransformer` (:454-517), `ProjectiveTransformer` (:519-608), `ProjectiveSymmetryTransformer`
+(:611-716), `_meshgrid` (:755-779), `_repeat` (:782-785), `_interpolate` (:787-792), `bilinear_interp` (:902-964)
+and `bicubic_interp` (:966-1072).  None of them is executed by the reference's runnable scripts (they are only
+imported, main:4 and cell.py:2); the arithmetic runs in HIP kernels (csrc/sampler_ops.hip).  The 3-D classes
+(`AffineVolumeTransformer`, `bilinear_interp3d`, `_meshgrid3d`, `_interpolate3d`) are not provided."""
 from __future__ import annotations
 
+import ctypes
+
+import numpy as np
 import torch
 
 from . import _lib, runtime
+
+_INTERP = {'bilinear': 0, 'bicubic': 1}          # VSTAB_INTERP_*
 
 
 def _f32_cuda(t, name):
@@ -50,12 +57,37 @@ def bilinear_interp(im, x, y, out_size):
     return out
 
 
+def bicubic_interp(im, x, y, out_size):
+    """im [B,H,W,C]; x, y flat [B*out_h*out_w] normalised to [-1,1] -> [B*out_h*out_w, C].
+    Coordinates are clipped to [-1, 1] before the scaling (NaN reads as -1); 4 x 4 taps, edges replicate
+    (no zero border), alpha = -0.75."""
+    im = _f32_cuda(im, "im")
+    B, H, W, Cc = im.shape
+    x = _f32_cuda(x.to(torch.float32), "x").reshape(-1)
+    y = _f32_cuda(y.to(torch.float32), "y").reshape(-1)
+    oh, ow = int(out_size[0]), int(out_size[1])
+    npix = oh * ow
+    if x.numel() != B * npix or y.numel() != B * npix:
+        raise ValueError(f"x/y must have B*out_h*out_w = {B * npix} elements")
+    out = torch.empty((B * npix, Cc), dtype=torch.float32, device=im.device)
+    with torch.cuda.device(im.device):
+        _lib.check(_lib.lib().vstab_st_bicubic_interp(im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow,
+                                                      out.data_ptr(), runtime.stream_ptr()))
+    return out
+
+
 def _interpolate(im, x, y, out_size, method):
     if method == 'bilinear':
         return bilinear_interp(im, x, y, out_size)
     if method == 'bicubic':
-        raise NotImplementedError("bicubic_interp is not on the path this build covers")
+        return bicubic_interp(im, x, y, out_size)
     return None            # the reference falls through to None for unknown methods (:792)
+
+
+def _interp_code(method):
+    if method not in _INTERP:
+        raise NotImplementedError(f"interp_method must be 'bilinear' or 'bicubic', not {method!r}")
+    return _INTERP[method]
 
 
 class _ThetaTransformer(object):
@@ -74,8 +106,7 @@ class _ThetaTransformer(object):
         return self._grid
 
     def transform(self, inp, theta):
-        if self.interp_method != 'bilinear':
-            raise NotImplementedError("only interp_method='bilinear' is implemented")
+        interp = _interp_code(self.interp_method)
         inp = _f32_cuda(inp, "inp")
         B, H, W, Cc = inp.shape
         theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
@@ -84,8 +115,12 @@ class _ThetaTransformer(object):
         oh, ow = self.out_size
         out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
         with torch.cuda.device(inp.device):
-            _lib.check(_lib.lib().vstab_st_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.param_dim,
-                                                     out.data_ptr(), oh, ow, runtime.stream_ptr()))
+            if interp == 0:
+                _lib.check(_lib.lib().vstab_st_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.param_dim,
+                                                         out.data_ptr(), oh, ow, runtime.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().vstab_st_transform_interp(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.param_dim,
+                                                                interp, out.data_ptr(), oh, ow, runtime.stream_ptr()))
         return out
 
 
@@ -104,6 +139,121 @@ class ProjectiveTransformer(_ThetaTransformer):
 
     def __init__(self, out_size, name='SpatialProjectiveTransformer', interp_method='bilinear', **kwargs):
         super().__init__(out_size, name, interp_method, **kwargs)
+
+
+class _SymmetryTransformer(object):
+    """The symmetric-pad transformers (ST:311-371, 454-517, 611-716): the input padded by 100 px per side in SYMMETRIC mode
+    (H, W >= 100, as tf.pad requires; never materialised), sampled on the linspace grid of (oh+200) x (ow+200) points, then
+    tf.image.resize_image_with_crop_or_pad(out, out_size[1], out_size[0]) -- target height ow, width oh: the result is
+    [B, ow, oh, C].  For square outputs the swap does not show."""
+    param_dim = 0
+    kind = -1
+
+    def __init__(self, out_size, name, interp_method='bilinear', **kwargs):
+        self.name = name
+        self.out_size = (int(out_size[0]), int(out_size[1]))
+        self.interp_method = interp_method
+
+    def transform(self, inp, theta):
+        interp = _interp_code(self.interp_method)
+        inp = _f32_cuda(inp, "inp")
+        B, H, W, Cc = inp.shape
+        if H < 100 or W < 100:
+            raise ValueError(f"{type(self).__name__}: the 100-pixel symmetric pad needs H, W >= 100, got {H}x{W}")
+        theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
+        if theta.numel() != B * self.param_dim:
+            raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
+        oh, ow = self.out_size
+        out = torch.empty((B, ow, oh, Cc), dtype=torch.float32, device=inp.device)
+        with torch.cuda.device(inp.device):
+            _lib.check(_lib.lib().vstab_st_symmetry_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.kind, interp,
+                                                              out.data_ptr(), oh, ow, runtime.stream_ptr()))
+        return out
+
+
+class SimilarityTransformer(_SymmetryTransformer):
+    """theta [B,4] = (angle, scale, tx, ty) pre-mapped by * [3.14/6, .1, .2, .2] + [0, 1, 0, 0] (ST:356-357) into
+    [s cos a, s sin a, tx; -s sin a, s cos a, ty].  The reference concatenates the six [B] vectors on axis 0 before the
+    reshape to [B,2,3] (ST:358-360), so for B > 1 the matrices interleave across samples ("BatchSize Should be One",
+    ST:355); that order is kept.  Output [B, ow, oh, C]."""
+    param_dim = 4
+    kind = 2
+
+    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', **kwargs):
+        super().__init__(out_size, name, interp_method, **kwargs)
+
+
+class AffineSymmetryTransformer(_SymmetryTransformer):
+    """theta [B,6] pre-mapped by * [[.1,0,.2],[.1,0,.2]] * 0 + I (ST:503-505): the identity for any finite theta (NaN / inf
+    still propagate).  The [B, ow, oh, C] crop is relabelled [B, oh, ow, C] by a reshape, as the reference does (ST:492)."""
+    param_dim = 6
+    kind = 0
+
+    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', **kwargs):
+        super().__init__(out_size, name, interp_method, **kwargs)
+
+    def transform(self, inp, theta):
+        out = super().transform(inp, theta)
+        return out.reshape(out.shape[0], self.out_size[0], self.out_size[1], out.shape[3])
+
+
+class ProjectiveSymmetryTransformer(_SymmetryTransformer):
+    """theta [B,8]: [theta, 1] * [[.01,.005,.01],[.01,.005,.01],[.01,.01,1]] + [[1,0,0],[0,1,0],[0,0,0]] (ST:692-699), divided
+    by z with no safe_z (ST:710-711).  Output [B, ow, oh, C]."""
+    param_dim = 8
+    kind = 1
+
+    def __init__(self, out_size, name='SpatialProjectiveTransformer', interp_method='bilinear', **kwargs):
+        super().__init__(out_size, name, interp_method, **kwargs)
+
+
+def _tps_linv(g):
+    """transpose(L_inv[:,3:]) [g*g, g*g+3] of ElasticTransformer._initialize_tps (ST:187-225), inverted in double on the host
+    and rounded to fp32."""
+    K = g * g
+    buf = np.empty((K, K + 3), dtype=np.float32)
+    _lib.check(_lib.lib().vstab_host_tps_linv(int(g), buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), buf.size))
+    return buf
+
+
+class ElasticTransformer(object):
+    """Thin-plate spline transformer (ST:40-224).  param_dim = g, the side of the g x g control grid (linspace(-1,1,g)
+    meshgrid, x fastest); theta [B, 2*g*g] = x offsets then y offsets of the control points.  L_inv is computed once at
+    construction, in double, and kept on the device as fp32 transpose(L_inv[:,3:]); the kernel computes each sample's
+    coefficients once and U = r^2 ln r^2 per output pixel.  Output [B, oh, ow, C]."""
+
+    def __init__(self, out_size, param_dim, name='SpatialElasticTransformer', interp_method='bilinear', **kwargs):
+        g = int(param_dim)
+        if g < 2:
+            raise ValueError("ElasticTransformer: param_dim (control grid side) must be >= 2; g = 1 makes L singular")
+        self.name = name
+        self.grid_size = g
+        self.num_control_points = g * g
+        self.param_dim = 2 * g * g
+        self.interp_method = interp_method
+        self.out_size = (int(out_size[0]), int(out_size[1]))
+        self.num_pixels = self.out_size[0] * self.out_size[1]
+        linv = _tps_linv(g)                       # ValueError for g > VSTAB_TPS_GMAX
+        runtime._require_gpu()
+        self.L_inv = torch.from_numpy(linv).to(torch.device("cuda", torch.cuda.current_device()))
+
+    def transform(self, inp, theta, forward=True, **kwargs):
+        """forward=False gives the same output: the reference computes the same coordinates twice (ST:122-132)."""
+        interp = _interp_code(self.interp_method)
+        inp = _f32_cuda(inp, "inp")
+        B, H, W, Cc = inp.shape
+        theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
+        if theta.numel() != B * self.param_dim:
+            raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
+        if self.L_inv.device != inp.device:
+            self.L_inv = self.L_inv.to(inp.device)
+        oh, ow = self.out_size
+        out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
+        with torch.cuda.device(inp.device):
+            _lib.check(_lib.lib().vstab_st_elastic_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.grid_size,
+                                                             self.L_inv.data_ptr(), interp, out.data_ptr(), oh, ow,
+                                                             runtime.stream_ptr()))
+        return out
 
 
 def transformer(inp, theta, out_size, name='SpatialTransformer', **kwargs):

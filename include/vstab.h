@@ -181,6 +181,34 @@ VSTAB_API int vstab_st_bilinear_interp(const float *img, int B, int H, int W, in
                                        int oh, int ow, float *out, void *stream);
 /* _meshgrid(out_size) (spatial_transformer.py:755-779): out[3*oh*ow] = x_t row, y_t row, ones. */
 VSTAB_API int vstab_st_meshgrid(float *out, int oh, int ow, void *stream);
+/* ---- the rest of spatial_transformer.py's 2-D samplers (bicubic, symmetric-pad transformers, thin-plate spline).  Shapes as in
+ * the entry points above; B <= 65535; VSTAB_E_SHAPE for anything outside the contract. */
+#define VSTAB_INTERP_BILINEAR 0
+#define VSTAB_INTERP_BICUBIC  1
+#define VSTAB_SYM_AFFINE      0   /* AffineSymmetryTransformer      ST:454-517, theta [B,6] */
+#define VSTAB_SYM_PROJECTIVE  1   /* ProjectiveSymmetryTransformer  ST:611-716, theta [B,8] */
+#define VSTAB_SYM_SIMILARITY  2   /* SimilarityTransformer          ST:311-371, theta [B,4] */
+#define VSTAB_TPS_GMAX       16   /* ElasticTransformer: at most 16 x 16 control points */
+/* bicubic_interp(im, x, y, out_size) (ST:966-1072): x, y flat [B*oh*ow] clipped to [-1,1] (NaN -> -1), 4x4 taps with edges
+ * replicated (no zero border), alpha = -0.75; out [B*oh*ow, C]. */
+VSTAB_API int vstab_st_bicubic_interp(const float *img, int B, int H, int W, int C, const float *x, const float *y, int oh, int ow,
+                                      float *out, void *stream);
+/* vstab_st_transform with a choice of sampler: VSTAB_INTERP_BILINEAR is vstab_st_transform itself (bit-equal),
+ * VSTAB_INTERP_BICUBIC samples with bicubic_interp.  out [B,oh,ow,C]. */
+VSTAB_API int vstab_st_transform_interp(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim, int interp,
+                                        float *out, int oh, int ow, void *stream);
+/* The symmetric-pad transformers' .transform: the image padded by 100 px per side in SYMMETRIC mode (H, W >= 100; never
+ * materialised), sampled on the linspace grid of (oh+200) x (ow+200) points, then resize_image_with_crop_or_pad(out, ow, oh):
+ * out [B,ow,oh,C] (height and width swapped, as the reference has them).  kind VSTAB_SYM_*. */
+VSTAB_API int vstab_st_symmetry_transform(const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
+                                          float *out, int oh, int ow, void *stream);
+/* Host only: ElasticTransformer's transpose(L_inv[:,3:]) for a g x g control grid (ST:187-225), inverted in double and rounded
+ * to fp32: linv_t [g*g, g*g+3] (cap floats available).  2 <= g <= VSTAB_TPS_GMAX (g = 1 makes L singular). */
+VSTAB_API int vstab_host_tps_linv(int g, float *linv_t, int cap);
+/* ElasticTransformer.transform (ST:84-158): theta [B, 2*g*g] control-point offsets (x block then y block), linv_t (device) from
+ * vstab_host_tps_linv; the thin-plate spline maps the linspace grid of (oh, ow) to source coordinates.  out [B,oh,ow,C]. */
+VSTAB_API int vstab_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
+                                         int interp, float *out, int oh, int ow, void *stream);
 /* warp.transformImage / transformCropImage (warp.py:46-86, 89-129): M [B,9] = refMtrx . pMtrx maps the canonical
  * linspace(-1,1) grid of the OUTPUT size to source pixel coordinates; floor/ceil taps, zero outside. */
 VSTAB_API int vstab_homography_warp(const float *img, int B, int Hi, int Wi, int C, const float *M, float *out, int oh,
