@@ -1,9 +1,13 @@
 // VALU kernels of the flow pyramid and the warp: everything on the hot path that is not
 // a wide-output convolution.  All are HBM/latency-bound gathers and lerps (~1 FLOP/byte).
+// The 3-channel tile kernels (warp, fused glue + warp, the fused tails, glue, resize) stand on the skeleton of tile3.h; each
+// piece of the reference's arithmetic is one device function (tf_warp_taps / tf_warp_blend, glue_fetch / glue_interp, lerp2)
+// that the one-thread-per-pixel kernel and every tile kernel call.
 // Built with -ffp-contract=off so that the lerp / weight arithmetic is the same sequence
 // of fp32 roundings the reference's TF graph performs; dot products use explicit fmaf.
 #include "vstab_internal.h"
 #include "hbm_profile.h"
+#include "tile3.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -11,9 +15,6 @@
 #include <vector>
 
 namespace vstab {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // ---- records of the optional per-launch timing of the HBM-side kernels (hbm_profile.h has the launch wrapper)
 struct HbmProfState {
@@ -58,7 +59,7 @@ hipError_t hbm_profile_begin(int slot, double alg_bytes, hipEvent_t *a, hipEvent
 {
     HbmProfState &P = hbm_prof();
     *a = *b = nullptr;
-    if (!P.on) return hipSuccess;
+    if (!P.on || slot < 0) return hipSuccess;        // slot < 0: a launch that is not timed
     HbmProfState::Rec r;
     hipError_t e = hipEventCreate(&r.a);
     if (e != hipSuccess) return e;
@@ -352,7 +353,9 @@ __global__ __launch_bounds__(256) void pf2_kernel(const float *__restrict__ T, i
 // its nine taps as 8-byte LDS reads instead of nine 8-byte global gathers -- the direct kernel spent its time in the L1 tag pipe
 // (nine lookups per pixel) with the table itself L2-resident.  Same sums in the same (dy, dx) order; a skipped out-of-image tap
 // is now an added +0.0f.
-constexpr int PF2_TH = 16, PF2_TW = 64, PF2_PPT = 4, PF2_CAP = 320;      // CAP: window pixels held in LDS (23 KB)
+constexpr int PF2_TW = 64, PF2_PPT = 4, PF2_CAP = 320;      // CAP: window pixels held in LDS (23 KB)
+using Pf2Tile = Tile3<4, 16, PF2_TW, PF2_PPT>;              // tile3.h's skeleton with a 16 x 64 tile, no staged store
+constexpr int PF2_TH = Pf2Tile::TH;
 __global__ __launch_bounds__(256) void pf2_tile_kernel(const float *__restrict__ T, int B, int h2, int w2,
                                                        const float *__restrict__ bias2, const float *__restrict__ pf3,
                                                        int h3, int w3, float *__restrict__ pf2, int H, int W,
@@ -360,11 +363,8 @@ __global__ __launch_bounds__(256) void pf2_tile_kernel(const float *__restrict__
 {
     __shared__ __attribute__((aligned(8))) float tab[PF2_CAP * 18];
     const int oh = H - 2, ow = W - 2;
-    unsigned bx, by, bz;
-    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int ty0 = (trem / tiles_x) * PF2_TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * PF2_TW;
+    const Pf2Tile tile(tiles_x, tiles_y);
+    const int n = tile.n, ty0 = tile.ty0, tx0 = tile.tx0;
     // source window (indices into the UNPADDED concat2 grid, so -1 and h2 / w2 are the zero ring)
     const int r_lo = nearest_ac(ty0, nsy, h2 + 2) - 1, r_hi = nearest_ac(min(ty0 + PF2_TH - 1, oh - 1) + 2, nsy, h2 + 2) - 1;
     const int c_lo = nearest_ac(tx0, nsx, w2 + 2) - 1, c_hi = nearest_ac(min(tx0 + PF2_TW - 1, ow - 1) + 2, nsx, w2 + 2) - 1;
@@ -380,11 +380,10 @@ __global__ __launch_bounds__(256) void pf2_tile_kernel(const float *__restrict__
         *reinterpret_cast<f32x2 *>(tab + px * 18 + t * 2) = v;
     }
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float b0 = bias2[0], b1 = bias2[1];
 #pragma unroll
     for (int j = 0; j < PF2_PPT; ++j) {
-        const int y = ty0 + j * 4 + (lane >> 4), x = tx0 + wave * 16 + (lane & 15);
+        const int y = tile.y(j), x = tile.x(j);
         if (y >= oh || x >= ow) continue;
         int ry[3], rx[3];
 #pragma unroll
@@ -502,6 +501,44 @@ hipError_t launch_div_const_selftest(float d, unsigned first, unsigned long long
     div_const_selftest_kernel<<<dim3(4096), dim3(256), 0, stream>>>(d, (float)(1.0 / (double)d), first, count, bad);
     return hipGetLastError();
 }
+// the glue of one output pixel from its four source-flow taps: the one statement of main:497-498's interpolation
+__device__ __forceinline__ f32x2 glue_interp(f32x2 tl, f32x2 tr, f32x2 bl, f32x2 br, float tx, float ty, const GlueParams &G)
+{
+    f32x2 o;
+    o.x = glue_post_x(lerp2(glue_pre(tl.x, G), glue_pre(tr.x, G), glue_pre(bl.x, G), glue_pre(br.x, G), tx, ty), G);
+    o.y = glue_post_y(lerp2(glue_pre(tl.y, G), glue_pre(tr.y, G), glue_pre(bl.y, G), glue_pre(br.y, G), tx, ty), G);
+    return o;
+}
+// The tile kernels' fetch of those taps.  The left/right taps of a row are neighbours (hi = lo + 1, or both the last column): ONE
+// 16-byte load per row -- half the L1 lookups of four 8-byte gathers -- of the source pixels (xb, xb + 1), xb = min(lo, w - 2)
+// (w >= 2: host).  `b` is the sample's flow.
+struct __attribute__((packed, aligned(8))) flow2 { f32x2 a, b; };     // two neighbouring flow pixels (8-byte aligned, 16 bytes)
+struct GlueTaps { flow2 top, bot; Lerp Y, X; int xb; };
+__device__ __forceinline__ GlueTaps glue_fetch(const f32x2 *__restrict__ b, int y, int x, const GlueParams &G)
+{
+    GlueTaps t;
+    t.Y = legacy_coord(y, G.ry, G.h); t.X = legacy_coord(x, G.rx, G.w);
+    t.xb = min(t.X.lo, G.w - 2);
+    t.top = *reinterpret_cast<const flow2 *>(b + t.Y.lo * G.w + t.xb);
+    t.bot = *reinterpret_cast<const flow2 *>(b + t.Y.hi * G.w + t.xb);
+    return t;
+}
+// the glue of a thread's PPT pixels: every load is issued before any interpolation; emit(j) as soon as f[j] is there
+template <int PPT, typename Emit>
+__device__ __forceinline__ void glue_pixels(const f32x2 *__restrict__ b, const int *yy, const int *xx, const GlueParams &G, f32x2 *f, Emit emit)
+{
+    GlueTaps t[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) t[j] = glue_fetch(b, yy[j], xx[j], G);
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        const bool l1 = t[j].X.lo != t[j].xb, h1 = t[j].X.hi != t[j].xb;
+        f[j] = glue_interp(l1 ? t[j].top.b : t[j].top.a, h1 ? t[j].top.b : t[j].top.a, l1 ? t[j].bot.b : t[j].bot.a, h1 ? t[j].bot.b : t[j].bot.a,
+                           t[j].X.t, t[j].Y.t, G);
+        emit(j);
+    }
+}
+
 __global__ __launch_bounds__(256) void flow_resize_scale_kernel(const float *__restrict__ flow, int B, float *__restrict__ out, int oh, int ow,
                                                                 GlueParams G)
 {
@@ -514,11 +551,7 @@ __global__ __launch_bounds__(256) void flow_resize_scale_kernel(const float *__r
     const int oy = rem / ow, ox = rem - oy * ow;
     const Lerp Y = legacy_coord(oy, G.ry, h), X = legacy_coord(ox, G.rx, w);
     const f32x2 *b = reinterpret_cast<const f32x2 *>(flow) + (long long)n * h * w;
-    f32x2 tl = b[Y.lo * w + X.lo], tr = b[Y.lo * w + X.hi], bl = b[Y.hi * w + X.lo], br = b[Y.hi * w + X.hi];
-    f32x2 o;
-    o.x = glue_post_x(lerp2(glue_pre(tl.x, G), glue_pre(tr.x, G), glue_pre(bl.x, G), glue_pre(br.x, G), X.t, Y.t), G);
-    o.y = glue_post_y(lerp2(glue_pre(tl.y, G), glue_pre(tr.y, G), glue_pre(bl.y, G), glue_pre(br.y, G), X.t, Y.t), G);
-    reinterpret_cast<f32x2 *>(out)[idx] = o;
+    reinterpret_cast<f32x2 *>(out)[idx] = glue_interp(b[Y.lo * w + X.lo], b[Y.lo * w + X.hi], b[Y.hi * w + X.lo], b[Y.hi * w + X.hi], X.t, Y.t, G);
 }
 
 // tiled forms (defined next to the warp's tile kernel below); they return hipErrorNotSupported when a shape is not theirs
@@ -577,6 +610,30 @@ hipError_t launch_resize_bilinear(const float *x, int B, int h, int w, int C, fl
 // zero, all four clipped into the image, weights from the CLIPPED corners (A.6).
 // The saturating v_cvt_i32_f32 keeps NaN/inf flows inside the image (no fault).
 // ---------------------------------------------------------------------------------
+// the four corners (a = (y0,x0), b = (y1,x0), c = (y0,x1), d = (y1,x1)) and weights of the sample point (x, y): the one statement
+// of tf_warp's arithmetic, for the pixel kernel and every tile kernel
+struct WarpTaps { int x0, x1, y0, y1; float wa, wb, wc, wd; };
+__device__ __forceinline__ WarpTaps tf_warp_taps(float x, float y, int H, int W)
+{
+    // Clamp BEFORE the conversion: float->int of an out-of-range value and x0 + 1 at INT_MAX are
+    // undefined in C++ (the optimiser folds the clips below around them and a NaN/inf flow then
+    // indexes out of bounds).  Inside [-2, W] nothing changes; outside, both corners still end
+    // up clipped to the same border pixel exactly as in the reference.
+    int x0 = (int)fminf(fmaxf(x, -2.f), (float)W), y0 = (int)fminf(fmaxf(y, -2.f), (float)H);
+    int x1 = x0 + 1, y1 = y0 + 1;
+    WarpTaps t;
+    t.x0 = min(max(x0, 0), W - 1); t.x1 = min(max(x1, 0), W - 1);
+    t.y0 = min(max(y0, 0), H - 1); t.y1 = min(max(y1, 0), H - 1);
+    const float x0f = (float)t.x0, x1f = (float)t.x1, y0f = (float)t.y0, y1f = (float)t.y1;
+    t.wa = (x1f - x) * (y1f - y); t.wb = (x1f - x) * (y - y0f);
+    t.wc = (x - x0f) * (y1f - y); t.wd = (x - x0f) * (y - y0f);
+    return t;
+}
+__device__ __forceinline__ float tf_warp_blend(const WarpTaps &t, float Ia, float Ib, float Ic, float Id)
+{
+    return ((t.wa * Ia + t.wb * Ib) + t.wc * Ic) + t.wd * Id;      // tf.add_n order
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void warp_flow_kernel(const float *__restrict__ img, const float *__restrict__ flow,
                                                         float *__restrict__ out, int B, int H, int W, int Cdyn)
@@ -588,24 +645,13 @@ __global__ __launch_bounds__(256) void warp_flow_kernel(const float *__restrict_
     const int rem = (int)(idx - (long long)n * H * W);
     const int yy = rem / W, xx = rem - yy * W;
     const f32x2 f = reinterpret_cast<const f32x2 *>(flow)[idx];
-    const float x = (float)xx + f.x, y = (float)yy + f.y;
-    // Clamp BEFORE the conversion: float->int of an out-of-range value and x0 + 1 at INT_MAX are
-    // undefined in C++ (the optimiser folds the clips below around them and a NaN/inf flow then
-    // indexes out of bounds).  Inside [-2, W] nothing changes; outside, both corners still end
-    // up clipped to the same border pixel exactly as in the reference.
-    int x0 = (int)fminf(fmaxf(x, -2.f), (float)W), y0 = (int)fminf(fmaxf(y, -2.f), (float)H);
-    int x1 = x0 + 1, y1 = y0 + 1;
-    x0 = min(max(x0, 0), W - 1); x1 = min(max(x1, 0), W - 1);
-    y0 = min(max(y0, 0), H - 1); y1 = min(max(y1, 0), H - 1);
-    const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-    const float wa = (x1f - x) * (y1f - y), wb = (x1f - x) * (y - y0f);
-    const float wc = (x - x0f) * (y1f - y), wd = (x - x0f) * (y - y0f);
+    const WarpTaps t = tf_warp_taps((float)xx + f.x, (float)yy + f.y, H, W);
     const int Cc = C > 0 ? C : Cdyn;
     const float *base = img + (long long)n * H * W * Cc;
-    const float *Ia = base + ((long long)y0 * W + x0) * Cc, *Ib = base + ((long long)y1 * W + x0) * Cc;
-    const float *Ic = base + ((long long)y0 * W + x1) * Cc, *Id = base + ((long long)y1 * W + x1) * Cc;
+    const float *Ia = base + ((long long)t.y0 * W + t.x0) * Cc, *Ib = base + ((long long)t.y1 * W + t.x0) * Cc;
+    const float *Ic = base + ((long long)t.y0 * W + t.x1) * Cc, *Id = base + ((long long)t.y1 * W + t.x1) * Cc;
     float *o = out + idx * Cc;
-    for (int c = 0; c < Cc; ++c) o[c] = ((wa * Ia[c] + wb * Ib[c]) + wc * Ic[c]) + wd * Id[c];   // tf.add_n order
+    for (int c = 0; c < Cc; ++c) o[c] = tf_warp_blend(t, Ia[c], Ib[c], Ic[c], Id[c]);
 }
 
 // ---------------------------------------------------------------------------------
@@ -616,72 +662,85 @@ __global__ __launch_bounds__(256) void warp_flow_kernel(const float *__restrict_
 // What bounds it (profiles/README.md, "r02 warp study"; PMC TCP_TOTAL_CACHE_ACCESSES): the L1 looks up one 64-byte piece per
 // four lanes per cycle, and a gather of 12-byte pixels costs 1.75 lookups per four lanes even when they are neighbours -- the
 // L1 tag pipe saturates before HBM does.  So the kernel minimises lookups per pixel:
-//   * a workgroup owns a 16 x 32 tile of ONE sample's output pixels and every wave instruction works on a 4 x 16 patch, so the
-//     lines a gather instruction touches are a compact 2-D footprint ((4 + spread) rows x (16 + spread) pixels) whether or not
+//   * the tile skeleton of tile3.h (16 x 32 tile of ONE sample, 4 x 16 wave patches, XCD-contiguous tile order): the lines a
+//     gather instruction touches are a compact 2-D footprint ((4 + spread) rows x (16 + spread) pixels) whether or not
 //     the flow is smooth (a 1-D run of 64 pixels touches 64 x `spread` lines once neighbouring flows differ: 0.37 -> 0.55 of
 //     8 TB/s on the benchmark's flows, which move neighbouring pixels' sample points 0.6 px apart per pixel);
 //   * one 3-dword load per corner (never three scalar ones), both pixels of a thread's loads issued back to back;
 //   * results leave through LDS as 16-byte stores of whole 384-byte tile rows (W % 4 == 0; otherwise 12-byte stores);
-//   * workgroups are numbered through the XCD map: one XCD's L2 sees a contiguous band of tile rows;
 //   * no 64-bit divisions.
-// The arithmetic is the sequence of warp_flow_kernel / flow_resize_scale_kernel above, statement for statement: results are
-// bit-identical to the two-launch path (tests: test_warp_tiled_kernel_bit_exact_vs_fp32_oracle, test_fused_glue_warp_bit_identical).
+// The arithmetic is tf_warp_taps / tf_warp_blend / glue_fetch / glue_interp, the functions the one-thread-per-pixel kernels call:
+// results are bit-identical to the two-launch path (tests: test_warp_tiled_kernel_bit_exact_vs_fp32_oracle,
+// test_fused_glue_warp_bit_identical).
 // Rejected after measurement (tools/warp_variants.inc): 1-D 1024-pixel tiles with LDS-staged stores, an LDS-staged source
 // window (bounding box of the tile's corners, coalesced fill, gathers from LDS) and its persistent, flow-prefetching form.
 // ---------------------------------------------------------------------------------
-struct __attribute__((packed, aligned(4))) rgb3 { float r, g, b; };
-struct __attribute__((packed, aligned(8))) flow2 { f32x2 a, b; };     // two neighbouring flow pixels (8-byte aligned, 16 bytes)
+using WarpTile = Tile3<>;
 
-// a workgroup owns a TH x TW tile of ONE sample's output pixels; a wave instruction works on a WH x WW patch (WH * WW = 64)
+// tf_warp of a thread's PPT pixels (yy, xx) displaced by f, out of one sample's frame: every gather is issued before any blend,
+// and pixel j goes to emit(j, rgb) as soon as it is blended (its store overlaps the later pixels' loads).
+// U8: the frame is BGR bytes and a pixel is swap(frame) / 255 through the 256-entry table `lut` (channels 2, 1, 0)
+template <bool U8, int PPT, typename Emit>
+__device__ __forceinline__ void warp3_pixels(const void *__restrict__ frame, const float *lut, const int *yy, const int *xx, const f32x2 *f,
+                                             int H, int W, Emit emit)
+{
+    auto px = [&](int y, int x) {
+        if constexpr (U8) {
+            const unsigned char *q = reinterpret_cast<const unsigned char *>(frame) + ((long long)y * W + x) * 3;
+            rgb3 p; p.r = lut[q[2]]; p.g = lut[q[1]]; p.b = lut[q[0]];
+            return p;
+        } else {
+            return reinterpret_cast<const rgb3 *>(frame)[y * W + x];
+        }
+    };
+    WarpTaps t[PPT];
+    rgb3 Ia[PPT], Ib[PPT], Ic[PPT], Id[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        t[j] = tf_warp_taps((float)xx[j] + f[j].x, (float)yy[j] + f[j].y, H, W);
+        Ia[j] = px(t[j].y0, t[j].x0); Ib[j] = px(t[j].y1, t[j].x0); Ic[j] = px(t[j].y0, t[j].x1); Id[j] = px(t[j].y1, t[j].x1);
+    }
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        rgb3 r;
+        r.r = tf_warp_blend(t[j], Ia[j].r, Ib[j].r, Ic[j].r, Id[j].r);
+        r.g = tf_warp_blend(t[j], Ia[j].g, Ib[j].g, Ic[j].g, Id[j].g);
+        r.b = tf_warp_blend(t[j], Ia[j].b, Ib[j].b, Ic[j].b, Id[j].b);
+        emit(j, r);
+    }
+}
+// quantise_output_kernel's: truncate, saturate where numpy is undefined, channels swapped back
+__device__ __forceinline__ void quantise3(const rgb3 &r, unsigned char *o)
+{
+    const float rr[3] = {r.r, r.g, r.b};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (unsigned char)fminf(fmaxf(truncf(rr[2 - c] * 255.0f), 0.f), 255.f);
+}
+
 template <bool FUSED, bool WRITE_FLOW, int WH, int WW, int TW, int PPT, bool REMAP = true, bool NT = false, bool STAGE = false>
 __global__ __launch_bounds__(256) void warp3_tile_kernel(const float *__restrict__ img, const float *__restrict__ flow,
                                                          float *__restrict__ out, float *__restrict__ outflow, int B,
                                                          int H, int W, int tiles_x, int tiles_y, GlueParams G)
 {
-    static_assert(WH * WW == 64 && TW % WW == 0 && (4 * PPT) % (TW / WW) == 0, "patch / tile shapes");
-    constexpr int PPR = TW / WW;                    // patches per tile row
-    constexpr int TH = WH * (4 * PPT) / PPR;
-    __shared__ __attribute__((aligned(16))) float stage[STAGE ? TH * TW * 3 : 4];
-    unsigned bx = blockIdx.x, by, bz;
-    if (REMAP) xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int ty0 = (trem / tiles_x) * TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    using T = Tile3<WH, WW, TW, PPT>;
+    __shared__ __attribute__((aligned(16))) float stage[STAGE ? T::TH * TW * 3 : 4];
+    const T tile(tiles_x, tiles_y, REMAP);
+    const int n = tile.n;
     const long long HW = (long long)H * W;
 
     int yy[PPT], xx[PPT];
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int q = j * 4 + wave;
-        yy[j] = ty0 + (q / PPR) * WH + lane / WW;
-        xx[j] = tx0 + (q % PPR) * WW + lane % WW;
+        yy[j] = tile.y(j); xx[j] = tile.x(j);
         ok[j] = yy[j] < H && xx[j] < W;
         if (!ok[j]) { yy[j] = 0; xx[j] = 0; }
     }
     f32x2 f[PPT];
     if (FUSED) {
-        f32x2 tl[PPT], tr[PPT], bl[PPT], br[PPT];
-        Lerp Y[PPT], X[PPT];
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-            Y[j] = legacy_coord(yy[j], G.ry, G.h); X[j] = legacy_coord(xx[j], G.rx, G.w);
-            const f32x2 *b = reinterpret_cast<const f32x2 *>(flow) + (long long)n * G.h * G.w;
-            // the left/right taps of a row are neighbours (hi = lo + 1, or both the last column): ONE 16-byte load per row
-            // -- half the L1 lookups of four 8-byte gathers -- of the source pixels (xb, xb + 1), xb = min(lo, w - 2) (w >= 2: host)
-            const int xb = min(X[j].lo, G.w - 2);
-            const flow2 top = *reinterpret_cast<const flow2 *>(b + Y[j].lo * G.w + xb), bot = *reinterpret_cast<const flow2 *>(b + Y[j].hi * G.w + xb);
-            const bool l1 = X[j].lo != xb, h1 = X[j].hi != xb;
-            tl[j] = l1 ? top.b : top.a; tr[j] = h1 ? top.b : top.a;
-            bl[j] = l1 ? bot.b : bot.a; br[j] = h1 ? bot.b : bot.a;
-        }
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-            f[j].x = glue_post_x(lerp2(glue_pre(tl[j].x, G), glue_pre(tr[j].x, G), glue_pre(bl[j].x, G), glue_pre(br[j].x, G), X[j].t, Y[j].t), G);
-            f[j].y = glue_post_y(lerp2(glue_pre(tl[j].y, G), glue_pre(tr[j].y, G), glue_pre(bl[j].y, G), glue_pre(br[j].y, G), X[j].t, Y[j].t), G);
+        glue_pixels<PPT>(reinterpret_cast<const f32x2 *>(flow) + (long long)n * G.h * G.w, yy, xx, G, f, [&](int j) {
             if (WRITE_FLOW && ok[j]) reinterpret_cast<f32x2 *>(outflow)[n * HW + (long long)yy[j] * W + xx[j]] = f[j];
-        }
+        });
     } else {
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
@@ -689,68 +748,35 @@ __global__ __launch_bounds__(256) void warp3_tile_kernel(const float *__restrict
             f[j] = NT ? __builtin_nontemporal_load(fp) : *fp;
         }
     }
-    float wa[PPT], wb[PPT], wc[PPT], wd[PPT];
-    rgb3 Ia[PPT], Ib[PPT], Ic[PPT], Id[PPT];
-    const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + n * HW;
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const float x = (float)xx[j] + f[j].x, y = (float)yy[j] + f[j].y;
-        int x0 = (int)fminf(fmaxf(x, -2.f), (float)W), y0 = (int)fminf(fmaxf(y, -2.f), (float)H);
-        int x1 = x0 + 1, y1 = y0 + 1;
-        x0 = min(max(x0, 0), W - 1); x1 = min(max(x1, 0), W - 1);
-        y0 = min(max(y0, 0), H - 1); y1 = min(max(y1, 0), H - 1);
-        const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-        wa[j] = (x1f - x) * (y1f - y); wb[j] = (x1f - x) * (y - y0f);
-        wc[j] = (x - x0f) * (y1f - y); wd[j] = (x - x0f) * (y - y0f);
-        Ia[j] = b[y0 * W + x0]; Ib[j] = b[y1 * W + x0]; Ic[j] = b[y0 * W + x1]; Id[j] = b[y1 * W + x1];
-    }
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        rgb3 r;
-        r.r = ((wa[j] * Ia[j].r + wb[j] * Ib[j].r) + wc[j] * Ic[j].r) + wd[j] * Id[j].r;      // tf.add_n order
-        r.g = ((wa[j] * Ia[j].g + wb[j] * Ib[j].g) + wc[j] * Ic[j].g) + wd[j] * Id[j].g;
-        r.b = ((wa[j] * Ia[j].b + wb[j] * Ib[j].b) + wc[j] * Ic[j].b) + wd[j] * Id[j].b;
+    warp3_pixels<false, PPT>(reinterpret_cast<const rgb3 *>(img) + n * HW, nullptr, yy, xx, f, H, W, [&](int j, const rgb3 &r) {
         if (STAGE) {
-            const int q = j * 4 + wave;
-            *reinterpret_cast<rgb3 *>(stage + (((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW) * 3) = r;
+            *reinterpret_cast<rgb3 *>(stage + tile.staged(j) * 3) = r;
         } else if (ok[j]) {
             float *o = out + (n * HW + (long long)yy[j] * W + xx[j]) * 3;
             if (NT) { __builtin_nontemporal_store(r.r, o); __builtin_nontemporal_store(r.g, o + 1); __builtin_nontemporal_store(r.b, o + 2); }
             else *reinterpret_cast<rgb3 *>(o) = r;
         }
-    }
-    if (STAGE) {       // W % 4 == 0 (host): a tile row is TW*12 bytes from a 16-byte aligned address; 16-byte stores, dwords at a ragged right edge
-        __syncthreads();
-        constexpr int R4 = TW * 3 / 4;
-        const int vw3 = min(TW, W - tx0) * 3;
-        for (int e = threadIdx.x; e < TH * R4; e += 256) {
-            const int row = e / R4, c4 = e - row * R4;
-            if (ty0 + row >= H || c4 * 4 >= vw3) continue;
-            float *o = out + (n * HW + (long long)(ty0 + row) * W + tx0) * 3 + c4 * 4;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(stage + row * TW * 3 + c4 * 4);
-            if (c4 * 4 + 4 <= vw3) { if (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(o)); else *reinterpret_cast<f32x4 *>(o) = v; }
-            else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = v[i];
-        }
-    }
+    });
+    if (STAGE) tile.template store_rows<3, NT>(stage, out, H, W);
 }
-
-constexpr int WT_WH = 4, WT_WW = 16, WT_TW = 32, WT_PPT = 2, WT_TH = WT_WH * (4 * WT_PPT) / (WT_TW / WT_WW);      // 16 x 32 tile
 
 static bool warp3_ok(const void *img, const void *out, const void *outflow, int B, int H, int W, int C)
 {
     return C == 3 && (long long)B * H * W < (1ll << 31) && (((uintptr_t)img | (uintptr_t)out | (uintptr_t)outflow) & 15) == 0;
 }
 
+// the caller has checked warp3_ok
 template <bool FUSED, bool WRITE_FLOW>
 static hipError_t launch_warp3(int slot, double alg_bytes, const float *img, const float *flow, float *out, float *outflow, int B, int H,
                                int W, const GlueParams &G, hipStream_t stream)
 {
-    const int tx = (W + WT_TW - 1) / WT_TW, ty = (H + WT_TH - 1) / WT_TH;
-    const dim3 grid((unsigned)((long long)tx * ty * B)), block(256);
-    if ((W & 3) == 0)
-        return launch_timed(slot, alg_bytes, warp3_tile_kernel<FUSED, WRITE_FLOW, WT_WH, WT_WW, WT_TW, WT_PPT, true, false, true>, grid, block,
+    int tx, ty;
+    dim3 grid;
+    WarpTile::plan(B, H, W, (long long)B * H * W, tx, ty, grid);
+    if (WarpTile::staged_ok(out, W, 3))
+        return launch_timed(slot, alg_bytes, warp3_tile_kernel<FUSED, WRITE_FLOW, WT_WH, WT_WW, WT_TW, WT_PPT, true, false, true>, grid, dim3(256),
                             stream, img, flow, out, outflow, B, H, W, tx, ty, G);
-    return launch_timed(slot, alg_bytes, warp3_tile_kernel<FUSED, WRITE_FLOW, WT_WH, WT_WW, WT_TW, WT_PPT, true, false, false>, grid, block,
+    return launch_timed(slot, alg_bytes, warp3_tile_kernel<FUSED, WRITE_FLOW, WT_WH, WT_WW, WT_TW, WT_PPT, true, false, false>, grid, dim3(256),
                         stream, img, flow, out, outflow, B, H, W, tx, ty, G);
 }
 
@@ -758,7 +784,7 @@ hipError_t launch_warp_flow(const float *img, const float *flow, float *out, int
 {
     const long long total = (long long)B * H * W;
     if (total == 0) return hipSuccess;
-    if (warp3_ok(img, out, nullptr, B, H, W, C) && (long long)((W + WT_TW - 1) / WT_TW) * ((H + WT_TH - 1) / WT_TH) * B < (1ll << 31))
+    if (warp3_ok(img, out, nullptr, B, H, W, C))
         return launch_warp3<false, false>(HBM_SLOT_WARP, 32.0 * total, img, flow, out, nullptr, B, H, W, GlueParams{}, stream);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
     const double bytes = (8.0 + 8.0 * C) * total;
@@ -786,29 +812,27 @@ hipError_t launch_flow_glue_warp(const float *flow, int B, int h, int w, const f
 // table + eight adds of the upsampled predict_flow3, pf2_tile_kernel above), the glue of main:497-498 and tf_warp (main:514,
 // warp3_tile_kernel<FUSED>).  A workgroup owns the same 16 x 32 tile of OUTPUT pixels the warp kernel does.  The glue's bilinear taps
 // of that tile reach a small rectangle of predict_flow2 (<= 18 x 34 pixels when the output is no smaller than the flow grid); the
-// workgroup computes exactly that rectangle -- statement for statement pf2_tile_kernel's sums, out of a tap-table window in LDS -- keeps
-// it in LDS, writes the part it OWNS to the returned predict_flow2 tensor (rows [lo(ty0), lo(ty0 + TH)), the last tile to the end:
-// neighbouring tiles' rectangles overlap by a pixel or two, every pixel is written once), and glue + warp read their four flow taps
-// from LDS.  predict_flow2 is written (it is a returned tensor) but never re-read: 33 MB less traffic at B=8 512x512, one launch
-// boundary less, and the warp's L1 tag pipe -- its limit -- loses the two flow lookups per pixel.  Same fp32 operations in the same
-// order as the two launches: bit-identical (tests/test_gpu_parity.py::test_fused_tail_bit_identical).
+// workgroup computes exactly that rectangle -- statement for statement pf2_tile_kernel's sums, out of a tap-table window
+// in LDS -- keeps it in LDS, writes the part it OWNS to the returned predict_flow2 tensor (rows [lo(ty0), lo(ty0 + TH)), the last
+// tile to the end: neighbouring tiles' rectangles overlap by a pixel or two, every pixel is written once), and glue + warp read
+// their four flow taps from LDS.  predict_flow2 is written (it is a returned tensor) but never re-read: 33 MB less traffic at B=8
+// 512x512, one launch boundary less, and the warp's L1 tag pipe -- its limit -- loses the two flow lookups per pixel.  Same fp32
+// operations in the same order as the two launches: bit-identical (tests/test_gpu_parity.py::test_fused_tail_bit_identical).
 // ---------------------------------------------------------------------------------
 constexpr int FT_PF_CAP = 640, FT_T_CAP = 96;       // predict_flow2 window pixels (18 x 34 = 612) and tap-table window pixels (7 x 11 = 77) held in LDS
 struct TailParams {
     int h2, w2, h3, w3, H, W;                       // tap table grid, predict_flow3 grid, network input size (predict_flow2 is (H-2) x (W-2))
     float nsy, nsx, usy, usx;
 };
-// U8 = the clip driver's frame path (warp3_u8_tile_kernel's statements: BGR bytes -> swap / 255 through the 256-entry table, the warp,
-// truncating quantiser, bytes out); otherwise fp32 frames in and out (warp3_tile_kernel's)
+// U8 = the clip driver's frame path (BGR bytes -> swap / 255 through the 256-entry table, the warp, truncating quantiser, bytes out:
+// warp3_u8_tile_kernel's frame handling); otherwise fp32 frames in and out (warp3_tile_kernel's)
 template <bool WRITE_FLOW, bool STAGE, bool U8>
 __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restrict__ T, const float *__restrict__ bias2, const float *__restrict__ pf3,
                                                             float *__restrict__ pf2, const void *__restrict__ img_, void *__restrict__ out_,
                                                             float *__restrict__ outflow, int B, int OH, int OW, int tiles_x, int tiles_y,
                                                             TailParams P, GlueParams G)
 {
-    const float *__restrict__ img = reinterpret_cast<const float *>(img_);
-    float *__restrict__ out = reinterpret_cast<float *>(out_);
-    constexpr int TH = WT_TH, TW = WT_TW, WH = WT_WH, WW = WT_WW, PPT = WT_PPT, PPR = TW / WW;
+    constexpr int TH = WarpTile::TH, TW = WarpTile::TW, PPT = WarpTile::PPT;
     // the tap-table window is dead once predict_flow2's rectangle is in `pfw` (second barrier): the output staging tile takes its place
     // (12 KB of LDS per workgroup instead of 23: the wave limit of the register file, not LDS, bounds the occupancy)
     constexpr int TAB_FLOATS = FT_T_CAP * 18, STAGE_FLOATS = STAGE ? TH * TW * 3 : 4;
@@ -817,18 +841,14 @@ __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restr
     float *stage = tab;
     __shared__ float lut[U8 ? 256 : 1];
     if (U8) lut[threadIdx.x] = (float)threadIdx.x / 255.0f;          // 256 threads; read after the barriers below
-    unsigned bx, by, bz;
-    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
-    const int ty0 = tyi * TH, tx0 = txi * TW;
+    const WarpTile tile(tiles_x, tiles_y);
+    const int n = tile.n, ty0 = tile.ty0, tx0 = tile.tx0;
     const int h = G.h, w = G.w;                       // predict_flow2's grid
     // ---- the predict_flow2 rectangle: what the tile's glue taps reach, extended to what the tile owns
     const int yl = min(ty0 + TH - 1, OH - 1), xl = min(tx0 + TW - 1, OW - 1);
     const int wy0 = legacy_coord(ty0, G.ry, h).lo, wx0 = legacy_coord(tx0, G.rx, w).lo;
-    const int own_y1 = tyi == tiles_y - 1 ? h : legacy_coord(ty0 + TH, G.ry, h).lo;
-    const int own_x1 = txi == tiles_x - 1 ? w : legacy_coord(tx0 + TW, G.rx, w).lo;
+    const int own_y1 = ty0 / TH == tiles_y - 1 ? h : legacy_coord(ty0 + TH, G.ry, h).lo;
+    const int own_x1 = tx0 / TW == tiles_x - 1 ? w : legacy_coord(tx0 + TW, G.rx, w).lo;
     const int wy1 = max(legacy_coord(yl, G.ry, h).hi, own_y1 - 1), wx1 = max(legacy_coord(xl, G.rx, w).hi, own_x1 - 1);
     const int WC = wx1 - wx0 + 1, npf = (wy1 - wy0 + 1) * WC;          // <= FT_PF_CAP: checked on the host
     // ---- its tap-table window (indices into the UNPADDED concat2 grid: -1 and h2 / w2 are the zero ring), pf2_tile_kernel's way
@@ -879,16 +899,13 @@ __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restr
         }
     }
     __syncthreads();
-    // ---- glue + warp of the tile's output pixels (warp3_tile_kernel<FUSED>'s statements; the four flow taps come from LDS)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // ---- glue + warp of the tile's output pixels (warp3_tile_kernel<FUSED>'s; the four flow taps come from LDS)
     const long long HW = (long long)OH * OW;
     int yy[PPT], xx[PPT];
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int q = j * 4 + wave;
-        yy[j] = ty0 + (q / PPR) * WH + lane / WW;
-        xx[j] = tx0 + (q % PPR) * WW + lane % WW;
+        yy[j] = tile.y(j); xx[j] = tile.x(j);
         ok[j] = yy[j] < OH && xx[j] < OW;
         if (!ok[j]) { yy[j] = ty0; xx[j] = tx0; }              // a pixel of this tile (its taps are inside the LDS rectangle); never stored
     }
@@ -896,90 +913,19 @@ __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restr
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
         const Lerp Y = legacy_coord(yy[j], G.ry, h), X = legacy_coord(xx[j], G.rx, w);
-        const f32x2 tl = pfw[(Y.lo - wy0) * WC + (X.lo - wx0)], tr = pfw[(Y.lo - wy0) * WC + (X.hi - wx0)];
-        const f32x2 bl = pfw[(Y.hi - wy0) * WC + (X.lo - wx0)], br = pfw[(Y.hi - wy0) * WC + (X.hi - wx0)];
-        f[j].x = glue_post_x(lerp2(glue_pre(tl.x, G), glue_pre(tr.x, G), glue_pre(bl.x, G), glue_pre(br.x, G), X.t, Y.t), G);
-        f[j].y = glue_post_y(lerp2(glue_pre(tl.y, G), glue_pre(tr.y, G), glue_pre(bl.y, G), glue_pre(br.y, G), X.t, Y.t), G);
+        f[j] = glue_interp(pfw[(Y.lo - wy0) * WC + (X.lo - wx0)], pfw[(Y.lo - wy0) * WC + (X.hi - wx0)],
+                           pfw[(Y.hi - wy0) * WC + (X.lo - wx0)], pfw[(Y.hi - wy0) * WC + (X.hi - wx0)], X.t, Y.t, G);
         if (WRITE_FLOW && ok[j]) reinterpret_cast<f32x2 *>(outflow)[n * HW + (long long)yy[j] * OW + xx[j]] = f[j];
     }
-    float wa[PPT], wb[PPT], wc_[PPT], wd[PPT];
-    rgb3 Ia[PPT], Ib[PPT], Ic[PPT], Id[PPT];
-    const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + n * HW;
-    const unsigned char *b8 = reinterpret_cast<const unsigned char *>(img_) + n * HW * 3;
-    auto px = [&](int y, int x) {                                     // fp32 frame, or swap(frame) / 255: channels 2, 1, 0 of the BGR pixel
-        if constexpr (U8) {
-            const unsigned char *q = b8 + ((long long)y * OW + x) * 3;
-            rgb3 r; r.r = lut[q[2]]; r.g = lut[q[1]]; r.b = lut[q[0]];
-            return r;
-        } else {
-            return b[y * OW + x];
-        }
-    };
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const float x = (float)xx[j] + f[j].x, y = (float)yy[j] + f[j].y;
-        int x0 = (int)fminf(fmaxf(x, -2.f), (float)OW), y0 = (int)fminf(fmaxf(y, -2.f), (float)OH);
-        int x1 = x0 + 1, y1 = y0 + 1;
-        x0 = min(max(x0, 0), OW - 1); x1 = min(max(x1, 0), OW - 1);
-        y0 = min(max(y0, 0), OH - 1); y1 = min(max(y1, 0), OH - 1);
-        const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-        wa[j] = (x1f - x) * (y1f - y); wb[j] = (x1f - x) * (y - y0f);
-        wc_[j] = (x - x0f) * (y1f - y); wd[j] = (x - x0f) * (y - y0f);
-        Ia[j] = px(y0, x0); Ib[j] = px(y1, x0); Ic[j] = px(y0, x1); Id[j] = px(y1, x1);
-    }
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        rgb3 r;
-        r.r = ((wa[j] * Ia[j].r + wb[j] * Ib[j].r) + wc_[j] * Ic[j].r) + wd[j] * Id[j].r;      // tf.add_n order
-        r.g = ((wa[j] * Ia[j].g + wb[j] * Ib[j].g) + wc_[j] * Ic[j].g) + wd[j] * Id[j].g;
-        r.b = ((wa[j] * Ia[j].b + wb[j] * Ib[j].b) + wc_[j] * Ic[j].b) + wd[j] * Id[j].b;
-        const int q = j * 4 + wave;
-        const int spix = ((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW;
-        if constexpr (U8) {                           // quantise_output_kernel's: truncate, saturate, channels swapped back
-            unsigned char *o = reinterpret_cast<unsigned char *>(stage) + spix * 3;
-            const float rr[3] = {r.r, r.g, r.b};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = (unsigned char)fminf(fmaxf(truncf(rr[2 - c] * 255.0f), 0.f), 255.f);
-        } else if (STAGE) {
-            *reinterpret_cast<rgb3 *>(stage + spix * 3) = r;
-        } else if (ok[j]) {
-            *reinterpret_cast<rgb3 *>(out + (n * HW + (long long)yy[j] * OW + xx[j]) * 3) = r;
-        }
-    }
-    if constexpr (U8) {
-        __syncthreads();
-        const unsigned char *sb = reinterpret_cast<const unsigned char *>(stage);
-        unsigned char *out8 = reinterpret_cast<unsigned char *>(out_);
-        // a tile row is TW*3 = 96 bytes; 4-byte stores where rows start on a 4-byte boundary (OW % 4 == 0), bytes otherwise / at a ragged edge
-        const int vw3 = min(TW, OW - tx0) * 3;
-        if ((OW & 3) == 0) {
-            constexpr int R4 = TW * 3 / 4;
-            for (int e = threadIdx.x; e < TH * R4; e += 256) {
-                const int row = e / R4, c4 = e - row * R4;
-                if (ty0 + row >= OH || c4 * 4 >= vw3) continue;
-                unsigned char *o = out8 + (n * HW + (long long)(ty0 + row) * OW + tx0) * 3 + c4 * 4;
-                if (c4 * 4 + 4 <= vw3) *reinterpret_cast<unsigned *>(o) = *reinterpret_cast<const unsigned *>(sb + row * TW * 3 + c4 * 4);
-                else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = sb[row * TW * 3 + c4 * 4 + i];
-            }
-        } else {
-            for (int e = threadIdx.x; e < TH * TW * 3; e += 256) {
-                const int row = e / (TW * 3), c = e - row * (TW * 3);
-                if (ty0 + row < OH && c < vw3) out8[(n * HW + (long long)(ty0 + row) * OW + tx0) * 3 + c] = sb[e];
-            }
-        }
-    } else if (STAGE) {       // OW % 4 == 0 (host): a tile row is TW*12 bytes from a 16-byte aligned address
-        __syncthreads();
-        constexpr int R4 = TW * 3 / 4;
-        const int vw3 = min(TW, OW - tx0) * 3;
-        for (int e = threadIdx.x; e < TH * R4; e += 256) {
-            const int row = e / R4, c4 = e - row * R4;
-            if (ty0 + row >= OH || c4 * 4 >= vw3) continue;
-            float *o = out + (n * HW + (long long)(ty0 + row) * OW + tx0) * 3 + c4 * 4;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(stage + row * TW * 3 + c4 * 4);
-            if (c4 * 4 + 4 <= vw3) *reinterpret_cast<f32x4 *>(o) = v;
-            else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = v[i];
-        }
-    }
+    warp3_pixels<U8, PPT>(U8 ? (const void *)(reinterpret_cast<const unsigned char *>(img_) + n * HW * 3)
+                             : (const void *)(reinterpret_cast<const rgb3 *>(img_) + n * HW), lut, yy, xx, f, OH, OW, [&](int j, const rgb3 &r) {
+        if constexpr (U8) quantise3(r, reinterpret_cast<unsigned char *>(stage) + tile.staged(j) * 3);
+        else if (STAGE) *reinterpret_cast<rgb3 *>(stage + tile.staged(j) * 3) = r;
+        else if (ok[j]) reinterpret_cast<rgb3 *>(out_)[n * HW + (long long)yy[j] * OW + xx[j]] = r;
+    });
+    // a tile row of bytes is TW*3 = 96 bytes; 4-byte stores where rows start on a 4-byte boundary (OW % 4 == 0), bytes otherwise
+    if constexpr (U8) tile.template store_rows<3>(reinterpret_cast<const unsigned char *>(stage), reinterpret_cast<unsigned char *>(out_), OH, OW, (OW & 3) == 0);
+    else if (STAGE) tile.template store_rows<3>(stage, reinterpret_cast<float *>(out_), OH, OW);
 }
 
 static Lerp legacy_coord_host(int o, float scale, int n_in)
@@ -1002,13 +948,14 @@ static hipError_t launch_tail(const float *T, int B, int h2, int w2, const float
     if (B < 1 || h < 1 || w < 2 || oh < 1 || ow < 1) return hipErrorNotSupported;
     if ((uintptr_t)pf2 & 7) return hipErrorNotSupported;
     if (u8) {
-        if ((long long)B * oh * ow >= (1ll << 31) / 3 || ((uintptr_t)outflow & 7) || ((uintptr_t)out & 3)) return hipErrorNotSupported;
+        if (((uintptr_t)outflow & 7) || ((uintptr_t)out & 3)) return hipErrorNotSupported;
     } else if (!warp3_ok(img, out, outflow, B, oh, ow, 3)) return hipErrorNotSupported;
     const GlueParams G = glue_params(h, w, oh, ow, H, W);
     TailParams P{h2, w2, h3, w3, H, W, H > 1 ? (float)(h2 + 2 - 1) / (float)(H - 1) : 0.f, W > 1 ? (float)(w2 + 2 - 1) / (float)(W - 1) : 0.f,
                  (float)h3 / (float)h, (float)w3 / (float)w};
-    const int tx = (ow + WT_TW - 1) / WT_TW, ty = (oh + WT_TH - 1) / WT_TH;
-    if ((long long)tx * ty * B >= (1ll << 31)) return hipErrorNotSupported;
+    int tx, ty;
+    dim3 grid;
+    if (!WarpTile::plan(B, oh, ow, (long long)B * oh * ow * (u8 ? 3 : 1), tx, ty, grid)) return hipErrorNotSupported;
     // the largest rectangles of any tile, rows and columns separately (the device evaluates the same fp32 maps); the tiles' owned ranges
     // must tile [0, h) x [0, w) without gaps: lo(0) = 0 and the ranges are consecutive by construction
     auto span = [&](int tiles, int T_, int OUT, float r, int nflow, float ns, int ntab, int &pf_max, int &t_max) {
@@ -1023,19 +970,19 @@ static hipError_t launch_tail(const float *T, int B, int h2, int w2, const float
     };
     if (legacy_coord_host(0, G.ry, h).lo != 0 || legacy_coord_host(0, G.rx, w).lo != 0) return hipErrorNotSupported;
     int pr = 0, pc = 0, tr = 0, tc = 0;
-    span(ty, WT_TH, oh, G.ry, h, P.nsy, h2, pr, tr);
-    span(tx, WT_TW, ow, G.rx, w, P.nsx, w2, pc, tc);
+    span(ty, WarpTile::TH, oh, G.ry, h, P.nsy, h2, pr, tr);
+    span(tx, WarpTile::TW, ow, G.rx, w, P.nsx, w2, pc, tc);
     if (pr * pc > FT_PF_CAP || tr * tc > FT_T_CAP) return hipErrorNotSupported;
     const long long total = (long long)B * oh * ow;
     // compulsory traffic: tap-table rows, the coarser flow, predict_flow2 WRITTEN once (never re-read), frame read, warped (and the
     // output-resolution flow) written
     const double px_bytes = u8 ? (outflow ? 14.0 : 6.0) : (outflow ? 32.0 : 24.0);
     const double alg_bytes = 128.0 * B * h2 * w2 + 8.0 * B * h3 * w3 + 8.0 * B * h * w + px_bytes * total;
-    const dim3 grid((unsigned)((long long)tx * ty * B)), block(256);
-#define VSTAB_TAIL(WF, ST, U) launch_timed(HBM_SLOT_TAIL, alg_bytes, pf2_glue_warp_kernel<WF, ST, U>, grid, block, stream, T, bias2, pf3, pf2, img, out, outflow, B, oh, ow, tx, ty, P, G)
+#define VSTAB_TAIL(WF, ST, U) launch_timed(HBM_SLOT_TAIL, alg_bytes, pf2_glue_warp_kernel<WF, ST, U>, grid, dim3(256), stream, T, bias2, pf3, pf2, img, out, outflow, B, oh, ow, tx, ty, P, G)
     if (u8) return outflow ? VSTAB_TAIL(true, true, true) : VSTAB_TAIL(false, true, true);
-    if (outflow) return (ow & 3) == 0 ? VSTAB_TAIL(true, true, false) : VSTAB_TAIL(true, false, false);
-    return (ow & 3) == 0 ? VSTAB_TAIL(false, true, false) : VSTAB_TAIL(false, false, false);
+    const bool staged = WarpTile::staged_ok(out, ow, 3);
+    if (outflow) return staged ? VSTAB_TAIL(true, true, false) : VSTAB_TAIL(true, false, false);
+    return staged ? VSTAB_TAIL(false, true, false) : VSTAB_TAIL(false, false, false);
 #undef VSTAB_TAIL
 }
 
@@ -1056,107 +1003,38 @@ hipError_t launch_pf2_glue_warp_u8(const float *T, int B, int h2, int w2, const 
 // The evaluator's frame path in ONE launch, 8-bit in and out (main:568, 497-514, 625/630): frame_f = swap(frame)/255, outflow =
 // glue(flow), warped = tf_warp(frame_f, outflow), out = uint8(swap(warped*255)) -- without frame_f and warped ever existing in HBM
 // (the clip driver ran four launches here: frame_to_float, the fused glue + warp, quantise_output; 2 x 12 B/px of fp32 traffic more).
-// Statement for statement those kernels' arithmetic: u8 -> float through a 256-entry table of the IEEE quotients i / 255.0f (what
-// frame_to_float_kernel divides per pixel), the warp as warp3_tile_kernel, the quantiser as quantise_output_kernel (truncation,
-// saturating where numpy is undefined, channels swapped back): identical bytes (tests/test_gpu_clip.py).
+// Those kernels' arithmetic: u8 -> float through a 256-entry table of the IEEE quotients i / 255.0f (what frame_to_float_kernel
+// divides per pixel), glue and warp as warp3_tile_kernel<FUSED> (glue_pixels, warp3_pixels), the quantiser as
+// quantise_output_kernel (quantise3): identical bytes (tests/test_gpu_clip.py).
 // ---------------------------------------------------------------------------------
 template <bool WRITE_FLOW>
 __global__ __launch_bounds__(256) void warp3_u8_tile_kernel(const unsigned char *__restrict__ img, const float *__restrict__ flow,
                                                             unsigned char *__restrict__ out, float *__restrict__ outflow, int B, int H, int W,
                                                             int tiles_x, int tiles_y, GlueParams G)
 {
-    constexpr int WH = WT_WH, WW = WT_WW, TW = WT_TW, PPT = WT_PPT, PPR = TW / WW, TH = WT_TH;
+    constexpr int PPT = WarpTile::PPT;
     __shared__ float lut[256];
-    __shared__ __attribute__((aligned(16))) unsigned char stage[TH * TW * 3];
+    __shared__ __attribute__((aligned(16))) unsigned char stage[WarpTile::TH * WarpTile::TW * 3];
     lut[threadIdx.x] = (float)threadIdx.x / 255.0f;                  // 256 threads
-    unsigned bx, by, bz;
-    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int ty0 = (trem / tiles_x) * TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const WarpTile tile(tiles_x, tiles_y);
+    const int n = tile.n;
     const long long HW = (long long)H * W;
     int yy[PPT], xx[PPT];
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int q = j * 4 + wave;
-        yy[j] = ty0 + (q / PPR) * WH + lane / WW;
-        xx[j] = tx0 + (q % PPR) * WW + lane % WW;
+        yy[j] = tile.y(j); xx[j] = tile.x(j);
         ok[j] = yy[j] < H && xx[j] < W;
         if (!ok[j]) { yy[j] = 0; xx[j] = 0; }
     }
     f32x2 f[PPT];
-    {
-        f32x2 tl[PPT], tr[PPT], bl[PPT], br[PPT];
-        Lerp Y[PPT], X[PPT];
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-            Y[j] = legacy_coord(yy[j], G.ry, G.h); X[j] = legacy_coord(xx[j], G.rx, G.w);
-            const f32x2 *b = reinterpret_cast<const f32x2 *>(flow) + (long long)n * G.h * G.w;
-            const int xb = min(X[j].lo, G.w - 2);
-            const flow2 top = *reinterpret_cast<const flow2 *>(b + Y[j].lo * G.w + xb), bot = *reinterpret_cast<const flow2 *>(b + Y[j].hi * G.w + xb);
-            const bool l1 = X[j].lo != xb, h1 = X[j].hi != xb;
-            tl[j] = l1 ? top.b : top.a; tr[j] = h1 ? top.b : top.a;
-            bl[j] = l1 ? bot.b : bot.a; br[j] = h1 ? bot.b : bot.a;
-        }
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-            f[j].x = glue_post_x(lerp2(glue_pre(tl[j].x, G), glue_pre(tr[j].x, G), glue_pre(bl[j].x, G), glue_pre(br[j].x, G), X[j].t, Y[j].t), G);
-            f[j].y = glue_post_y(lerp2(glue_pre(tl[j].y, G), glue_pre(tr[j].y, G), glue_pre(bl[j].y, G), glue_pre(br[j].y, G), X[j].t, Y[j].t), G);
-            if (WRITE_FLOW && ok[j]) reinterpret_cast<f32x2 *>(outflow)[n * HW + (long long)yy[j] * W + xx[j]] = f[j];
-        }
-    }
+    glue_pixels<PPT>(reinterpret_cast<const f32x2 *>(flow) + (long long)n * G.h * G.w, yy, xx, G, f, [&](int j) {
+        if (WRITE_FLOW && ok[j]) reinterpret_cast<f32x2 *>(outflow)[n * HW + (long long)yy[j] * W + xx[j]] = f[j];
+    });
     __syncthreads();                                                  // the table
-    const unsigned char *b8 = img + n * HW * 3;
-    float wa[PPT], wb[PPT], wc[PPT], wd[PPT];
-    rgb3 Ia[PPT], Ib[PPT], Ic[PPT], Id[PPT];
-    auto px = [&](int y, int x) {                                     // swap(frame)/255: channels 2, 1, 0 of the BGR pixel
-        const unsigned char *q = b8 + ((long long)y * W + x) * 3;
-        rgb3 r; r.r = lut[q[2]]; r.g = lut[q[1]]; r.b = lut[q[0]];
-        return r;
-    };
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const float x = (float)xx[j] + f[j].x, y = (float)yy[j] + f[j].y;
-        int x0 = (int)fminf(fmaxf(x, -2.f), (float)W), y0 = (int)fminf(fmaxf(y, -2.f), (float)H);
-        int x1 = x0 + 1, y1 = y0 + 1;
-        x0 = min(max(x0, 0), W - 1); x1 = min(max(x1, 0), W - 1);
-        y0 = min(max(y0, 0), H - 1); y1 = min(max(y1, 0), H - 1);
-        const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-        wa[j] = (x1f - x) * (y1f - y); wb[j] = (x1f - x) * (y - y0f);
-        wc[j] = (x - x0f) * (y1f - y); wd[j] = (x - x0f) * (y - y0f);
-        Ia[j] = px(y0, x0); Ib[j] = px(y1, x0); Ic[j] = px(y0, x1); Id[j] = px(y1, x1);
-    }
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        float r[3];
-        r[0] = ((wa[j] * Ia[j].r + wb[j] * Ib[j].r) + wc[j] * Ic[j].r) + wd[j] * Id[j].r;      // tf.add_n order
-        r[1] = ((wa[j] * Ia[j].g + wb[j] * Ib[j].g) + wc[j] * Ic[j].g) + wd[j] * Id[j].g;
-        r[2] = ((wa[j] * Ia[j].b + wb[j] * Ib[j].b) + wc[j] * Ic[j].b) + wd[j] * Id[j].b;
-        const int q = j * 4 + wave;
-        unsigned char *o = stage + (((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = (unsigned char)fminf(fmaxf(truncf(r[2 - c] * 255.0f), 0.f), 255.f);   // quantise_output_kernel's
-    }
-    __syncthreads();
+    warp3_pixels<true, PPT>(img + n * HW * 3, lut, yy, xx, f, H, W, [&](int j, const rgb3 &r) { quantise3(r, stage + tile.staged(j) * 3); });
     // a tile row is TW*3 = 96 bytes; 4-byte stores where rows start on a 4-byte boundary (W % 4 == 0), bytes otherwise / at a ragged edge
-    const int vw3 = min(TW, W - tx0) * 3;
-    if ((W & 3) == 0) {
-        constexpr int R4 = TW * 3 / 4;
-        for (int e = threadIdx.x; e < TH * R4; e += 256) {
-            const int row = e / R4, c4 = e - row * R4;
-            if (ty0 + row >= H || c4 * 4 >= vw3) continue;
-            unsigned char *o = out + (n * HW + (long long)(ty0 + row) * W + tx0) * 3 + c4 * 4;
-            if (c4 * 4 + 4 <= vw3) *reinterpret_cast<unsigned *>(o) = *reinterpret_cast<const unsigned *>(stage + row * TW * 3 + c4 * 4);
-            else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = stage[row * TW * 3 + c4 * 4 + i];
-        }
-    } else {
-        for (int e = threadIdx.x; e < TH * TW * 3; e += 256) {
-            const int row = e / (TW * 3), c = e - row * (TW * 3);
-            if (ty0 + row < H && c < vw3) out[(n * HW + (long long)(ty0 + row) * W + tx0) * 3 + c] = stage[e];
-        }
-    }
+    tile.template store_rows<3>(stage, out, H, W, (W & 3) == 0);
 }
 
 hipError_t launch_flow_glue_warp_u8(const float *flow, int B, int h, int w, const unsigned char *frame, float *outflow, unsigned char *out, int oh,
@@ -1164,90 +1042,55 @@ hipError_t launch_flow_glue_warp_u8(const float *flow, int B, int h, int w, cons
 {
     const long long total = (long long)B * oh * ow;
     if (total == 0) return hipSuccess;
-    const int tx = (ow + WT_TW - 1) / WT_TW, ty = (oh + WT_TH - 1) / WT_TH;
-    if (w < 2 || total >= (1ll << 31) / 3 || (long long)tx * ty * B >= (1ll << 31) || ((uintptr_t)flow & 7) || ((uintptr_t)outflow & 7) || ((uintptr_t)out & 3))
+    int tx, ty;
+    dim3 grid;
+    if (!WarpTile::plan(B, oh, ow, total * 3, tx, ty, grid) || w < 2 || ((uintptr_t)flow & 7) || ((uintptr_t)outflow & 7) || ((uintptr_t)out & 3))
         return hipErrorInvalidValue;
     const GlueParams G = glue_params(h, w, oh, ow, net_h, net_w);
-    const dim3 grid((unsigned)((long long)tx * ty * B)), block(256);
     const double src = 8.0 * B * h * w;                       // 3 B/px frame + 3 B/px out (+ 8 B/px flow written)
-    if (outflow) return launch_timed(HBM_SLOT_GLUE_WARP, src + 14.0 * total, warp3_u8_tile_kernel<true>, grid, block, stream, frame, flow, out, outflow, B, oh, ow, tx, ty, G);
-    return launch_timed(HBM_SLOT_GLUE_WARP, src + 6.0 * total, warp3_u8_tile_kernel<false>, grid, block, stream, frame, flow, out, (float *)nullptr, B, oh, ow, tx, ty, G);
+    if (outflow) return launch_timed(HBM_SLOT_GLUE_WARP, src + 14.0 * total, warp3_u8_tile_kernel<true>, grid, dim3(256), stream, frame, flow, out, outflow, B, oh, ow, tx, ty, G);
+    return launch_timed(HBM_SLOT_GLUE_WARP, src + 6.0 * total, warp3_u8_tile_kernel<false>, grid, dim3(256), stream, frame, flow, out, (float *)nullptr, B, oh, ow, tx, ty, G);
 }
 
 // ---------------------------------------------------------------------------------
 // The stand-alone glue (main:497-498, for callers that filter the flow between glue and warp) and the 3-channel legacy-bilinear
 // resize (main:806: the unstable frame -- channels 24:27 of the 27-channel stack, read in place through `Cs` / `c_off` -- to
-// the flow grid; main:202-203) on the warp's tile mapping: 16 x 32 pixel tiles, 4 x 16 wave patches, the left/right taps of a
-// source row fetched as neighbours, rows leaving through LDS as 16-byte stores.  Same statements as flow_resize_scale_kernel /
-// resize_bilinear_kernel: bit-identical (tests/test_gpu_parity.py).
+// the flow grid; main:202-203) on the warp's tile skeleton.  The glue is glue_pixels, the resize lerp2 as resize_bilinear_kernel:
+// bit-identical to the one-thread-per-pixel kernels (tests/test_gpu_parity.py).
 // ---------------------------------------------------------------------------------
 template <bool STAGE>
 __global__ __launch_bounds__(256) void glue_tile_kernel(const float *__restrict__ flow, float *__restrict__ out, int B, int oh, int ow,
                                                         int tiles_x, int tiles_y, GlueParams G)
 {
-    constexpr int TW = WT_TW, TH = WT_TH, PPT = WT_PPT, WW = WT_WW, WH = WT_WH, PPR = TW / WW;
-    __shared__ __attribute__((aligned(16))) float stage[STAGE ? TH * TW * 2 : 4];
-    unsigned bx, by, bz;
-    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int ty0 = (trem / tiles_x) * TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const f32x2 *b = reinterpret_cast<const f32x2 *>(flow) + (size_t)n * G.h * G.w;
-    flow2 top[PPT], bot[PPT];
-    Lerp Y[PPT], X[PPT];
-    int yy[PPT], xx[PPT], xb[PPT];
+    constexpr int PPT = WarpTile::PPT;
+    __shared__ __attribute__((aligned(16))) float stage[STAGE ? WarpTile::TH * WarpTile::TW * 2 : 4];
+    const WarpTile tile(tiles_x, tiles_y);
+    const int n = tile.n;
+    int yy[PPT], xx[PPT];
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int q = j * 4 + wave;
-        const int y = ty0 + (q / PPR) * WH + lane / WW, x = tx0 + (q % PPR) * WW + lane % WW;
-        ok[j] = y < oh && x < ow;
-        yy[j] = min(y, oh - 1); xx[j] = min(x, ow - 1);
-        Y[j] = legacy_coord(yy[j], G.ry, G.h); X[j] = legacy_coord(xx[j], G.rx, G.w);
-        xb[j] = min(X[j].lo, G.w - 2);
-        top[j] = *reinterpret_cast<const flow2 *>(b + Y[j].lo * G.w + xb[j]);
-        bot[j] = *reinterpret_cast<const flow2 *>(b + Y[j].hi * G.w + xb[j]);
+        ok[j] = tile.y(j) < oh && tile.x(j) < ow;
+        yy[j] = min(tile.y(j), oh - 1); xx[j] = min(tile.x(j), ow - 1);
     }
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const bool l1 = X[j].lo != xb[j], h1 = X[j].hi != xb[j];
-        const f32x2 tl = l1 ? top[j].b : top[j].a, tr = h1 ? top[j].b : top[j].a, bl = l1 ? bot[j].b : bot[j].a, br = h1 ? bot[j].b : bot[j].a;
-        f32x2 o;
-        o.x = glue_post_x(lerp2(glue_pre(tl.x, G), glue_pre(tr.x, G), glue_pre(bl.x, G), glue_pre(br.x, G), X[j].t, Y[j].t), G);
-        o.y = glue_post_y(lerp2(glue_pre(tl.y, G), glue_pre(tr.y, G), glue_pre(bl.y, G), glue_pre(br.y, G), X[j].t, Y[j].t), G);
-        if (STAGE) {
-            const int q = j * 4 + wave;
-            *reinterpret_cast<f32x2 *>(stage + (((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW) * 2) = o;
-        } else if (ok[j]) {
-            reinterpret_cast<f32x2 *>(out)[((size_t)n * oh + yy[j]) * ow + xx[j]] = o;
-        }
-    }
-    if (STAGE) {           // ow even (host): a tile row is 256 bytes from a 16-byte aligned address
-        __syncthreads();
-        constexpr int R4 = TW * 2 / 4;
-        const int vw2 = min(TW, ow - tx0) * 2;
-        for (int e = threadIdx.x; e < TH * R4; e += 256) {
-            const int row = e / R4, c4 = e - row * R4;
-            if (ty0 + row >= oh || c4 * 4 >= vw2) continue;
-            float *o = out + (((size_t)n * oh + ty0 + row) * ow + tx0) * 2 + c4 * 4;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(stage + row * TW * 2 + c4 * 4);
-            if (c4 * 4 + 4 <= vw2) *reinterpret_cast<f32x4 *>(o) = v;
-            else { o[0] = v[0]; o[1] = v[1]; }
-        }
-    }
+    f32x2 o[PPT];
+    glue_pixels<PPT>(reinterpret_cast<const f32x2 *>(flow) + (size_t)n * G.h * G.w, yy, xx, G, o, [&](int j) {
+        if (STAGE) *reinterpret_cast<f32x2 *>(stage + tile.staged(j) * 2) = o[j];
+        else if (ok[j]) reinterpret_cast<f32x2 *>(out)[((size_t)n * oh + yy[j]) * ow + xx[j]] = o[j];
+    });
+    if (STAGE) tile.template store_rows<2>(stage, out, oh, ow);           // ow even (host): a tile row is 256 bytes from a 16-byte aligned address
 }
 
 static hipError_t launch_glue_tile(const float *flow, int B, float *out, int oh, int ow, const GlueParams &G, hipStream_t stream)
 {
     const int h = G.h, w = G.w;
-    const long long tiles = (long long)((ow + WT_TW - 1) / WT_TW) * ((oh + WT_TH - 1) / WT_TH) * B;
-    if (w < 2 || tiles >= (1ll << 31) || (long long)B * oh * ow >= (1ll << 31) || ((uintptr_t)out & 15)) return hipErrorNotSupported;
-    const int tx = (ow + WT_TW - 1) / WT_TW, ty = (oh + WT_TH - 1) / WT_TH;
+    int tx, ty;
+    dim3 grid;
+    if (!WarpTile::plan(B, oh, ow, (long long)B * oh * ow, tx, ty, grid) || w < 2 || ((uintptr_t)out & 15)) return hipErrorNotSupported;
     const double bytes = 8.0 * B * h * w + 8.0 * B * oh * ow;
-    if ((ow & 1) == 0)
-        return launch_timed(HBM_SLOT_GLUE, bytes, glue_tile_kernel<true>, dim3((unsigned)tiles), dim3(256), stream, flow, out, B, oh, ow, tx, ty, G);
-    return launch_timed(HBM_SLOT_GLUE, bytes, glue_tile_kernel<false>, dim3((unsigned)tiles), dim3(256), stream, flow, out, B, oh, ow, tx, ty, G);
+    if (WarpTile::staged_ok(out, ow, 2))
+        return launch_timed(HBM_SLOT_GLUE, bytes, glue_tile_kernel<true>, grid, dim3(256), stream, flow, out, B, oh, ow, tx, ty, G);
+    return launch_timed(HBM_SLOT_GLUE, bytes, glue_tile_kernel<false>, grid, dim3(256), stream, flow, out, B, oh, ow, tx, ty, G);
 }
 
 template <bool STAGE>
@@ -1255,14 +1098,10 @@ __global__ __launch_bounds__(256) void resize3_tile_kernel(const float *__restri
                                                            float *__restrict__ out, int oh, int ow, float ry, float rx, int tiles_x,
                                                            int tiles_y)
 {
-    constexpr int TW = WT_TW, TH = WT_TH, PPT = WT_PPT, WW = WT_WW, WH = WT_WH, PPR = TW / WW;
-    __shared__ __attribute__((aligned(16))) float stage[STAGE ? TH * TW * 3 : 4];
-    unsigned bx, by, bz;
-    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int ty0 = (trem / tiles_x) * TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    constexpr int PPT = WarpTile::PPT;
+    __shared__ __attribute__((aligned(16))) float stage[STAGE ? WarpTile::TH * WarpTile::TW * 3 : 4];
+    const WarpTile tile(tiles_x, tiles_y);
+    const int n = tile.n;
     const float *b = x + (size_t)n * h * w * Cs + c_off;
     rgb3 tl[PPT], tr[PPT], bl[PPT], br[PPT];
     Lerp Y[PPT], X[PPT];
@@ -1270,10 +1109,8 @@ __global__ __launch_bounds__(256) void resize3_tile_kernel(const float *__restri
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        const int q = j * 4 + wave;
-        const int y = ty0 + (q / PPR) * WH + lane / WW, xo = tx0 + (q % PPR) * WW + lane % WW;
-        ok[j] = y < oh && xo < ow;
-        yy[j] = min(y, oh - 1); xx[j] = min(xo, ow - 1);
+        ok[j] = tile.y(j) < oh && tile.x(j) < ow;
+        yy[j] = min(tile.y(j), oh - 1); xx[j] = min(tile.x(j), ow - 1);
         Y[j] = legacy_coord(yy[j], ry, h); X[j] = legacy_coord(xx[j], rx, w);
         tl[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].lo * w + X[j].lo) * Cs); tr[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].lo * w + X[j].hi) * Cs);
         bl[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].hi * w + X[j].lo) * Cs); br[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].hi * w + X[j].hi) * Cs);
@@ -1284,37 +1121,21 @@ __global__ __launch_bounds__(256) void resize3_tile_kernel(const float *__restri
         o.r = lerp2(tl[j].r, tr[j].r, bl[j].r, br[j].r, X[j].t, Y[j].t);
         o.g = lerp2(tl[j].g, tr[j].g, bl[j].g, br[j].g, X[j].t, Y[j].t);
         o.b = lerp2(tl[j].b, tr[j].b, bl[j].b, br[j].b, X[j].t, Y[j].t);
-        if (STAGE) {
-            const int q = j * 4 + wave;
-            *reinterpret_cast<rgb3 *>(stage + (((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW) * 3) = o;
-        } else if (ok[j]) {
-            reinterpret_cast<rgb3 *>(out)[((size_t)n * oh + yy[j]) * ow + xx[j]] = o;
-        }
+        if (STAGE) *reinterpret_cast<rgb3 *>(stage + tile.staged(j) * 3) = o;
+        else if (ok[j]) reinterpret_cast<rgb3 *>(out)[((size_t)n * oh + yy[j]) * ow + xx[j]] = o;
     }
-    if (STAGE) {           // ow % 4 == 0 (host)
-        __syncthreads();
-        constexpr int R4 = TW * 3 / 4;
-        const int vw3 = min(TW, ow - tx0) * 3;
-        for (int e = threadIdx.x; e < TH * R4; e += 256) {
-            const int row = e / R4, c4 = e - row * R4;
-            if (ty0 + row >= oh || c4 * 4 >= vw3) continue;
-            float *o = out + (((size_t)n * oh + ty0 + row) * ow + tx0) * 3 + c4 * 4;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(stage + row * TW * 3 + c4 * 4);
-            if (c4 * 4 + 4 <= vw3) *reinterpret_cast<f32x4 *>(o) = v;
-            else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = v[i];
-        }
-    }
+    if (STAGE) tile.template store_rows<3>(stage, out, oh, ow);           // ow % 4 == 0 (host)
 }
 
 static hipError_t launch_resize3_tile(const float *x, int B, int h, int w, int Cs, int c_off, float *out, int oh, int ow, hipStream_t stream)
 {
-    const long long tiles = (long long)((ow + WT_TW - 1) / WT_TW) * ((oh + WT_TH - 1) / WT_TH) * B;
-    if (tiles >= (1ll << 31) || (long long)B * oh * ow >= (1ll << 31) || ((uintptr_t)out & 15) || c_off < 0 || c_off + 3 > Cs)
+    int tx, ty;
+    dim3 grid;
+    if (!WarpTile::plan(B, oh, ow, (long long)B * oh * ow, tx, ty, grid) || ((uintptr_t)out & 15) || c_off < 0 || c_off + 3 > Cs)
         return hipErrorNotSupported;
-    const int tx = (ow + WT_TW - 1) / WT_TW, ty = (oh + WT_TH - 1) / WT_TH;
     const float ry = (float)h / (float)oh, rx = (float)w / (float)ow;
-    if ((ow & 3) == 0) resize3_tile_kernel<true><<<dim3((unsigned)tiles), dim3(256), 0, stream>>>(x, B, h, w, Cs, c_off, out, oh, ow, ry, rx, tx, ty);
-    else resize3_tile_kernel<false><<<dim3((unsigned)tiles), dim3(256), 0, stream>>>(x, B, h, w, Cs, c_off, out, oh, ow, ry, rx, tx, ty);
+    if (WarpTile::staged_ok(out, ow, 3)) resize3_tile_kernel<true><<<grid, dim3(256), 0, stream>>>(x, B, h, w, Cs, c_off, out, oh, ow, ry, rx, tx, ty);
+    else resize3_tile_kernel<false><<<grid, dim3(256), 0, stream>>>(x, B, h, w, Cs, c_off, out, oh, ow, ry, rx, tx, ty);
     return hipGetLastError();
 }
 

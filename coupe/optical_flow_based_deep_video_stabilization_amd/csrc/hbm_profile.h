@@ -8,7 +8,8 @@
 
 namespace vstab {
 
-// profiling on: creates the two events of one launch, books `alg_bytes` under `slot` and returns them; off: *a = *b = nullptr
+// profiling on: creates the two events of one launch, books `alg_bytes` under `slot` and returns them; off, or slot < 0 (a launch
+// that goes through launch_timed but is not timed: the newer sampler launches): *a = *b = nullptr
 hipError_t hbm_profile_begin(int slot, double alg_bytes, hipEvent_t *a, hipEvent_t *b);
 
 template <typename... KArgs, typename... Args>

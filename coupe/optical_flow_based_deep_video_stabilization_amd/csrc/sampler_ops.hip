@@ -1,89 +1,22 @@
 // Samplers named by the reference's spatial_transformer.py and warp.py (BASELINE configs[2]'s
-// "spatial_transformer warp").  HBM-bound 4-tap gathers, coordinates generated in-kernel (no grid tensor is materialised).
-// 3-channel frames run on st3_tile_kernel (2-D tiles, 3-dword corner gathers, rows leaving as 16-byte stores); other channel
-// counts on the one-thread-per-pixel kernels.
+// "spatial_transformer warp").  HBM-bound tap gathers, coordinates generated in-kernel (no grid tensor is materialised).
+// ONE family of kernels, templated on where a pixel's source coordinates come from (XS_*) and on the sampler (XI_*):
+// st3_tile_kernel for 3-channel frames (tile3.h's skeleton: 2-D tiles, 3-dword tap gathers, rows leaving as 16-byte stores),
+// st_pixel_kernel (one thread per pixel) for other channel counts.  Each piece of the reference's arithmetic is one device
+// function (st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.
 // -ffp-contract=off keeps the weight arithmetic the reference's op-by-op fp32 sequence.
 #include "vstab_internal.h"
 #include "hbm_profile.h"
+#include "tile3.h"
+#include <algorithm>
 
 namespace vstab {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // tf.linspace(-1, 1, n)[i] in fp32 (start + i*step, step = 2/(n-1); a single point is -1)
 __device__ __forceinline__ float lin11(int i, int n)
 {
     const float step = n > 1 ? 2.0f / (float)(n - 1) : 0.0f;
     return -1.0f + (float)i * step;
-}
-
-// ---------------------------------------------------------------------------------
-// bilinear_interp (spatial_transformer.py:902-964): normalised coordinates in [-1,1] against an image
-// zero-padded by one pixel; x = (x+1)/2*(W-1), clipped to [-1, W], shifted by the pad; x0 = floor,
-// x1 = min(x0+1, W+1) as index but weights use the UNclipped x0+1.
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ void st_sample_pixel(const float *__restrict__ img, int n, int H, int W, int C, float xn, float yn,
-                                                float *__restrict__ o)
-{
-    const float wf = (float)W, hf = (float)H;
-    float x = (xn + 1.0f) / 2.0f * (wf - 1.0f);
-    float y = (yn + 1.0f) / 2.0f * (hf - 1.0f);
-    x = fminf(fmaxf(x, -1.0f), wf - 1.0f + 1.0f);       // clip_by_value(x, -edge, W-1+edge); NaN -> -1
-    y = fminf(fmaxf(y, -1.0f), hf - 1.0f + 1.0f);
-    x += 1.0f;
-    y += 1.0f;
-    const float x0f = floorf(x), y0f = floorf(y);
-    const float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;              // in [0, W+1] after the clip
-    const int x1 = (int)fminf(x1f, wf - 1.0f + 2.0f), y1 = (int)fminf(y1f, hf - 1.0f + 2.0f);
-    const float w00 = (x1f - x) * (y1f - y), w01 = (x - x0f) * (y1f - y);
-    const float w10 = (x1f - x) * (y - y0f), w11 = (x - x0f) * (y - y0f);
-    // padded index p in [0, W+1]: image column p-1, zero on the border
-    const bool vx0 = x0 >= 1 && x0 <= W, vx1 = x1 >= 1 && x1 <= W, vy0 = y0 >= 1 && y0 <= H, vy1 = y1 >= 1 && y1 <= H;
-    const float *b = img + (long long)n * H * W * C;
-    const long long i00 = ((long long)(y0 - 1) * W + (x0 - 1)) * C, i01 = ((long long)(y0 - 1) * W + (x1 - 1)) * C;
-    const long long i10 = ((long long)(y1 - 1) * W + (x0 - 1)) * C, i11 = ((long long)(y1 - 1) * W + (x1 - 1)) * C;
-    for (int c = 0; c < C; ++c) {
-        const float I00 = (vx0 && vy0) ? b[i00 + c] : 0.f, I01 = (vx1 && vy0) ? b[i01 + c] : 0.f;
-        const float I10 = (vx0 && vy1) ? b[i10 + c] : 0.f, I11 = (vx1 && vy1) ? b[i11 + c] : 0.f;
-        o[c] = ((w00 * I00 + w01 * I01) + w10 * I10) + w11 * I11;      // tf.add_n order
-    }
-}
-
-// explicit coordinates: x, y flat [B*npix] (spatial_transformer.py:902)
-__global__ __launch_bounds__(256) void st_interp_kernel(const float *__restrict__ img, int B, int H, int W, int C,
-                                                        const float *__restrict__ x, const float *__restrict__ y,
-                                                        int npix, float *__restrict__ out)
-{
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)B * npix) return;
-    const int n = (int)(idx / npix);
-    st_sample_pixel(img, n, H, W, C, x[idx], y[idx], out + idx * C);
-}
-
-// AffineTransformer / ProjectiveTransformer .transform (spatial_transformer.py:400-452, 539-608):
-// T_g = theta . (x_t, y_t, 1) on the linspace(-1,1) grid of the OUTPUT size; projective divides by
-// z with z == 0 replaced by z + 1e-8 (:598).
-__global__ __launch_bounds__(256) void st_transform_kernel(const float *__restrict__ img, int B, int H, int W, int C,
-                                                           const float *__restrict__ theta, int tdim,
-                                                           float *__restrict__ out, int oh, int ow)
-{
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)B * oh * ow) return;
-    const int n = (int)(idx / (oh * ow));
-    const int rem = (int)(idx - (long long)n * oh * ow);
-    const int oy = rem / ow, ox = rem - oy * ow;
-    const float xt = lin11(ox, ow), yt = lin11(oy, oh);
-    const float *t = theta + (long long)n * tdim;
-    float xs = (t[0] * xt + t[1] * yt) + t[2];
-    float ys = (t[3] * xt + t[4] * yt) + t[5];
-    if (tdim == 8) {
-        float zs = (t[6] * xt + t[7] * yt) + 1.0f;
-        if (zs == 0.0f) zs = zs + 1e-8f;
-        xs = xs / zs;
-        ys = ys / zs;
-    }
-    st_sample_pixel(img, n, H, W, C, xs, ys, out + idx * C);
 }
 
 // _meshgrid(out_size) (spatial_transformer.py:755-779): flat [3*oh*ow] = x_t row, y_t row, ones
@@ -98,12 +31,6 @@ __global__ __launch_bounds__(256) void st_meshgrid_kernel(float *__restrict__ ou
     out[2 * np + idx] = 1.0f;
 }
 
-// ---------------------------------------------------------------------------------
-// warp.transformImage / transformCropImage (warp.py:46-129): homography from the canonical
-// [-1,1]^2 grid (np.linspace in float64, cast to fp32) straight to source PIXEL coordinates,
-// /(z+1e-8), floor/ceil taps, taps outside the image read an appended zero row.
-// M = refMtrx . pMtrx, row-major [B,9].
-// ---------------------------------------------------------------------------------
 // M = refMtrx . pMtrx (warp.py:48-49's tf.matmul) composed here when `ref` is given: every product and sum its own fp32 operation,
 // (r0*p0 + r1*p1) + r2*p2, like the grid products below -- no library GEMM in front of the launch
 __device__ __forceinline__ void compose3(const float *__restrict__ ref, const float *__restrict__ p, float *m)
@@ -114,100 +41,70 @@ __device__ __forceinline__ void compose3(const float *__restrict__ ref, const fl
         for (int j = 0; j < 3; ++j) m[3 * i + j] = (ref[3 * i] * p[j] + ref[3 * i + 1] * p[3 + j]) + ref[3 * i + 2] * p[6 + j];
 }
 
-__global__ __launch_bounds__(256) void homography_warp_kernel(const float *__restrict__ img, int B, int Hi, int Wi, int C,
-                                                              const float *__restrict__ M, const float *__restrict__ ref,
-                                                              float *__restrict__ out, int oh, int ow)
-{
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)B * oh * ow) return;
-    const int n = (int)(idx / (oh * ow));
-    const int rem = (int)(idx - (long long)n * oh * ow);
-    const int oy = rem / ow, ox = rem - oy * ow;
-    const float X = ow > 1 ? (float)(-1.0 + (double)ox * (2.0 / (double)(ow - 1))) : -1.0f;
-    const float Y = oh > 1 ? (float)(-1.0 + (double)oy * (2.0 / (double)(oh - 1))) : -1.0f;
-    float m[9];
-    if (ref) compose3(ref, M + (long long)n * 9, m);
-    else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) m[k] = M[(long long)n * 9 + k];
-    }
-    const float xh = (m[0] * X + m[1] * Y) + m[2];
-    const float yh = (m[3] * X + m[4] * Y) + m[5];
-    const float zh = (m[6] * X + m[7] * Y) + m[8];
-    const float xw = xh / (zh + 1e-8f), yw = yh / (zh + 1e-8f);
-    const float xf = floorf(xw), xc = ceilf(xw), yf = floorf(yw), yc = ceilf(yw);
-    // clamp before the int conversion (out-of-range float->int is undefined); anything outside is "outside"
-    const float lim = 1.0e9f;
-    const int xfi = (int)fminf(fmaxf(xf, -lim), lim), xci = (int)fminf(fmaxf(xc, -lim), lim);
-    const int yfi = (int)fminf(fmaxf(yf, -lim), lim), yci = (int)fminf(fmaxf(yc, -lim), lim);
-    const float xr = xw - xf, yr = yw - yf;
-    const bool fx = xfi >= 0 && xfi < Wi, cx = xci >= 0 && xci < Wi, fy = yfi >= 0 && yfi < Hi, cy = yci >= 0 && yci < Hi;
-    const float *b = img + (long long)n * Hi * Wi * C;
-    const float wUL = (1.0f - xr) * (1.0f - yr), wUR = xr * (1.0f - yr), wBL = (1.0f - xr) * yr, wBR = xr * yr;
-    float *o = out + idx * C;
-    for (int c = 0; c < C; ++c) {
-        const float UL = (fx && fy) ? b[((long long)yfi * Wi + xfi) * C + c] : 0.f;
-        const float UR = (cx && fy) ? b[((long long)yfi * Wi + xci) * C + c] : 0.f;
-        const float BL = (fx && cy) ? b[((long long)yci * Wi + xfi) * C + c] : 0.f;
-        const float BR = (cx && cy) ? b[((long long)yci * Wi + xci) * C + c] : 0.f;
-        // image*(1-Xratio)*(1-Yratio) evaluates left to right: (I*(1-xr))*(1-yr)
-        o[c] = (((UL * (1.0f - xr)) * (1.0f - yr) + (UR * xr) * (1.0f - yr)) + (BL * (1.0f - xr)) * yr) + (BR * xr) * yr;
-    }
-    (void)wUL; (void)wUR; (void)wBL; (void)wBR;
-}
-
 // ---------------------------------------------------------------------------------
-// 3-channel frames: all three sampler families on one tile kernel (24 B/px algorithmic: 12 gathered + 12 written, + 8 with
-// explicit coordinates).
-//   FAM_ST_THETA  Affine/ProjectiveTransformer.transform   (spatial_transformer.py:400-452, 539-608)
-//   FAM_ST_COORDS bilinear_interp with explicit x, y       (spatial_transformer.py:902-964)
-//   FAM_HOMOG     warp.transformImage / transformCropImage (warp.py:46-129)
-// Shaped like tf_warp's tile kernel (flow_ops.hip, warp3_tile_kernel; profiles/README.md "r02 warp study"): a workgroup owns a
-// 16 x 32 tile of ONE sample's output pixels and a wave instruction works on a 4 x 16 patch, so the lines a gather touches are a
-// compact 2-D footprint under any rotation; one 3-dword load per corner; results leave through LDS as 16-byte stores of whole
-// 384-byte tile rows (ow % 4 == 0; 12-byte stores otherwise); XCD-contiguous tile order.
-// Measured and rejected twice (profiles/README.md "r03 sampler study"): staging the source window in LDS -- bounding box of the taps
-// by DPP reductions, aligned 16-byte fill, corners from LDS -- cuts the L1 lookups 3x (0.50 instead of 1.56 per pixel) and is
-// SLOWER both per workgroup tile (commit 2076632: four barriers, three dependent phases; 0.34-0.39 of 8 TB/s against 0.53-0.65)
-// and per wave patch with no barrier at all (0.41-0.49): what bounds these kernels is requests in flight, not tag lookups.
-// The arithmetic is st_sample_pixel's / homography_warp_kernel's statement for statement: bit-identical results.
+// Where a pixel's source coordinates come from, and the sampler:
+//   XS_COORDS  explicit x, y [B*oh*ow]                       (bilinear_interp ST:902-964, bicubic_interp ST:966-1072)
+//   XS_THETA   Affine/ProjectiveTransformer.transform: T_g = theta . (x_t, y_t, 1) on the linspace(-1,1) grid of the OUTPUT size;
+//              projective divides by z with z == 0 replaced by z + 1e-8 (ST:400-452, 539-608)
+//   XS_SYM     the symmetric-pad transformers (SimilarityTransformer ST:311-371, AffineSymmetryTransformer ST:454-517,
+//              ProjectiveSymmetryTransformer ST:611-716): the image padded by 100 px per side in SYMMETRIC mode is never
+//              materialised (a padded index p reads refl(p - 100)); the (oh+200) x (ow+200) grid is sampled only where
+//              resize_image_with_crop_or_pad keeps it, the pixels it pads are written as zeros
+//   XS_TPS     ElasticTransformer's thin-plate spline (ST:40-224): coeff [2, K+3] = (source points + theta) . L_inv^T once per
+//              workgroup into LDS, then per pixel x_s = coeff_x . [x_t, y_t, 1, U_1..U_K] with U_k = r^2 ln r^2 evaluated
+//              in-kernel (no (K+1) x N table)
+//   XS_HOMOG   warp.transformImage / transformCropImage (warp.py:46-129): homography from the canonical [-1,1]^2 grid
+//              (np.linspace in float64, cast to fp32) straight to source PIXEL coordinates, /(z+1e-8), floor/ceil taps, taps
+//              outside the image read an appended zero row.  M = refMtrx . pMtrx, row-major [B,9].  XI_BILINEAR only.
+//   XI_BILINEAR  bilinear_interp: normalised coordinates in [-1,1] against an image zero-padded by one pixel (st_taps)
+//   XI_BICUBIC   bicubic_interp: 16 taps, edges replicate (cubic_axis)
 // ---------------------------------------------------------------------------------
-enum { FAM_ST_THETA = 0, FAM_ST_COORDS = 1, FAM_HOMOG = 2 };
-struct __attribute__((packed, aligned(4))) rgb3 { float r, g, b; };
-// theta [B,tdim] (M [B,9] for FAM_HOMOG) or x, y [B*oh*ow]; the grid steps 2/(n-1) are divided once on the host (the same IEEE
-// quotient lin11 / homography_warp_kernel compute per pixel): fp32 for tf.linspace, fp64 for np.linspace
-struct StSrc { const float *theta; const float *x; const float *y; int tdim; float sx, sy; double dsx, dsy; const float *ref; };      // ref: FAM_HOMOG's refMtrx (theta = pMtrx then) or null
+enum { XS_THETA = 0, XS_COORDS = 1, XS_HOMOG = 2, XS_SYM = 3, XS_TPS = 4 };      // THETA = 0 and HOMOG = 2: the names bench.py reports
+enum { XI_BILINEAR = 0, XI_BICUBIC = 1 };
+constexpr int ST_TPS_KMAX = 256;                     // g <= 16 control points per side (api.cpp)
 
-constexpr int ST_TW = 32, ST_TH = 16, ST_PPT = 2, ST_WW = 16, ST_WH = 4, ST_PPR = ST_TW / ST_WW;
-static_assert(ST_WH * (4 * ST_PPT) / ST_PPR == ST_TH, "tile shape");
+struct StSrc {
+    const float *x, *y;            // XS_COORDS
+    const float *theta;            // XS_THETA [B,tdim]; XS_SYM [B,6|8|4]; XS_TPS [B,2K]; XS_HOMOG M (or pMtrx) [B,9]
+    const float *ref;              // XS_HOMOG: refMtrx (theta = pMtrx then) or null
+    const float *linv_t;           // XS_TPS: transpose(L_inv[:,3:]) [K, K+3]
+    int tdim, kind, g, B;          // kind: XS_SYM's VSTAB_SYM_* (0 affine, 1 projective, 2 similarity); g: TPS grid side
+    int gh, gw;                    // the linspace sampling grid
+    float sx, sy;                  // its steps 2/(n-1), divided once on the host (the same IEEE quotient lin11 computes): fp32 for
+    double dsx, dsy;               // tf.linspace, fp64 for XS_HOMOG's np.linspace
+    int pady, cropy, leny, padx, cropx, lenx;        // XS_SYM's crop-or-pad: final i reads grid i - pad + crop when 0 <= i - pad < len
+};
 
 // the four taps of one output pixel: image coordinates clamped into the image (what is addressed), validity per axis (what
 // counts: an invalid tap reads as zero) and the blend weights (ST: w00, w01, w10, w11; homography: xr, yr)
 struct Taps { int xa, xb, ya, yb; bool vxa, vxb, vya, vyb; float w0, w1, w2, w3; };
 
-__device__ __forceinline__ Taps st_taps(float xn, float yn, int H, int W)          // st_sample_pixel's arithmetic
+// bilinear_interp (spatial_transformer.py:902-964): x = (x+1)/2*(W-1), clipped to [-1, W], shifted by the one-pixel zero pad;
+// x0 = floor, x1 = min(x0+1, W+1) as index but weights use the UNclipped x0+1
+__device__ __forceinline__ Taps st_taps(float xn, float yn, int H, int W)
 {
     const float wf = (float)W, hf = (float)H;
     float x = (xn + 1.0f) / 2.0f * (wf - 1.0f);
     float y = (yn + 1.0f) / 2.0f * (hf - 1.0f);
-    x = fminf(fmaxf(x, -1.0f), wf - 1.0f + 1.0f);
+    x = fminf(fmaxf(x, -1.0f), wf - 1.0f + 1.0f);       // clip_by_value(x, -edge, W-1+edge); NaN -> -1
     y = fminf(fmaxf(y, -1.0f), hf - 1.0f + 1.0f);
     x += 1.0f;
     y += 1.0f;
     const float x0f = floorf(x), y0f = floorf(y);
     const float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
+    const int x0 = (int)x0f, y0 = (int)y0f;              // in [0, W+1] after the clip
     const int x1 = (int)fminf(x1f, wf - 1.0f + 2.0f), y1 = (int)fminf(y1f, hf - 1.0f + 2.0f);
     Taps t;
     t.w0 = (x1f - x) * (y1f - y); t.w1 = (x - x0f) * (y1f - y);
     t.w2 = (x1f - x) * (y - y0f); t.w3 = (x - x0f) * (y - y0f);
+    // padded index p in [0, W+1]: image column p-1, zero on the border
     t.vxa = x0 >= 1 && x0 <= W; t.vxb = x1 >= 1 && x1 <= W; t.vya = y0 >= 1 && y0 <= H; t.vyb = y1 >= 1 && y1 <= H;
     t.xa = min(max(x0 - 1, 0), W - 1); t.xb = min(max(x1 - 1, 0), W - 1);
     t.ya = min(max(y0 - 1, 0), H - 1); t.yb = min(max(y1 - 1, 0), H - 1);
     return t;
 }
 
-__device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, int oy, double dsx, double dsy, int Hi, int Wi)   // homography_warp_kernel's
+__device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, int oy, double dsx, double dsy, int Hi, int Wi)
 {
     const float X = (float)(-1.0 + (double)ox * dsx);
     const float Y = (float)(-1.0 + (double)oy * dsy);
@@ -216,6 +113,7 @@ __device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, 
     const float zh = (m[6] * X + m[7] * Y) + m[8];
     const float xw = xh / (zh + 1e-8f), yw = yh / (zh + 1e-8f);
     const float xf = floorf(xw), xc = ceilf(xw), yf = floorf(yw), yc = ceilf(yw);
+    // clamp before the int conversion (out-of-range float->int is undefined); anything outside is "outside"
     const float lim = 1.0e9f;
     const int xfi = (int)fminf(fmaxf(xf, -lim), lim), xci = (int)fminf(fmaxf(xc, -lim), lim);
     const int yfi = (int)fminf(fmaxf(yf, -lim), lim), yci = (int)fminf(fmaxf(yc, -lim), lim);
@@ -227,239 +125,33 @@ __device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, 
     return t;
 }
 
-template <int FAM>
+template <bool HOMOG>
 __device__ __forceinline__ float st_blend(const Taps &t, float I00, float I01, float I10, float I11)
 {
-    if (FAM == FAM_HOMOG) {
-        const float xr = t.w0, yr = t.w1;        // image*(1-Xratio)*(1-Yratio) evaluates left to right
+    if (HOMOG) {
+        const float xr = t.w0, yr = t.w1;        // image*(1-Xratio)*(1-Yratio) evaluates left to right: (I*(1-xr))*(1-yr)
         return (((I00 * (1.0f - xr)) * (1.0f - yr) + (I01 * xr) * (1.0f - yr)) + (I10 * (1.0f - xr)) * yr) + (I11 * xr) * yr;
     }
     return ((t.w0 * I00 + t.w1 * I01) + t.w2 * I10) + t.w3 * I11;      // tf.add_n order
 }
-
-template <int FAM, bool STAGE>
-__global__ __launch_bounds__(256) void st3_tile_kernel(const float *__restrict__ img, int B, int H, int W, StSrc S,
-                                                       float *__restrict__ out, int oh, int ow, int tiles_x, int tiles_y)
-{
-    constexpr int TW = ST_TW, TH = ST_TH, PPT = ST_PPT, WW = ST_WW, WH = ST_WH, PPR = ST_PPR;
-    __shared__ __attribute__((aligned(16))) float lds[STAGE ? ST_TH * ST_TW * 3 : 4];
-    unsigned bx, by, bz;
-    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int ty0 = (trem / tiles_x) * TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int HW = H * W;                              // 3 B H W < 2^31 (host)
-
-    Taps t[PPT];
-    int yy[PPT], xx[PPT];
-    bool ok[PPT];
-    float th[9];
-    if (FAM != FAM_ST_COORDS) {
-        const float *tp = S.theta + (long long)n * S.tdim;       // wave-uniform: scalar loads
-#pragma unroll
-        for (int k = 0; k < 9; ++k) th[k] = k < S.tdim ? tp[k] : 1.0f;
-        if (FAM == FAM_HOMOG && S.ref) {                           // M = refMtrx . pMtrx, here instead of a GEMM launch in front
-            float pm[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) pm[k] = th[k];
-            compose3(S.ref, pm, th);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const int q = j * 4 + wave;
-        const int y = ty0 + (q / PPR) * WH + lane / WW, x = tx0 + (q % PPR) * WW + lane % WW;
-        ok[j] = y < oh && x < ow;
-        yy[j] = min(y, oh - 1); xx[j] = min(x, ow - 1);          // a pixel beyond the output repeats an edge pixel of this tile (not stored)
-        if (FAM == FAM_ST_THETA) {
-            const float xt = -1.0f + (float)xx[j] * S.sx, yt = -1.0f + (float)yy[j] * S.sy;
-            float xs = (th[0] * xt + th[1] * yt) + th[2];
-            float ys = (th[3] * xt + th[4] * yt) + th[5];
-            if (S.tdim == 8) {
-                float zs = (th[6] * xt + th[7] * yt) + 1.0f;
-                if (zs == 0.0f) zs = zs + 1e-8f;
-                xs = xs / zs;
-                ys = ys / zs;
-            }
-            t[j] = st_taps(xs, ys, H, W);
-        } else if (FAM == FAM_ST_COORDS) {
-            const long long i = ((long long)n * oh + yy[j]) * ow + xx[j];
-            t[j] = st_taps(S.x[i], S.y[i], H, W);
-        } else {
-            t[j] = homog_taps(th, xx[j], yy[j], S.dsx, S.dsy, H, W);
-        }
-    }
-    const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + (long long)n * HW;
-    rgb3 I00[PPT], I01[PPT], I10[PPT], I11[PPT];
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        I00[j] = b[t[j].ya * W + t[j].xa]; I01[j] = b[t[j].ya * W + t[j].xb];
-        I10[j] = b[t[j].yb * W + t[j].xa]; I11[j] = b[t[j].yb * W + t[j].xb];
-    }
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const bool v00 = t[j].vxa && t[j].vya, v01 = t[j].vxb && t[j].vya, v10 = t[j].vxa && t[j].vyb, v11 = t[j].vxb && t[j].vyb;
-        rgb3 r;
-        r.r = st_blend<FAM>(t[j], v00 ? I00[j].r : 0.f, v01 ? I01[j].r : 0.f, v10 ? I10[j].r : 0.f, v11 ? I11[j].r : 0.f);
-        r.g = st_blend<FAM>(t[j], v00 ? I00[j].g : 0.f, v01 ? I01[j].g : 0.f, v10 ? I10[j].g : 0.f, v11 ? I11[j].g : 0.f);
-        r.b = st_blend<FAM>(t[j], v00 ? I00[j].b : 0.f, v01 ? I01[j].b : 0.f, v10 ? I10[j].b : 0.f, v11 ? I11[j].b : 0.f);
-        if (STAGE) {
-            const int q = j * 4 + wave;
-            *reinterpret_cast<rgb3 *>(lds + (((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW) * 3) = r;
-        } else if (ok[j]) {
-            reinterpret_cast<rgb3 *>(out)[((long long)n * oh + yy[j]) * ow + xx[j]] = r;
-        }
-    }
-    if (STAGE) {       // ow % 4 == 0 (host): a tile row is TW*12 bytes from a 16-byte aligned address
-        __syncthreads();
-        constexpr int R4 = TW * 3 / 4;
-        const int vw3 = min(TW, ow - tx0) * 3;
-        for (int e = threadIdx.x; e < TH * R4; e += 256) {
-            const int row = e / R4, c4 = e - row * R4;
-            if (ty0 + row >= oh || c4 * 4 >= vw3) continue;
-            float *o = out + (((long long)n * oh + ty0 + row) * ow + tx0) * 3 + c4 * 4;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(lds + row * TW * 3 + c4 * 4);
-            if (c4 * 4 + 4 <= vw3) *reinterpret_cast<f32x4 *>(o) = v;
-            else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = v[i];
-        }
-    }
-}
-
-// picks the instantiation for a 3-channel launch; hipErrorNotSupported when the shape is not the tile kernel's
-template <int FAM>
-static hipError_t launch_st3(int slot, const float *img, int B, int H, int W, StSrc S, float *out, int oh, int ow, hipStream_t stream)
-{
-    S.sx = ow > 1 ? 2.0f / (float)(ow - 1) : 0.0f; S.sy = oh > 1 ? 2.0f / (float)(oh - 1) : 0.0f;
-    S.dsx = ow > 1 ? 2.0 / (double)(ow - 1) : 0.0; S.dsy = oh > 1 ? 2.0 / (double)(oh - 1) : 0.0;
-    const long long tx = (ow + ST_TW - 1) / ST_TW, ty = (oh + ST_TH - 1) / ST_TH, tiles = tx * ty * B;
-    if (tiles >= (1ll << 31) || (long long)B * H * W * 3 >= (1ll << 31) || (long long)B * oh * ow * 3 >= (1ll << 31)) return hipErrorNotSupported;
-    const bool stage = (ow & 3) == 0 && ((uintptr_t)out & 15) == 0;
-    const double bytes = (FAM == FAM_ST_COORDS ? 32.0 : 24.0) * B * oh * ow;       // every output pixel reads ~one source pixel, writes one (+ x, y)
-    const dim3 grid((unsigned)tiles), block(256);
-    if (stage) return launch_timed(slot, bytes, st3_tile_kernel<FAM, true>, grid, block, stream, img, B, H, W, S, out, oh, ow, (int)tx, (int)ty);
-    return launch_timed(slot, bytes, st3_tile_kernel<FAM, false>, grid, block, stream, img, B, H, W, S, out, oh, ow, (int)tx, (int)ty);
-}
-
-// warp.vec2mtrx (warp.py:25-43): sl(3) / affine generator -> matrix exponential by Taylor series,
-// pMtrx = sum_{i=0}^{warpApprox-1} A^i / i!   (fp32, one thread per batch element)
-__global__ void vec2mtrx_kernel(const float *__restrict__ p, int B, int dim, int approx, float *__restrict__ out)
-{
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= B) return;
-    const float *q = p + (long long)n * dim;
-    float A[9];
-    if (dim == 8) {
-        A[0] = q[2]; A[1] = q[1]; A[2] = q[0];
-        A[3] = q[5]; A[4] = -q[2] - q[6]; A[5] = q[4];
-        A[6] = q[3]; A[7] = q[7]; A[8] = q[6];
-    } else {
-        A[0] = q[0]; A[1] = q[1]; A[2] = q[2];
-        A[3] = q[3]; A[4] = q[4]; A[5] = q[5];
-        A[6] = 0.f; A[7] = 0.f; A[8] = 0.f;
-    }
-    float P[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Nm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    float denom = 1.0f;
-    for (int i = 1; i < approx; ++i) {
-        float T[9];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) T[r * 3 + c] = (Nm[r * 3] * A[c] + Nm[r * 3 + 1] * A[3 + c]) + Nm[r * 3 + 2] * A[6 + c];
-        denom *= (float)i;
-        for (int k = 0; k < 9; ++k) { Nm[k] = T[k]; P[k] += T[k] / denom; }
-    }
-    for (int k = 0; k < 9; ++k) out[(long long)n * 9 + k] = P[k];
-}
-
-hipError_t launch_st_interp(const float *img, int B, int H, int W, int C, const float *x, const float *y, int oh, int ow, float *out,
-                            hipStream_t stream)
-{
-    const int npix = oh * ow;
-    const long long total = (long long)B * npix;
-    if (C == 3) {
-        const hipError_t e = launch_st3<FAM_ST_COORDS>(HBM_SLOT_ST, img, B, H, W, StSrc{nullptr, x, y, 0, 0.f, 0.f, 0., 0., nullptr}, out, oh, ow, stream);
-        if (e != hipErrorNotSupported) return e;
-    }
-    st_interp_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream>>>(img, B, H, W, C, x, y, npix, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_st_transform(const float *img, int B, int H, int W, int C, const float *theta, int tdim, float *out, int oh,
-                               int ow, hipStream_t stream)
-{
-    const long long total = (long long)B * oh * ow;
-    if (C == 3) {
-        const hipError_t e = launch_st3<FAM_ST_THETA>(HBM_SLOT_ST, img, B, H, W, StSrc{theta, nullptr, nullptr, tdim, 0.f, 0.f, 0., 0., nullptr}, out, oh, ow, stream);
-        if (e != hipErrorNotSupported) return e;
-    }
-    st_transform_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream>>>(img, B, H, W, C, theta, tdim, out, oh, ow);
-    return hipGetLastError();
-}
-
-hipError_t launch_st_meshgrid(float *out, int oh, int ow, hipStream_t stream)
-{
-    st_meshgrid_kernel<<<dim3((unsigned)((oh * ow + 255) / 256)), dim3(256), 0, stream>>>(out, oh, ow);
-    return hipGetLastError();
-}
-
-hipError_t launch_homography_warp(const float *img, int B, int Hi, int Wi, int C, const float *M, float *out, int oh, int ow,
-                                  hipStream_t stream, const float *ref)
-{
-    const long long total = (long long)B * oh * ow;
-    if (C == 3) {
-        const hipError_t e = launch_st3<FAM_HOMOG>(HBM_SLOT_HOMOG, img, B, Hi, Wi, StSrc{M, nullptr, nullptr, 9, 0.f, 0.f, 0., 0., ref}, out, oh, ow, stream);
-        if (e != hipErrorNotSupported) return e;
-    }
-    homography_warp_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream>>>(img, B, Hi, Wi, C, M, ref, out, oh, ow);
-    return hipGetLastError();
-}
-
-hipError_t launch_vec2mtrx(const float *p, int B, int dim, int approx, float *out, hipStream_t stream)
-{
-    vec2mtrx_kernel<<<dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream>>>(p, B, dim, approx, out);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------
-// The rest of spatial_transformer.py's 2-D samplers: bicubic_interp (ST:966-1072), the symmetric-pad transformers
-// (SimilarityTransformer ST:311-371, AffineSymmetryTransformer ST:454-517, ProjectiveSymmetryTransformer ST:611-716) and
-// ElasticTransformer's thin-plate spline (ST:40-224).  One family of kernels, templated on where a pixel's source coordinates
-// come from (XS_*) and on the sampler (XI_*): stx3_tile_kernel for 3-channel frames (st3_tile_kernel's tile, tap gathers and
-// 16-byte row stores), stx_pixel_kernel (one thread per pixel, one sample per workgroup row of the grid) for other channel counts.
-// Bilinear sampling is st_taps / st_blend statement for statement; the existing kernels above are not touched.
-//   XS_COORDS  explicit x, y [B*oh*ow]                       (bicubic_interp)
-//   XS_THETA   Affine/ProjectiveTransformer's theta . grid   (interp_method='bicubic'; bilinear stays on st_transform)
-//   XS_SYM     the symmetric-pad transformers: the image padded by 100 px per side in SYMMETRIC mode is never materialised (a
-//              padded index p reads refl(p - 100)); the (oh+200) x (ow+200) grid is sampled only where
-//              resize_image_with_crop_or_pad keeps it, the pixels it pads are written as zeros
-//   XS_TPS     ElasticTransformer: coeff [2, K+3] = (source points + theta) . L_inv^T once per workgroup into LDS, then per
-//              pixel x_s = coeff_x . [x_t, y_t, 1, U_1..U_K] with U_k = r^2 ln r^2 evaluated in-kernel (no (K+1) x N table)
-// ---------------------------------------------------------------------------------
-enum { XS_COORDS = 0, XS_THETA = 1, XS_SYM = 2, XS_TPS = 3 };
-enum { XI_BILINEAR = 0, XI_BICUBIC = 1 };
-constexpr int STX_TPS_KMAX = 256;                    // g <= 16 control points per side (api.cpp)
-
-struct StxSrc {
-    const float *x, *y;            // XS_COORDS
-    const float *theta;            // XS_THETA [B,tdim]; XS_SYM [B,6|8|4]; XS_TPS [B,2K]
-    const float *linv_t;           // XS_TPS: transpose(L_inv[:,3:]) [K, K+3]
-    int tdim, kind, g, B;          // kind: XS_SYM's VSTAB_SYM_* (0 affine, 1 projective, 2 similarity); g: TPS grid side
-    int gh, gw;                    // the linspace sampling grid
-    float sx, sy;                  // its steps 2/(n-1), divided once on the host (lin11's quotient)
-    int Hs, Ws;                    // extent the sampler sees: (H+200, W+200) for XS_SYM, (H, W) otherwise
-    int pady, cropy, leny, padx, cropx, lenx;        // crop-or-pad: final i reads grid i - pad + crop when 0 <= i - pad < len
-};
 
 // np.pad(mode='symmetric') index map for one reflection (|u| stays within one image size: H, W >= 100 on the host)
 __device__ __forceinline__ int refl(int u, int n) { return u < 0 ? -u - 1 : (u >= n ? 2 * n - 1 - u : u); }
 
 // the sample's 2x3 / 3x3 matrix, theta pre-maps included, every product and sum its own fp32 operation
 template <int SRC>
-__device__ __forceinline__ void stx_matrix(const StxSrc &S, int n, float *th)
+__device__ __forceinline__ void st_matrix(const StSrc &S, int n, float *th)
 {
-    if (SRC == XS_THETA) {
-        const float *tp = S.theta + (long long)n * S.tdim;
+    if (SRC == XS_THETA || SRC == XS_HOMOG) {
+        const float *tp = S.theta + (long long)n * S.tdim;       // wave-uniform: scalar loads
 #pragma unroll
         for (int k = 0; k < 9; ++k) th[k] = k < S.tdim ? tp[k] : 1.0f;
+        if (SRC == XS_HOMOG && S.ref) {                            // M = refMtrx . pMtrx, here instead of a GEMM launch in front
+            float pm[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) pm[k] = th[k];
+            compose3(S.ref, pm, th);
+        }
     } else if (SRC == XS_SYM && S.kind == 0) {           // theta * [[.1,0,.2],[.1,0,.2]] * 0 + I (ST:503-505): NaN / inf survive
         const float c[6] = {0.1f, 0.0f, 0.2f, 0.1f, 0.0f, 0.2f}, I[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
         const float *tp = S.theta + (long long)n * 6;
@@ -491,15 +183,15 @@ __device__ __forceinline__ void stx_matrix(const StxSrc &S, int n, float *th)
     }
 }
 
-// stx_matrix for a whole workgroup: SimilarityTransformer's six entries (cos / sin, the interleave's divisions) are computed by
-// six threads into LDS instead of by every thread; the others as stx_matrix.  Every thread of the workgroup calls it.
+// st_matrix for a whole workgroup: SimilarityTransformer's six entries (cos / sin, the interleave's divisions) are computed by
+// six threads into LDS instead of by every thread; the others as st_matrix.  Every thread of the workgroup calls it.
 template <int SRC>
-__device__ __forceinline__ void stx_matrix_wg(const StxSrc &S, int n, float *th, float *sm)
+__device__ __forceinline__ void st_matrix_wg(const StSrc &S, int n, float *th, float *sm)
 {
     if (SRC == XS_SYM && S.kind == 2) {
         if (threadIdx.x == 0) {
             float m[9];
-            stx_matrix<SRC>(S, n, m);
+            st_matrix<SRC>(S, n, m);
 #pragma unroll
             for (int k = 0; k < 6; ++k) sm[k] = m[k];
         }
@@ -507,15 +199,15 @@ __device__ __forceinline__ void stx_matrix_wg(const StxSrc &S, int n, float *th,
 #pragma unroll
         for (int k = 0; k < 6; ++k) th[k] = sm[k];
         th[6] = th[7] = 0.f; th[8] = 1.f;
-    } else if (SRC == XS_THETA || SRC == XS_SYM) {
-        stx_matrix<SRC>(S, n, th);
+    } else if (SRC != XS_COORDS && SRC != XS_TPS) {
+        st_matrix<SRC>(S, n, th);
     }
 }
 
 // TPS coefficients of sample n into LDS: cf[r*(K+3) + j] = sum_k (src_r[k] + theta[n, r*K+k]) * linv_t[k, j] (ST:108, 145-147), in
 // k order, and the control points (lin11 of k % g, k / g) after them for the per-pixel loop.  All threads of the workgroup take
 // part; the caller synchronises.
-__device__ __forceinline__ void stx_tps_coeff(const StxSrc &S, int n, float *cf)
+__device__ __forceinline__ void st_tps_coeff(const StSrc &S, int n, float *cf)
 {
     const int K = S.g * S.g, K3 = K + 3;
     const float *tp = S.theta + (long long)n * 2 * K;
@@ -536,7 +228,7 @@ __device__ __forceinline__ void stx_tps_coeff(const StxSrc &S, int n, float *cf)
 
 // normalised source coordinates of grid point (gx, gy) of sample n
 template <int SRC>
-__device__ __forceinline__ void stx_coords(const StxSrc &S, const float *th, const float *cf, int n, int gx, int gy, float &xs, float &ys)
+__device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const float *cf, int n, int gx, int gy, float &xs, float &ys)
 {
     if (SRC == XS_COORDS) {
         const long long i = ((long long)n * S.gh + gy) * S.gw + gx;
@@ -593,35 +285,74 @@ __device__ __forceinline__ void cubic_axis(float v, int n, int *ix, float *w)
 
 struct Cubic { int x[4], y[4]; float wx[4], wy[4]; };
 
-// a sampled-extent index to an image index: the symmetric pad for XS_SYM, the identity otherwise
+// a sampled-extent index to an image index, and the extent the sampler sees: the symmetric pad for XS_SYM, the image otherwise
 template <int SRC>
-__device__ __forceinline__ int stx_src(int p, int n) { return SRC == XS_SYM ? refl(p - 100, n) : p; }
+__device__ __forceinline__ int st_src(int p, int n) { return SRC == XS_SYM ? refl(p - 100, n) : p; }
+template <int SRC>
+__device__ __forceinline__ int st_extent(int n) { return SRC == XS_SYM ? n + 200 : n; }
 
-// one output pixel, any channel count; `live` false writes zeros (the crop-or-pad padding)
-template <int SRC, int INTERP>
-__device__ __forceinline__ void stx_sample_pixel(const float *__restrict__ b, int H, int W, int C, const StxSrc &S, float xs, float ys,
-                                                 bool live, float *__restrict__ o)
+// final pixel (fx, fy) -> grid point and whether the crop keeps it (only XS_SYM crops or pads)
+template <int SRC>
+__device__ __forceinline__ bool st_grid_pos(const StSrc &S, int fx, int fy, int &gx, int &gy)
 {
-    if (!live) {
-        for (int c = 0; c < C; ++c) o[c] = 0.0f;
-        return;
+    if (SRC != XS_SYM) { gx = fx; gy = fy; return true; }
+    const int uy = fy - S.pady, ux = fx - S.padx;
+    gy = min(max(uy + S.cropy, 0), S.gh - 1);
+    gx = min(max(ux + S.cropx, 0), S.gw - 1);
+    return uy >= 0 && uy < S.leny && ux >= 0 && ux < S.lenx;
+}
+
+// the bilinear taps of a grid point: from its normalised source coordinates, or (XS_HOMOG) from the homography itself
+template <int SRC>
+__device__ __forceinline__ Taps st_point_taps(const StSrc &S, const float *th, int gx, int gy, float xs, float ys, int H, int W)
+{
+    if (SRC == XS_HOMOG) return homog_taps(th, gx, gy, S.dsx, S.dsy, H, W);
+    return st_taps(xs, ys, st_extent<SRC>(H), st_extent<SRC>(W));
+}
+
+// any channel count, one thread per pixel: workgroups [n * bps, (n + 1) * bps) belong to sample n, so the TPS coefficients are
+// computed once per workgroup.  amdgpu_waves_per_eu(4) is there for ONE instantiation, <XS_COORDS, XI_BICUBIC>: the other bicubic
+// ones (16 taps in flight) reach four waves per SIMD on their own (124-126 VGPRs), this one the register allocator otherwise lets
+// drift to 152; the bilinear instantiations (22-35 VGPRs, eight waves) are not affected.
+template <int SRC, int INTERP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void st_pixel_kernel(const float *__restrict__ img, int H, int W, int C, StSrc S,
+                                                       float *__restrict__ out, int FH, int FW, unsigned bps)
+{
+    __shared__ float cf[SRC == XS_TPS ? 2 * (ST_TPS_KMAX + 3) + 2 * ST_TPS_KMAX : 8];
+    const int n = (int)(blockIdx.x / bps);
+    if (SRC == XS_TPS) {
+        st_tps_coeff(S, n, cf);
+        __syncthreads();
     }
-    if (INTERP == XI_BILINEAR) {
-        const Taps t = st_taps(xs, ys, S.Hs, S.Ws);
-        const long long i00 = ((long long)stx_src<SRC>(t.ya, H) * W + stx_src<SRC>(t.xa, W)) * C;
-        const long long i01 = ((long long)stx_src<SRC>(t.ya, H) * W + stx_src<SRC>(t.xb, W)) * C;
-        const long long i10 = ((long long)stx_src<SRC>(t.yb, H) * W + stx_src<SRC>(t.xa, W)) * C;
-        const long long i11 = ((long long)stx_src<SRC>(t.yb, H) * W + stx_src<SRC>(t.xb, W)) * C;
+    float th[9];
+    st_matrix_wg<SRC>(S, n, th, cf);
+    const long long p = (long long)(blockIdx.x - (unsigned)n * bps) * 256 + threadIdx.x;
+    if (p >= (long long)FH * FW) return;
+    const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+    int gx, gy;
+    const bool live = st_grid_pos<SRC>(S, fx, fy, gx, gy);
+    float xs = 0.f, ys = 0.f;
+    if (SRC != XS_HOMOG) st_coords<SRC>(S, th, cf, n, gx, gy, xs, ys);
+    const float *__restrict__ b = img + (long long)n * H * W * C;
+    float *__restrict__ o = out + ((long long)n * FH * FW + p) * C;
+    if (!live) {                                         // the crop-or-pad padding
+        for (int c = 0; c < C; ++c) o[c] = 0.0f;
+    } else if (INTERP == XI_BILINEAR) {
+        const Taps t = st_point_taps<SRC>(S, th, gx, gy, xs, ys, H, W);
+        const long long i00 = ((long long)st_src<SRC>(t.ya, H) * W + st_src<SRC>(t.xa, W)) * C;
+        const long long i01 = ((long long)st_src<SRC>(t.ya, H) * W + st_src<SRC>(t.xb, W)) * C;
+        const long long i10 = ((long long)st_src<SRC>(t.yb, H) * W + st_src<SRC>(t.xa, W)) * C;
+        const long long i11 = ((long long)st_src<SRC>(t.yb, H) * W + st_src<SRC>(t.xb, W)) * C;
         const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
         for (int c = 0; c < C; ++c)
-            o[c] = st_blend<FAM_ST_THETA>(t, v00 ? b[i00 + c] : 0.f, v01 ? b[i01 + c] : 0.f, v10 ? b[i10 + c] : 0.f, v11 ? b[i11 + c] : 0.f);
+            o[c] = st_blend<SRC == XS_HOMOG>(t, v00 ? b[i00 + c] : 0.f, v01 ? b[i01 + c] : 0.f, v10 ? b[i10 + c] : 0.f, v11 ? b[i11 + c] : 0.f);
     } else {
         Cubic q;
-        cubic_axis(xs, S.Ws, q.x, q.wx);
-        cubic_axis(ys, S.Hs, q.y, q.wy);
+        cubic_axis(xs, st_extent<SRC>(W), q.x, q.wx);
+        cubic_axis(ys, st_extent<SRC>(H), q.y, q.wy);
         long long row[4], col[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { row[i] = (long long)stx_src<SRC>(q.y[i], H) * W; col[i] = stx_src<SRC>(q.x[i], W); }
+        for (int i = 0; i < 4; ++i) { row[i] = (long long)st_src<SRC>(q.y[i], H) * W; col[i] = st_src<SRC>(q.x[i], W); }
         for (int c = 0; c < C; ++c) {
             float r[4];
 #pragma unroll
@@ -633,189 +364,247 @@ __device__ __forceinline__ void stx_sample_pixel(const float *__restrict__ b, in
     }
 }
 
-// final pixel (fx, fy) -> grid point and whether the crop keeps it
-__device__ __forceinline__ bool stx_grid_pos(const StxSrc &S, int fx, int fy, int &gx, int &gy)
-{
-    const int uy = fy - S.pady, ux = fx - S.padx;
-    gy = min(max(uy + S.cropy, 0), S.gh - 1);
-    gx = min(max(ux + S.cropx, 0), S.gw - 1);
-    return uy >= 0 && uy < S.leny && ux >= 0 && ux < S.lenx;
-}
+// ---------------------------------------------------------------------------------
+// 3-channel frames (24 B/px algorithmic: 12 gathered + 12 written, + 8 with explicit coordinates).
+// Shaped like tf_warp's tile kernel (flow_ops.hip, warp3_tile_kernel; profiles/README.md "r02 warp study"): a workgroup owns a
+// 16 x 32 tile of ONE sample's output pixels and a wave instruction works on a 4 x 16 patch, so the lines a gather touches are a
+// compact 2-D footprint under any rotation; one 3-dword load per tap; results leave through LDS as 16-byte stores of whole
+// 384-byte tile rows (ow % 4 == 0; 12-byte stores otherwise); XCD-contiguous tile order.
+// Measured and rejected twice (profiles/README.md "r03 sampler study"): staging the source window in LDS -- bounding box of the taps
+// by DPP reductions, aligned 16-byte fill, corners from LDS -- cuts the L1 lookups 3x (0.50 instead of 1.56 per pixel) and is
+// SLOWER both per workgroup tile (commit 2076632: four barriers, three dependent phases; 0.34-0.39 of 8 TB/s against 0.53-0.65)
+// and per wave patch with no barrier at all (0.41-0.49): what bounds these kernels is requests in flight, not tag lookups.  So the
+// bilinear path of the theta, coordinate and homography sources issues the gathers of both of a thread's pixels before it blends
+// either (arrays over PPT).  Bicubic gathers 16 taps per pixel, row by row in tap order, one pixel at a time: both pixels' 32 taps
+// in flight cost registers and occupancy.
+// ---------------------------------------------------------------------------------
+using StTile = Tile3<>;
 
-// any channel count: grid (pixel blocks, B), one sample per workgroup so the TPS coefficients are computed once per workgroup
-template <int SRC, int INTERP>
-__global__ __launch_bounds__(256) void stx_pixel_kernel(const float *__restrict__ img, int H, int W, int C, StxSrc S,
-                                                        float *__restrict__ out, int FH, int FW)
+template <int SRC, bool STAGE, int INTERP>
+__global__ __launch_bounds__(256) void st3_tile_kernel(const float *__restrict__ img, int H, int W, StSrc S,
+                                                       float *__restrict__ out, int FH, int FW, int tiles_x, int tiles_y)
 {
-    __shared__ float cf[SRC == XS_TPS ? 2 * (STX_TPS_KMAX + 3) + 2 * STX_TPS_KMAX : 8];
-    const int n = blockIdx.y;
+    constexpr int PPT = StTile::PPT;
+    __shared__ __attribute__((aligned(16))) float lds[STAGE ? StTile::TH * StTile::TW * 3 : 4];
+    __shared__ float cf[SRC == XS_TPS ? 2 * (ST_TPS_KMAX + 3) + 2 * ST_TPS_KMAX : 8];
+    const StTile tile(tiles_x, tiles_y);
+    const int n = tile.n;
     if (SRC == XS_TPS) {
-        stx_tps_coeff(S, n, cf);
+        st_tps_coeff(S, n, cf);
         __syncthreads();
     }
     float th[9];
-    stx_matrix_wg<SRC>(S, n, th, cf);
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= (long long)FH * FW) return;
-    const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
-    int gx, gy;
-    const bool live = stx_grid_pos(S, fx, fy, gx, gy);
-    float xs, ys;
-    stx_coords<SRC>(S, th, cf, n, gx, gy, xs, ys);
-    stx_sample_pixel<SRC, INTERP>(img + (long long)n * H * W * C, H, W, C, S, xs, ys, live, out + ((long long)n * FH * FW + p) * C);
-}
-
-// 3-channel frames: st3_tile_kernel's 16 x 32 tile of one sample, XCD-contiguous tile order, one 3-dword load per tap and rows
-// leaving through LDS as 16-byte stores.  Bicubic gathers 16 taps per pixel, row by row in tap order.
-template <int SRC, int INTERP, bool STAGE>
-__global__ __launch_bounds__(256) void stx3_tile_kernel(const float *__restrict__ img, int H, int W, StxSrc S,
-                                                        float *__restrict__ out, int FH, int FW, int tiles_x, int tiles_y)
-{
-    constexpr int TW = ST_TW, TH = ST_TH, PPT = ST_PPT, WW = ST_WW, WH = ST_WH, PPR = ST_PPR;
-    __shared__ __attribute__((aligned(16))) float lds[STAGE ? ST_TH * ST_TW * 3 : 4];
-    __shared__ float cf[SRC == XS_TPS ? 2 * (STX_TPS_KMAX + 3) + 2 * STX_TPS_KMAX : 8];
-    unsigned bx, by, bz;
-    xcd_remap_calc(gridDim.x, 1, 1, blockIdx.x, bx, by, bz);
-    const int tpi = tiles_x * tiles_y;
-    const int n = (int)bx / tpi, trem = (int)bx - n * tpi;
-    const int ty0 = (trem / tiles_x) * TH, tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (SRC == XS_TPS) {
-        stx_tps_coeff(S, n, cf);
-        __syncthreads();
-    }
-    float th[9];
-    stx_matrix_wg<SRC>(S, n, th, cf);
+    st_matrix_wg<SRC>(S, n, th, cf);
     const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + (long long)n * H * W;     // 3 B H W < 2^31 (host)
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const int q = j * 4 + wave;
-        const int y = ty0 + (q / PPR) * WH + lane / WW, x = tx0 + (q % PPR) * WW + lane % WW;
-        const bool ok = y < FH && x < FW;
-        const int yy = min(y, FH - 1), xx = min(x, FW - 1);
+    int yy[PPT], xx[PPT];
+    bool ok[PPT], live[PPT];
+    float xs[PPT], ys[PPT];
+    Taps t[PPT];
+    // pass j's pixel: its source coordinates and, for the bilinear sampler, its taps
+    auto point = [&](int j) {
+        ok[j] = tile.y(j) < FH && tile.x(j) < FW;
+        yy[j] = min(tile.y(j), FH - 1); xx[j] = min(tile.x(j), FW - 1);          // a pixel beyond the output repeats an edge pixel of this tile (not stored)
         int gx, gy;
-        const bool live = stx_grid_pos(S, xx, yy, gx, gy);
-        float xs, ys;
-        stx_coords<SRC>(S, th, cf, n, gx, gy, xs, ys);
-        rgb3 r;
-        if (INTERP == XI_BILINEAR) {
-            const Taps t = st_taps(xs, ys, S.Hs, S.Ws);
-            const int ya = stx_src<SRC>(t.ya, H) * W, yb = stx_src<SRC>(t.yb, H) * W, xa = stx_src<SRC>(t.xa, W), xb = stx_src<SRC>(t.xb, W);
-            const rgb3 I00 = b[ya + xa], I01 = b[ya + xb], I10 = b[yb + xa], I11 = b[yb + xb];
-            const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
-            r.r = st_blend<FAM_ST_THETA>(t, v00 ? I00.r : 0.f, v01 ? I01.r : 0.f, v10 ? I10.r : 0.f, v11 ? I11.r : 0.f);
-            r.g = st_blend<FAM_ST_THETA>(t, v00 ? I00.g : 0.f, v01 ? I01.g : 0.f, v10 ? I10.g : 0.f, v11 ? I11.g : 0.f);
-            r.b = st_blend<FAM_ST_THETA>(t, v00 ? I00.b : 0.f, v01 ? I01.b : 0.f, v10 ? I10.b : 0.f, v11 ? I11.b : 0.f);
+        live[j] = st_grid_pos<SRC>(S, xx[j], yy[j], gx, gy);
+        if (SRC != XS_HOMOG) st_coords<SRC>(S, th, cf, n, gx, gy, xs[j], ys[j]);
+        if (INTERP == XI_BILINEAR) t[j] = st_point_taps<SRC>(S, th, gx, gy, xs[j], ys[j], H, W);
+    };
+    auto put = [&](int j, rgb3 r) {
+        if (!live[j]) r.r = r.g = r.b = 0.0f;
+        if (STAGE) *reinterpret_cast<rgb3 *>(lds + tile.staged(j) * 3) = r;
+        else if (ok[j]) reinterpret_cast<rgb3 *>(out)[((long long)n * FH + yy[j]) * FW + xx[j]] = r;
+    };
+    if (INTERP == XI_BILINEAR) {
+        rgb3 I00[PPT], I01[PPT], I10[PPT], I11[PPT];
+        auto gather = [&](int j) {
+            const int ya = st_src<SRC>(t[j].ya, H) * W, yb = st_src<SRC>(t[j].yb, H) * W, xa = st_src<SRC>(t[j].xa, W), xb = st_src<SRC>(t[j].xb, W);
+            I00[j] = b[ya + xa]; I01[j] = b[ya + xb]; I10[j] = b[yb + xa]; I11[j] = b[yb + xb];
+        };
+        auto blend = [&](int j) {
+            const bool v00 = t[j].vxa && t[j].vya, v01 = t[j].vxb && t[j].vya, v10 = t[j].vxa && t[j].vyb, v11 = t[j].vxb && t[j].vyb;
+            rgb3 r;
+            r.r = st_blend<SRC == XS_HOMOG>(t[j], v00 ? I00[j].r : 0.f, v01 ? I01[j].r : 0.f, v10 ? I10[j].r : 0.f, v11 ? I11[j].r : 0.f);
+            r.g = st_blend<SRC == XS_HOMOG>(t[j], v00 ? I00[j].g : 0.f, v01 ? I01[j].g : 0.f, v10 ? I10[j].g : 0.f, v11 ? I11[j].g : 0.f);
+            r.b = st_blend<SRC == XS_HOMOG>(t[j], v00 ? I00[j].b : 0.f, v01 ? I01[j].b : 0.f, v10 ? I10[j].b : 0.f, v11 ? I11[j].b : 0.f);
+            put(j, r);
+        };
+        // The gathers of both pixels are issued before either is blended (requests in flight, above).  The symmetric-pad and
+        // thin-plate-spline sources, heavier per pixel, keep the one-pixel-at-a-time order they were written and measured in
+        // (DESIGN.md section 11); both in flight was 2-3 % slower for the symmetric-pad ones when tried.
+        if (SRC == XS_SYM || SRC == XS_TPS) {
+#pragma unroll
+            for (int j = 0; j < PPT; ++j) { point(j); gather(j); blend(j); }
         } else {
+#pragma unroll
+            for (int j = 0; j < PPT; ++j) point(j);
+#pragma unroll
+            for (int j = 0; j < PPT; ++j) gather(j);
+#pragma unroll
+            for (int j = 0; j < PPT; ++j) blend(j);
+        }
+    } else {                                         // one pixel at a time
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            point(j);
             Cubic c;
-            cubic_axis(xs, S.Ws, c.x, c.wx);
-            cubic_axis(ys, S.Hs, c.y, c.wy);
+            cubic_axis(xs[j], st_extent<SRC>(W), c.x, c.wx);
+            cubic_axis(ys[j], st_extent<SRC>(H), c.y, c.wy);
             int col[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) col[i] = stx_src<SRC>(c.x[i], W);
+            for (int i = 0; i < 4; ++i) col[i] = st_src<SRC>(c.x[i], W);
             rgb3 rw[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int ro = stx_src<SRC>(c.y[i], H) * W;
+                const int ro = st_src<SRC>(c.y[i], H) * W;
                 const rgb3 I0 = b[ro + col[0]], I1 = b[ro + col[1]], I2 = b[ro + col[2]], I3 = b[ro + col[3]];
                 rw[i].r = ((c.wx[0] * I0.r + c.wx[1] * I1.r) + c.wx[2] * I2.r) + c.wx[3] * I3.r;
                 rw[i].g = ((c.wx[0] * I0.g + c.wx[1] * I1.g) + c.wx[2] * I2.g) + c.wx[3] * I3.g;
                 rw[i].b = ((c.wx[0] * I0.b + c.wx[1] * I1.b) + c.wx[2] * I2.b) + c.wx[3] * I3.b;
             }
+            rgb3 r;
             r.r = ((c.wy[0] * rw[0].r + c.wy[1] * rw[1].r) + c.wy[2] * rw[2].r) + c.wy[3] * rw[3].r;
             r.g = ((c.wy[0] * rw[0].g + c.wy[1] * rw[1].g) + c.wy[2] * rw[2].g) + c.wy[3] * rw[3].g;
             r.b = ((c.wy[0] * rw[0].b + c.wy[1] * rw[1].b) + c.wy[2] * rw[2].b) + c.wy[3] * rw[3].b;
-        }
-        if (!live) r.r = r.g = r.b = 0.0f;
-        if (STAGE) {
-            *reinterpret_cast<rgb3 *>(lds + (((q / PPR) * WH + lane / WW) * TW + (q % PPR) * WW + lane % WW) * 3) = r;
-        } else if (ok) {
-            reinterpret_cast<rgb3 *>(out)[((long long)n * FH + yy) * FW + xx] = r;
+            put(j, r);
         }
     }
-    if (STAGE) {       // FW % 4 == 0 (host): a tile row is TW*12 bytes from a 16-byte aligned address
-        __syncthreads();
-        constexpr int R4 = TW * 3 / 4;
-        const int vw3 = min(TW, FW - tx0) * 3;
-        for (int e = threadIdx.x; e < TH * R4; e += 256) {
-            const int row = e / R4, c4 = e - row * R4;
-            if (ty0 + row >= FH || c4 * 4 >= vw3) continue;
-            float *o = out + (((long long)n * FH + ty0 + row) * FW + tx0) * 3 + c4 * 4;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(lds + row * TW * 3 + c4 * 4);
-            if (c4 * 4 + 4 <= vw3) *reinterpret_cast<f32x4 *>(o) = v;
-            else for (int i = 0; c4 * 4 + i < vw3; ++i) o[i] = v[i];
-        }
-    }
+    if (STAGE) tile.template store_rows<3>(lds, out, FH, FW);          // FW % 4 == 0 (host): a tile row is TW*12 bytes from a 16-byte aligned address
 }
 
+// Picks the kernel of a launch: the tile kernel for 3-channel frames of a shape that is its own, the pixel kernel otherwise.
+// `slot` / `px_bytes`: the launch_timed slot and algorithmic bytes per output pixel of the tile launch (slot < 0: not timed).
 template <int SRC, int INTERP>
-static hipError_t launch_stx(const float *img, int B, int H, int W, int C, StxSrc S, float *out, int FH, int FW, hipStream_t stream)
+static hipError_t launch_st(int slot, double px_bytes, const float *img, int B, int H, int W, int C, StSrc S, float *out, int FH, int FW,
+                            hipStream_t stream)
 {
     S.B = B;
-    S.sx = S.gw > 1 ? 2.0f / (float)(S.gw - 1) : 0.0f;
-    S.sy = S.gh > 1 ? 2.0f / (float)(S.gh - 1) : 0.0f;
-    if (C == 3) {
-        const long long tx = (FW + ST_TW - 1) / ST_TW, ty = (FH + ST_TH - 1) / ST_TH, tiles = tx * ty * B;
-        if (tiles < (1ll << 31) && (long long)B * H * W * 3 < (1ll << 31) && (long long)B * FH * FW * 3 < (1ll << 31)) {
-            const dim3 grid((unsigned)tiles), block(256);
-            if ((FW & 3) == 0 && ((uintptr_t)out & 15) == 0)
-                stx3_tile_kernel<SRC, INTERP, true><<<grid, block, 0, stream>>>(img, H, W, S, out, FH, FW, (int)tx, (int)ty);
-            else
-                stx3_tile_kernel<SRC, INTERP, false><<<grid, block, 0, stream>>>(img, H, W, S, out, FH, FW, (int)tx, (int)ty);
-            return hipGetLastError();
-        }
+    S.sx = S.gw > 1 ? 2.0f / (float)(S.gw - 1) : 0.0f; S.sy = S.gh > 1 ? 2.0f / (float)(S.gh - 1) : 0.0f;
+    S.dsx = S.gw > 1 ? 2.0 / (double)(S.gw - 1) : 0.0; S.dsy = S.gh > 1 ? 2.0 / (double)(S.gh - 1) : 0.0;
+    int tx, ty;
+    dim3 grid;
+    if (C == 3 && StTile::plan(B, FH, FW, 3 * std::max((long long)B * H * W, (long long)B * FH * FW), tx, ty, grid)) {
+        const double bytes = px_bytes * B * FH * FW;       // every output pixel reads ~one source pixel, writes one (+ x, y)
+        if (StTile::staged_ok(out, FW, 3))
+            return launch_timed(slot, bytes, st3_tile_kernel<SRC, true, INTERP>, grid, dim3(256), stream, img, H, W, S, out, FH, FW, tx, ty);
+        return launch_timed(slot, bytes, st3_tile_kernel<SRC, false, INTERP>, grid, dim3(256), stream, img, H, W, S, out, FH, FW, tx, ty);
     }
-    const long long blocks = ((long long)FH * FW + 255) / 256;
-    if (blocks >= (1ll << 31) || B > 65535) return hipErrorInvalidValue;
-    stx_pixel_kernel<SRC, INTERP><<<dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, stream>>>(img, H, W, C, S, out, FH, FW);
+    const long long bps = ((long long)FH * FW + 255) / 256;
+    if (bps * B >= (1ll << 31)) return hipErrorInvalidValue;
+    st_pixel_kernel<SRC, INTERP><<<dim3((unsigned)(bps * B)), dim3(256), 0, stream>>>(img, H, W, C, S, out, FH, FW, (unsigned)bps);
     return hipGetLastError();
 }
 
-static StxSrc stx_plain(int oh, int ow)
+// a source whose sampling grid is the output: no crop, no pad
+static StSrc st_plain(int oh, int ow)
 {
-    StxSrc S{};
-    S.gh = oh; S.gw = ow; S.leny = oh; S.lenx = ow;
+    StSrc S{};
+    S.gh = oh; S.gw = ow;
     return S;
+}
+
+hipError_t launch_st_interp(const float *img, int B, int H, int W, int C, const float *x, const float *y, int oh, int ow, float *out,
+                            hipStream_t stream)
+{
+    StSrc S = st_plain(oh, ow);
+    S.x = x; S.y = y;
+    return launch_st<XS_COORDS, XI_BILINEAR>(HBM_SLOT_ST, 32.0, img, B, H, W, C, S, out, oh, ow, stream);
+}
+
+hipError_t launch_st_transform(const float *img, int B, int H, int W, int C, const float *theta, int tdim, float *out, int oh,
+                               int ow, hipStream_t stream)
+{
+    StSrc S = st_plain(oh, ow);
+    S.theta = theta; S.tdim = tdim;
+    return launch_st<XS_THETA, XI_BILINEAR>(HBM_SLOT_ST, 24.0, img, B, H, W, C, S, out, oh, ow, stream);
+}
+
+hipError_t launch_homography_warp(const float *img, int B, int Hi, int Wi, int C, const float *M, float *out, int oh, int ow,
+                                  hipStream_t stream, const float *ref)
+{
+    StSrc S = st_plain(oh, ow);
+    S.theta = M; S.tdim = 9; S.ref = ref;
+    return launch_st<XS_HOMOG, XI_BILINEAR>(HBM_SLOT_HOMOG, 24.0, img, B, Hi, Wi, C, S, out, oh, ow, stream);
+}
+
+hipError_t launch_st_meshgrid(float *out, int oh, int ow, hipStream_t stream)
+{
+    st_meshgrid_kernel<<<dim3((unsigned)((oh * ow + 255) / 256)), dim3(256), 0, stream>>>(out, oh, ow);
+    return hipGetLastError();
+}
+
+// warp.vec2mtrx (warp.py:25-43): sl(3) / affine generator -> matrix exponential by Taylor series,
+// pMtrx = sum_{i=0}^{warpApprox-1} A^i / i!   (fp32, one thread per batch element)
+__global__ void vec2mtrx_kernel(const float *__restrict__ p, int B, int dim, int approx, float *__restrict__ out)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= B) return;
+    const float *q = p + (long long)n * dim;
+    float A[9];
+    if (dim == 8) {
+        A[0] = q[2]; A[1] = q[1]; A[2] = q[0];
+        A[3] = q[5]; A[4] = -q[2] - q[6]; A[5] = q[4];
+        A[6] = q[3]; A[7] = q[7]; A[8] = q[6];
+    } else {
+        A[0] = q[0]; A[1] = q[1]; A[2] = q[2];
+        A[3] = q[3]; A[4] = q[4]; A[5] = q[5];
+        A[6] = 0.f; A[7] = 0.f; A[8] = 0.f;
+    }
+    float P[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Nm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    float denom = 1.0f;
+    for (int i = 1; i < approx; ++i) {
+        float T[9];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) T[r * 3 + c] = (Nm[r * 3] * A[c] + Nm[r * 3 + 1] * A[3 + c]) + Nm[r * 3 + 2] * A[6 + c];
+        denom *= (float)i;
+        for (int k = 0; k < 9; ++k) { Nm[k] = T[k]; P[k] += T[k] / denom; }
+    }
+    for (int k = 0; k < 9; ++k) out[(long long)n * 9 + k] = P[k];
+}
+
+hipError_t launch_vec2mtrx(const float *p, int B, int dim, int approx, float *out, hipStream_t stream)
+{
+    vec2mtrx_kernel<<<dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream>>>(p, B, dim, approx, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_st_bicubic_interp(const float *img, int B, int H, int W, int C, const float *x, const float *y, int oh, int ow,
                                     float *out, hipStream_t stream)
 {
-    StxSrc S = stx_plain(oh, ow);
-    S.x = x; S.y = y; S.Hs = H; S.Ws = W;
-    return launch_stx<XS_COORDS, XI_BICUBIC>(img, B, H, W, C, S, out, oh, ow, stream);
+    StSrc S = st_plain(oh, ow);
+    S.x = x; S.y = y;
+    return launch_st<XS_COORDS, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
 }
 
 hipError_t launch_st_transform_interp(const float *img, int B, int H, int W, int C, const float *theta, int tdim, int interp,
                                       float *out, int oh, int ow, hipStream_t stream)
 {
     if (interp == XI_BILINEAR) return launch_st_transform(img, B, H, W, C, theta, tdim, out, oh, ow, stream);
-    StxSrc S = stx_plain(oh, ow);
-    S.theta = theta; S.tdim = tdim; S.Hs = H; S.Ws = W;
-    return launch_stx<XS_THETA, XI_BICUBIC>(img, B, H, W, C, S, out, oh, ow, stream);
+    StSrc S = st_plain(oh, ow);
+    S.theta = theta; S.tdim = tdim;
+    return launch_st<XS_THETA, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
 }
 
 hipError_t launch_st_symmetry_transform(const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
                                         float *out, int oh, int ow, hipStream_t stream)
 {
-    StxSrc S{};
+    StSrc S{};
     S.theta = theta; S.kind = kind;
-    S.gh = oh + 200; S.gw = ow + 200; S.Hs = H + 200; S.Ws = W + 200;
+    S.gh = oh + 200; S.gw = ow + 200;
     // resize_image_with_crop_or_pad(out, ow, oh) (ST:343, 488, 682): target height ow, width oh -- swapped
     const int th = ow, tw = oh;
     S.cropy = max((S.gh - th) / 2, 0); S.pady = max((th - S.gh) / 2, 0); S.leny = min(S.gh, th);
     S.cropx = max((S.gw - tw) / 2, 0); S.padx = max((tw - S.gw) / 2, 0); S.lenx = min(S.gw, tw);
-    if (interp == XI_BILINEAR) return launch_stx<XS_SYM, XI_BILINEAR>(img, B, H, W, C, S, out, th, tw, stream);
-    return launch_stx<XS_SYM, XI_BICUBIC>(img, B, H, W, C, S, out, th, tw, stream);
+    if (interp == XI_BILINEAR) return launch_st<XS_SYM, XI_BILINEAR>(-1, 0.0, img, B, H, W, C, S, out, th, tw, stream);
+    return launch_st<XS_SYM, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, th, tw, stream);
 }
 
 hipError_t launch_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                        int interp, float *out, int oh, int ow, hipStream_t stream)
 {
-    StxSrc S = stx_plain(oh, ow);
-    S.theta = theta; S.g = g; S.linv_t = linv_t; S.Hs = H; S.Ws = W;
-    if (interp == XI_BILINEAR) return launch_stx<XS_TPS, XI_BILINEAR>(img, B, H, W, C, S, out, oh, ow, stream);
-    return launch_stx<XS_TPS, XI_BICUBIC>(img, B, H, W, C, S, out, oh, ow, stream);
+    StSrc S = st_plain(oh, ow);
+    S.theta = theta; S.g = g; S.linv_t = linv_t;
+    if (interp == XI_BILINEAR) return launch_st<XS_TPS, XI_BILINEAR>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
+    return launch_st<XS_TPS, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
 }
 
 }  // namespace vstab

@@ -386,7 +386,7 @@ hipError_t launch_st_meshgrid(float *out, int oh, int ow, hipStream_t stream);
 hipError_t launch_homography_warp(const float *img, int B, int Hi, int Wi, int C, const float *M, float *out,
                                   int oh, int ow, hipStream_t stream, const float *ref = nullptr);
 hipError_t launch_vec2mtrx(const float *p, int B, int dim, int approx, float *out, hipStream_t stream);
-// the rest of spatial_transformer.py's 2-D samplers (sampler_ops.hip, stx3_tile_kernel / stx_pixel_kernel); interp: 0 bilinear, 1 bicubic
+// the rest of spatial_transformer.py's 2-D samplers (sampler_ops.hip, the same st3_tile_kernel / st_pixel_kernel family); interp: 0 bilinear, 1 bicubic
 hipError_t launch_st_bicubic_interp(const float *img, int B, int H, int W, int C, const float *x, const float *y, int oh, int ow,
                                     float *out, hipStream_t stream);
 hipError_t launch_st_transform_interp(const float *img, int B, int H, int W, int C, const float *theta, int tdim, int interp,

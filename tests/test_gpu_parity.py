@@ -59,8 +59,8 @@ def test_warp_nonfinite_flow_does_not_fault():
 
 @pytest.mark.parametrize("B,H,W", [(1, 37, 53), (2, 64, 96), (3, 31, 1031), (1, 270, 480), (5, 8, 9), (1, 1, 1)])
 def test_warp_tiled_kernel_bit_exact_vs_fp32_oracle(B, H, W):
-    # the 3-channel warp works on 1024-pixel tiles of the flat pixel index (ragged last tile, rows shorter and longer than a
-    # wave pass, tiles that span samples): same fp32 statement sequence as the oracle -> identical bits
+    # the 3-channel warp works on 16 x 32 pixel tiles of one sample (ragged right and bottom tiles, images narrower and wider than a
+    # tile row, smaller than one tile): same fp32 statement sequence as the oracle -> identical bits
     g = torch.Generator().manual_seed(B * 7919 + H * 31 + W)
     img = torch.rand(B, H, W, 3, generator=g)
     flow = torch.randn(B, H, W, 2, generator=g) * 6
