@@ -1,5 +1,5 @@
-// Shared between the translation units that implement the C ABI (api.cpp, nldf_api.cpp): the
-// context object, error plumbing and the helpers that turn a plain convolution into a launch plan.
+// Shared between the translation units that implement the C ABI (api.cpp, flownet_plan.cpp, flownet_forward.cpp, vgg_api.cpp,
+// nldf_api.cpp, train_api.cpp): the context object, error plumbing and the helpers that turn a plain convolution into a launch plan.
 #pragma once
 #include <cstdarg>
 #include <cstdio>
@@ -71,13 +71,27 @@ struct TraceRange {
     bool active;
 };
 
-// ---- helpers defined in api.cpp
-void choose_split(vstab::ConvParams &p, int BN, int BM = 128);
-vstab::ConvTile choose_tile_split(vstab::ConvParams &p, vstab::ConvTile tile, bool vec4);
-void set_layout(vstab::ConvParams &p, const vstab::KLayout &L);
-void set_ranges(vstab::ConvParams &p);
+void adopt_last_error(vstab_ctx *ctx);     // a context-less callee failed: its message becomes the context's
 const vstab_tensor *find(const vstab_tensor *t, int n, const std::string &name);
 bool shape_is(const vstab_tensor *t, std::initializer_list<int> s);
+inline size_t a256(size_t n) { return (n + 255) / 256 * 256; }
+
+// largest b in [0, B] with fits(b), for a monotone fits (chunking: the largest batch whose every tensor stays below 2 GiB)
+template <class Fits> int largest_fitting(int B, Fits fits)
+{
+    if (fits(B)) return B;
+    int lo = 0, hi = B;                     // invariant: lo fits (or 0), hi+1.. do not
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        if (fits(mid)) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// ---- the cost model of flownet_plan.cpp
+void choose_split(vstab::ConvParams &p, int BN, int BM = 128);
+vstab::ConvTile choose_tile_split(vstab::ConvParams &p, vstab::ConvTile tile, bool vec4);
+bool wino_applies(int B, int H, int W, int cin, int cout);      // does a 3x3 stride-1 pad-1 layer run in Winograd F(2x2,3x3) form?
 // plain conv (k x k, stride, zero pad) on an NHWC tensor whose pixel stride is cs_in >= cin (run mode
 // when cs_in == cin, tap mode otherwise); output slice [c_off, c_off+cout) of a cs_out-wide pixel
 bool fill_plain_conv(vstab::ConvParams &p, vstab::ConvTile &tile, bool &vec4, int B, int Hi, int Wi, int cin, int cs_in, int k,

@@ -3,6 +3,7 @@
 // built last and only at the reference's hard-wired geometry: pool1..pool5 of a 352x352 input
 // (176, 88, 44, 22, 11), outputs at 176x176 (NLDF.py:58-64, 74).
 #include "api_internal.h"
+#include "conv_desc.h"
 
 using namespace vstab;
 
@@ -85,8 +86,8 @@ extern "C" int vstab_nldf_load(vstab_ctx *ctx, const vstab_tensor *t, int count)
     auto conv = [&](const std::string &name, int k, int cin, int cs_in, int cout, size_t &ow, size_t &ob) -> bool {
         const vstab_tensor *W = find(t, count, name + "/W"), *b = find(t, count, name + "/b");
         if (!shape_is(W, {k, k, cin, cout}) || !shape_is(b, {cout})) { fail(ctx, VSTAB_E_WEIGHTS, "missing or mis-shaped variable %s/{W,b}", name.c_str()); return false; }
-        const int BN = cout >= 128 ? 128 : (cout > 32 ? 64 : 32), npad = round_up(cout, BN);
-        const KLayout L = cs_in == cin ? klayout_run(k, k, cs_in) : klayout_tap(k, k, cin, cs_in);
+        const int npad = padded_cols(cout);
+        const KLayout L = conv_layout(k, k, cin, cs_in);
         ones.assign(npad, 1.0);
         ob = reserve(npad);
         fold_bn(b->data, nullptr, nullptr, nullptr, cout, npad, ones.data(), host.data() + ob);
@@ -105,7 +106,7 @@ extern "C" int vstab_nldf_load(vstab_ctx *ctx, const vstab_tensor *t, int count)
         const int cin = CAT_C[k + 1], cout = UP_C[k];
         const vstab_tensor *W = find(t, count, name + "/W"), *b = find(t, count, name + "/b");
         if (!shape_is(W, {5, 5, cout, cin}) || !shape_is(b, {cout})) return fail(ctx, VSTAB_E_WEIGHTS, "missing or mis-shaped variable %s/{W,b}", name.c_str());
-        const int npad = round_up(cout, 128);
+        const int npad = padded_cols(cout);
         ones.assign(npad, 1.0);
         o.d_b[k] = reserve(npad);
         fold_bn(b->data, nullptr, nullptr, nullptr, cout, npad, ones.data(), host.data() + o.d_b[k]);
@@ -172,24 +173,9 @@ extern "C" int vstab_nldf_forward(vstab_ctx *ctx, const float *const *pools5, in
     }
     // top-down 5x5 stride-2 transposed convs + ReLU (:57-64): cat5 -> cat4[256:], ..., cat2 -> cat1[256:]
     for (int k = 3; k >= 0; --k) {
-        ConvParams p;
-        std::memset(&p, 0, sizeof p);
         const int hin = POOL_HW[k + 1], hout = POOL_HW[k], cin = CAT_C[k + 1], cout = UP_C[k];
-        p.B = B; p.Hi = hin; p.Wi = hin; p.Cs_in = cin;
-        const KLayout L = klayout_run(3, 3, cin);
-        set_layout(p, L);
-        p.s_in = 1; p.s_out = 2; p.Ho = hout; p.Wo = hout; p.Cs_out = CAT_C[k]; p.c_off = 2 * FEA;
-        p.N = cout; p.Npad = round_up(cout, 128); p.act = 2; p.nphase = 4;
-        const size_t phase_floats = (size_t)L.ktiles() * p.Npad * 32;
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px) {
-                ConvPhase &ph = p.ph[py * 2 + px];
-                ph.Hg = (hout - py + 1) / 2; ph.Wg = (hout - px + 1) / 2; ph.M = B * ph.Hg * ph.Wg;
-                ph.off_y = -1; ph.off_x = -1; ph.o_y = py; ph.o_x = px;
-                ph.w_off = (long long)(py * 2 + px) * phase_floats;
-                p.Mmax = std::max(p.Mmax, ph.M);
-            }
-        set_ranges(p);
+        const int off[2] = {-1, -1};             // 3 taps from input row j - 1 in both parities (the even ones use two: pack_deconv5)
+        ConvParams p = conv_desc_parity4(B, hin, hin, cin, cin, 3, off, hout, hout, cout, padded_cols(cout), CAT_C[k], 2 * FEA, 2);
         choose_split(p, 128);
         if ((size_t)p.nphase * p.ksplit * p.Mmax * p.Npad > part_floats) p.ksplit = 1;
         p.in = buf(cat_buf[k + 1]); p.out = buf(cat_buf[k]); p.wpk = w + o.d_w[k]; p.bias = w + o.d_b[k]; p.partial = part;

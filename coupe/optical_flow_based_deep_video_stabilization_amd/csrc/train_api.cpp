@@ -1,5 +1,5 @@
 // C ABI of the training-side building blocks: convolution weight / bias gradients.
-// The loss entry point lives in api.cpp next to the other small wrappers.
+// The loss entry points live in api.cpp next to the other small wrappers.
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -10,6 +10,7 @@
 
 #include "../../../include/vstab.h"
 #include "api_internal.h"
+#include "conv_desc.h"
 #include "vstab_internal.h"
 
 using namespace vstab;
@@ -197,9 +198,8 @@ bool dgrad_plan(int B, int Ho, int Wo, int cs_g, int cout, int k, int stride, in
     } else if (k & 1) {
         // one launch per output-parity phase, each with exactly its taps: row taps ky = t0y + 2u (u < nty), input row j + c - u
         if (cs_g & 3) return false;
-        const int BN = cin >= 128 ? 128 : (cin > 32 ? 64 : 32);
-        const ConvTile base = cin >= 128 ? TILE_128x128 : (cin > 32 ? TILE_128x64 : TILE_128x32);
-        const int npad = (cin + BN - 1) / BN * BN;
+        const ConvTile base = default_tile(cin);
+        const int BN = tile_cols(base), npad = padded_cols(cin, base);
         d.vec4 = true;
         d.packed_floats = 0;
         for (int py = 0; py < 2; ++py)
@@ -209,19 +209,11 @@ bool dgrad_plan(int B, int Ho, int Wo, int cs_g, int cout, int k, int stride, in
                 const int Hg = (Hi - py + 1) / 2, Wg = (Wi - px + 1) / 2;
                 if (Hg < 1 || Wg < 1 || nty < 1 || ntx < 1) continue;
                 ConvParams &q = d.sp[d.nsub];
-                std::memset(&q, 0, sizeof q);
-                q.B = B; q.Hi = Ho; q.Wi = Wo; q.Cs_in = cs_g;
-                const KLayout L = cs_g == cout ? klayout_run(nty, ntx, cs_g) : klayout_tap(nty, ntx, cout, cs_g);
-                set_layout(q, L);
+                q = conv_desc_phase(B, Ho, Wo, cout, cs_g, nty, ntx, 1,
+                                    ConvGrid{Hg, Wg, (py + pad - t0y) / 2 - nty + 1, (px + pad - t0x) / 2 - ntx + 1, 2, py, px}, Hi, Wi, cin, npad,
+                                    cs_x, cx_off, act);
                 if (q.SEG & 3) return false;
-                q.s_in = 1; q.s_out = 2; q.Ho = Hi; q.Wo = Wi; q.Cs_out = cs_x; q.c_off = cx_off;
-                q.N = cin; q.Npad = npad; q.act = act; q.nphase = 1;
-                ConvPhase &ph = q.ph[0];
-                ph.Hg = Hg; ph.Wg = Wg; ph.M = B * Hg * Wg;
-                ph.off_y = (py + pad - t0y) / 2 - nty + 1; ph.off_x = (px + pad - t0x) / 2 - ntx + 1;
-                ph.o_y = py; ph.o_x = px; ph.w_off = 0;
-                q.Mmax = ph.M;
-                set_ranges(q);
+                const KLayout L{q.KH, q.NSEG, q.SEG, q.SEGP, q.SEG_STRIDE};
                 d.stile[d.nsub] = choose_tile_split(q, base, true);
                 d.soff[d.nsub] = d.packed_floats;
                 const size_t pf = (size_t)L.ktiles() * npad * 32;
@@ -273,33 +265,14 @@ bool dgrad_plan(int B, int Ho, int Wo, int cs_g, int cout, int k, int stride, in
             d.tile = d.stile[0];
         }
     } else {
-        const int kt2 = (k + 1) / 2;
-        std::memset(&p, 0, sizeof p);
-        p.B = B; p.Hi = Ho; p.Wi = Wo; p.Cs_in = cs_g;
-        const KLayout L = cs_g == cout ? klayout_run(kt2, kt2, cs_g) : klayout_tap(kt2, kt2, cout, cs_g);
-        set_layout(p, L);
-        p.s_in = 1; p.s_out = 2; p.Ho = Hi; p.Wo = Wi; p.Cs_out = cs_x; p.c_off = cx_off;
-        p.N = cin;
-        const int BN = cin >= 128 ? 128 : (cin > 32 ? 64 : 32);
-        d.tile = cin >= 128 ? TILE_128x128 : (cin > 32 ? TILE_128x64 : TILE_128x32);
-        p.Npad = (cin + BN - 1) / BN * BN;
-        p.act = act; p.nphase = 4;
+        // four output-parity phases of ceil(k/2)^2 taps; parity b's first tap is input row j + (b + pad) / 2 - kt2 + 1
+        const int kt2 = (k + 1) / 2, off[2] = {pad / 2 - kt2 + 1, (1 + pad) / 2 - kt2 + 1};
+        d.tile = default_tile(cin);
+        p = conv_desc_parity4(B, Ho, Wo, cout, cs_g, kt2, off, Hi, Wi, cin, padded_cols(cin), cs_x, cx_off, act);
+        const KLayout L{p.KH, p.NSEG, p.SEG, p.SEGP, p.SEG_STRIDE};
         const size_t phase_floats = (size_t)L.ktiles() * p.Npad * 32;
-        p.Mmax = 0;
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px) {
-                ConvPhase &ph = p.ph[py * 2 + px];
-                const int t0y = (py + pad) & 1, t0x = (px + pad) & 1;
-                ph.Hg = (Hi - py + 1) / 2; ph.Wg = (Wi - px + 1) / 2;
-                ph.M = B * ph.Hg * ph.Wg;
-                ph.off_y = (py + pad - t0y) / 2 - kt2 + 1; ph.off_x = (px + pad - t0x) / 2 - kt2 + 1;
-                ph.o_y = py; ph.o_x = px;
-                ph.w_off = (long long)(py * 2 + px) * phase_floats;
-                p.Mmax = std::max(p.Mmax, ph.M);
-            }
         d.vec4 = true;
         if ((cs_g & 3) || (p.SEG & 3)) return false;
-        set_ranges(p);
         d.tile = choose_tile_split(p, d.tile, true);
         d.packed_floats = 4 * phase_floats;
         tbl.resize(d.packed_floats);
@@ -454,8 +427,7 @@ bool fwd_plan(int B, int Hi, int Wi, int cs_x, int cin, int k, int stride, int p
         if ((long long)B * Ho * Wo * cs_y * 4 >= 0x80000000LL) return false;
         d.p.Ho = Ho; d.p.Wo = Wo;
         d.p.ph[0].Hg = Ho; d.p.ph[0].Wg = Wo; d.p.ph[0].M = B * Ho * Wo; d.p.Mmax = d.p.ph[0].M;
-        const ConvTile base = cout >= 128 ? TILE_128x128 : (cout > 32 ? TILE_128x64 : TILE_128x32);
-        d.tile = choose_tile_split(d.p, base, d.vec4);
+        d.tile = choose_tile_split(d.p, default_tile(cout), d.vec4);
     }
     const KLayout L{d.p.KH, d.p.NSEG, d.p.SEG, d.p.SEGP, d.p.SEG_STRIDE};
     d.packed_floats = (size_t)L.ktiles() * d.p.Npad * 32;
@@ -556,7 +528,7 @@ bool rowwin_plan(int B, int H, int W, int Cin, int cs_w, int cout, int k, int st
     r.in = reinterpret_cast<const float *>(16);       // (rowwin_applicable tests the alignment of the real pointer at launch time)
     if (!rowwin_applicable(r)) return false;
     const int rem = Wo % 128;
-    if (r.MB == 2 && Wo > 128 && rem >= 1 && rem <= 64) {      // 128 k + (1..64) columns: k full tiles, then ONE 64-pixel tile (api.cpp's rule)
+    if (r.MB == 2 && Wo > 128 && rem >= 1 && rem <= 64) {      // 128 k + (1..64) columns: k full tiles, then ONE 64-pixel tile (flownet_forward.cpp's rule)
         RowWinParams t = r;
         t.MB = 1; t.ox_base = (Wo / 128) * 128; t.ntile_x = 1;
         t.WLEN = round_up(t.s_in * Cin * 63 + t.w_a + t.SEGP, 4);
@@ -722,28 +694,12 @@ bool wino_plan(int B, int H, int W, int K, int N, WinoPlan &out)
     WinoPlan d{};
     d.K = K; d.N = N; d.TH = (H + 1) / 2; d.TW = (W + 1) / 2;
     if ((long long)B * 16 * d.TH * d.TW * std::max(K, N) * 4 >= 0x80000000LL) return false;
-    ConvParams &p = d.p;
-    std::memset(&p, 0, sizeof p);
-    p.B = B; p.Hi = 16 * d.TH; p.Wi = d.TW; p.Cs_in = K;
-    const KLayout L = klayout_run(1, 1, K);
-    set_layout(p, L);
-    p.s_in = 1; p.s_out = 1; p.Ho = 16 * d.TH; p.Wo = d.TW; p.Cs_out = N; p.c_off = 0;
-    p.N = N; p.Npad = N; p.act = 0; p.nphase = 16; p.ksplit = 1;
-    d.phase_floats = (size_t)L.ktiles() * p.Npad * 32;
-    for (int xi = 0; xi < 16; ++xi) {
-        ConvPhase &ph = p.ph[xi];
-        ph.Hg = d.TH; ph.Wg = d.TW; ph.M = B * d.TH * d.TW;
-        ph.off_y = xi * d.TH; ph.o_y = xi * d.TH;
-        ph.w_off = (long long)xi * d.phase_floats;
-    }
-    p.Mmax = B * d.TH * d.TW;
-    set_ranges(p);
+    d.p = conv_desc_wino_gemm(B, H, W, K, N);
+    d.phase_floats = (size_t)klayout_run(1, 1, K).ktiles() * N * 32;
     cache[key] = d;
     out = d;
     return true;
 }
-
-size_t a256(size_t n) { return (n + 255) / 256 * 256; }
 }  // namespace
 
 extern "C" size_t vstab_conv3x3_winograd_workspace_bytes(int B, int H, int W, int cin, int cout, int transpose)

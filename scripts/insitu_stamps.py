@@ -26,7 +26,7 @@ _lib.lib().vstab_debug_stamp_reset = L.vstab_debug_stamp_reset
 L.vstab_debug_stamp_reset()
 vs.flownetS_pyramid(feats, B)
 torch.cuda.synchronize()
-# launch order of conv_mfma launches in a forward (conv1 runs on the row-window kernel): see api.cpp forward_chunk
+# launch order of conv_mfma launches in a forward (conv1 runs on the row-window kernel): see flownet_forward.cpp forward_chunk
 # (conv3_1 / conv4_1's GEMMs run on wino_gemm_stream_kernel and predict_flow2's taps on tap_panel_kernel at B=8 512x512: no stamps in those)
 names = ["conv2", "conv3", "conv4", "conv5", "conv5_1 gemm", "conv6", "conv6_1 gemm",
          "pf6 taps", "deconv5", "pf5 taps", "deconv4", "pf4 taps", "deconv3", "pf3 taps", "deconv2"]
