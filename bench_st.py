@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """The spatial_transformer.py samplers at configs[2]'s size (B = 32, 720 x 1280 x 3): per variant the median time of one call
 over HIP events (>= 20 timed calls after warm-up), algorithmic bytes (12 read + 12 written per output pixel) and the fraction
-of 8 TB/s.  Prints one JSON line.  AffineTransformer with the bilinear sampler is the existing kernel, the yardstick."""
+of 8 TB/s.  Prints one JSON line.  AffineTransformer with the bilinear sampler is the existing kernel, the yardstick.
+--backward adds the gradients of the affine bilinear transformer at the same shape (rows "backward"): d img (four global atomics
+per pixel-channel), d theta, both together, and torch's own grid_sample backward (NCHW, bilinear, zeros, align_corners=True) for scale -- an independent implementation of a comparable op,
+not a gate."""
 import argparse
 import json
 import os
@@ -29,6 +32,49 @@ def time_call(fn, iters, warmup):
     return statistics.median(a.elapsed_time(b) for a, b in ev) * 1e3
 
 
+def time_interleaved(fns, iters, warmup):
+    """median us of each call, the calls taking turns (A B A B ...) so that clock and cache state are shared"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for k in fns}
+    for i in range(iters):
+        for k, fn in fns.items():
+            a, b = ev[k][i]
+            a.record()
+            fn()
+            b.record()
+    torch.cuda.synchronize()
+    return {k: statistics.median(a.elapsed_time(b) for a, b in v) * 1e3 for k, v in ev.items()}
+
+
+def backward_rows(img, th6, out_size, iters, warmup):
+    """d img reads dout (12 B / pixel) and adds into an image it first zero-fills (12 B written by the fill + 12 B added per source
+    pixel): 36 B per pixel at equal sizes; d theta reads dout and the image: 24 B; both: 48 B."""
+    from coupe.optical_flow_based_deep_video_stabilization_amd import training
+    import torch.nn.functional as F
+    B, H, W, _ = img.shape
+    npix = B * out_size[0] * out_size[1]
+    dout = torch.rand(B, out_size[0], out_size[1], 3, generator=torch.Generator().manual_seed(2)).cuda()
+
+    def run(need_img, need_theta):
+        return lambda: training.st_transform_backward(img, th6, dout, out_size, need_img=need_img, need_theta=need_theta)
+
+    fns = {"d_img": run(True, False), "d_theta": run(False, True), "both": run(True, True)}
+    # yardstick: grid_sample's backward for both inputs
+    x = img.permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    grid = F.affine_grid(th6.reshape(B, 2, 3), (B, 3, out_size[0], out_size[1]), align_corners=True).requires_grad_(True)
+    gout = dout.permute(0, 3, 1, 2).contiguous()
+    y = F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=True)
+    fns["torch_grid_sample_backward"] = lambda: torch.autograd.grad(y, (x, grid), gout, retain_graph=True)
+    us = time_interleaved(fns, iters, warmup)
+    nbytes = {"d_img": 36.0, "d_theta": 24.0, "both": 48.0,
+              "torch_grid_sample_backward": 48.0 + 16.0}                      # + the grid read and its gradient written
+    return {k: {"us": round(v, 1), "alg_bytes": int(nbytes[k] * npix), "frac_8TBs": round(nbytes[k] * npix / (v * 1e-6) / 1e9 / PEAK_GBS, 3)}
+            for k, v in us.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -37,6 +83,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", default="", help="comma-separated variant names (default: all)")
+    ap.add_argument("--backward", action="store_true", help="add the affine bilinear transformer's gradients (rows 'backward')")
     args = ap.parse_args()
     if args.iters < 20:
         ap.error("--iters must be >= 20")
@@ -71,8 +118,11 @@ def main():
     if base:
         for r in rows.values():
             r["x_affine_bilinear"] = round(r["us"] / base, 3)
-    print(json.dumps({"bench": "spatial_transformer_samplers", "batch": B, "height": H, "width": W, "channels": 3,
-                      "iters": args.iters, "device": torch.cuda.get_device_name(0), "variants": rows}))
+    result = {"bench": "spatial_transformer_samplers", "batch": B, "height": H, "width": W, "channels": 3,
+              "iters": args.iters, "device": torch.cuda.get_device_name(0), "variants": rows}
+    if args.backward:
+        result["backward"] = backward_rows(img, th6, out_size, args.iters, args.warmup)
+    print(json.dumps(result))
 
 
 if __name__ == "__main__":

@@ -57,6 +57,11 @@ EXPORTS = {
     "vstab_host_tps_linv": (C.c_int, [C.c_int, c_float_p, C.c_int]),
     "vstab_st_elastic_transform": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                                          C.c_void_p]),
+    "vstab_st_transform_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "vstab_st_transform_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_st_bilinear_interp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_transform_image": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p]),
     "vstab_vec2mtrx": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_vgg16_load": (C.c_int, [C.c_void_p, C.POINTER(VstabTensor), C.c_int]),

@@ -371,6 +371,43 @@ extern "C" int vstab_st_elastic_transform(const float *img, int B, int H, int W,
     return VSTAB_OK;
 }
 
+// ---- backward of the bilinear sampler (sampler_ops.hip): d img by float atomics, d theta by a reproducible two-stage sum
+extern "C" size_t vstab_st_transform_backward_workspace_bytes(int B, int H, int W, int C, int oh, int ow)
+{
+    if (!stx_shape_ok(B, H, W, C, oh, ow)) return 0;
+    return st_transform_backward_ws_bytes(B, H, W, C, oh, ow);
+}
+
+extern "C" int vstab_st_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim, const float *dout,
+                                           int oh, int ow, float *d_img, int accumulate, float *d_theta, void *workspace,
+                                           size_t workspace_bytes, void *stream)
+{
+    if (!img || !theta || !dout) return fail(nullptr, VSTAB_E_STATE, "st_transform_backward: NULL buffer");
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL || (theta_dim != 6 && theta_dim != 8))
+        return fail(nullptr, VSTAB_E_SHAPE, "st_transform_backward: bad shape (theta must be [B,6] or [B,8], B <= 65535)");
+    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "st_transform_backward: d_img and d_theta are both NULL");
+    if (d_theta) {
+        const size_t need = st_transform_backward_ws_bytes(B, H, W, C, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "st_transform_backward: workspace needs %zu bytes", need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "st_transform_backward: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(nullptr, launch_st_transform_backward(img, B, H, W, C, theta, theta_dim, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
+                                                  (double *)workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st_bilinear_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y,
+                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x, float *d_y,
+                                                 void *stream)
+{
+    if (!img || !x || !y || !dout) return fail(nullptr, VSTAB_E_STATE, "st_bilinear_interp_backward: NULL buffer");
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL)
+        return fail(nullptr, VSTAB_E_SHAPE, "st_bilinear_interp_backward: bad shape (B <= 65535)");
+    if (!d_img && !d_x && !d_y) return fail(nullptr, VSTAB_E_SHAPE, "st_bilinear_interp_backward: d_img, d_x and d_y are all NULL");
+    HIP_TRY(nullptr, launch_st_interp_backward(img, B, H, W, C, x, y, dout, oh, ow, d_img, accumulate ? 1 : 0, d_x, d_y, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
 extern "C" int vstab_vec2mtrx(const float *p, int B, int dim, int warp_approx, float *out, void *stream)
 {
     if (!p || !out) return fail(nullptr, VSTAB_E_STATE, "vec2mtrx: NULL buffer");

@@ -3,7 +3,9 @@
 // ONE family of kernels, templated on where a pixel's source coordinates come from (XS_*) and on the sampler (XI_*):
 // st3_tile_kernel for 3-channel frames (tile3.h's skeleton: 2-D tiles, 3-dword tap gathers, rows leaving as 16-byte stores),
 // st_pixel_kernel (one thread per pixel) for other channel counts.  Each piece of the reference's arithmetic is one device
-// function (st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.
+// function (st_axis, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta and
+// explicit-coordinate sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel, at the end of the file) that calls the same
+// functions; its d img is summed by float atomics and depends on their arrival order in its last bits, its d theta is reproducible.
 // -ffp-contract=off keeps the weight arithmetic the reference's op-by-op fp32 sequence.
 #include "vstab_internal.h"
 #include "hbm_profile.h"
@@ -79,30 +81,41 @@ struct StSrc {
 // counts: an invalid tap reads as zero) and the blend weights (ST: w00, w01, w10, w11; homography: xr, yr)
 struct Taps { int xa, xb, ya, yb; bool vxa, vxb, vya, vyb; float w0, w1, w2, w3; };
 
-// bilinear_interp (spatial_transformer.py:902-964): x = (x+1)/2*(W-1), clipped to [-1, W], shifted by the one-pixel zero pad;
-// x0 = floor, x1 = min(x0+1, W+1) as index but weights use the UNclipped x0+1
-__device__ __forceinline__ Taps st_taps(float xn, float yn, int H, int W)
+// One axis of bilinear_interp (spatial_transformer.py:902-964): v = (v+1)/2*(n-1), clipped to [-1, n], shifted by the one-pixel zero
+// pad; v0 = floor, v1 = min(v0+1, n+1) as index but the weights use the UNclipped v0+1.  lo = v - v0, hi = (v0+1) - v
+// (both exact in fp32); a, b the two image indices clamped into the image (what is addressed), va, vb whether they count (a tap on
+// the zero border reads as zero).  pass: the clip lets a gradient through, -1 <= v <= n inclusive, not for NaN (the backward's rule).
+struct Axis { float lo, hi; int a, b; bool va, vb, pass; };
+
+__device__ __forceinline__ Axis st_axis(float vn, int n)
 {
-    const float wf = (float)W, hf = (float)H;
-    float x = (xn + 1.0f) / 2.0f * (wf - 1.0f);
-    float y = (yn + 1.0f) / 2.0f * (hf - 1.0f);
-    x = fminf(fmaxf(x, -1.0f), wf - 1.0f + 1.0f);       // clip_by_value(x, -edge, W-1+edge); NaN -> -1
-    y = fminf(fmaxf(y, -1.0f), hf - 1.0f + 1.0f);
-    x += 1.0f;
-    y += 1.0f;
-    const float x0f = floorf(x), y0f = floorf(y);
-    const float x1f = x0f + 1.0f, y1f = y0f + 1.0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;              // in [0, W+1] after the clip
-    const int x1 = (int)fminf(x1f, wf - 1.0f + 2.0f), y1 = (int)fminf(y1f, hf - 1.0f + 2.0f);
+    const float nf = (float)n;
+    float v = (vn + 1.0f) / 2.0f * (nf - 1.0f);
+    Axis A;
+    A.pass = v >= -1.0f && v <= nf - 1.0f + 1.0f;
+    v = fminf(fmaxf(v, -1.0f), nf - 1.0f + 1.0f);       // clip_by_value(x, -edge, W-1+edge); NaN -> -1
+    v += 1.0f;
+    const float v0f = floorf(v), v1f = v0f + 1.0f;
+    const int v0 = (int)v0f;                             // in [0, n+1] after the clip
+    const int v1 = (int)fminf(v1f, nf - 1.0f + 2.0f);
+    A.lo = v - v0f; A.hi = v1f - v;
+    // padded index p in [0, n+1]: image index p-1, zero on the border
+    A.va = v0 >= 1 && v0 <= n; A.vb = v1 >= 1 && v1 <= n;
+    A.a = min(max(v0 - 1, 0), n - 1); A.b = min(max(v1 - 1, 0), n - 1);
+    return A;
+}
+
+__device__ __forceinline__ Taps st_taps(const Axis &X, const Axis &Y)
+{
     Taps t;
-    t.w0 = (x1f - x) * (y1f - y); t.w1 = (x - x0f) * (y1f - y);
-    t.w2 = (x1f - x) * (y - y0f); t.w3 = (x - x0f) * (y - y0f);
-    // padded index p in [0, W+1]: image column p-1, zero on the border
-    t.vxa = x0 >= 1 && x0 <= W; t.vxb = x1 >= 1 && x1 <= W; t.vya = y0 >= 1 && y0 <= H; t.vyb = y1 >= 1 && y1 <= H;
-    t.xa = min(max(x0 - 1, 0), W - 1); t.xb = min(max(x1 - 1, 0), W - 1);
-    t.ya = min(max(y0 - 1, 0), H - 1); t.yb = min(max(y1 - 1, 0), H - 1);
+    t.w0 = X.hi * Y.hi; t.w1 = X.lo * Y.hi;
+    t.w2 = X.hi * Y.lo; t.w3 = X.lo * Y.lo;
+    t.vxa = X.va; t.vxb = X.vb; t.vya = Y.va; t.vyb = Y.vb;
+    t.xa = X.a; t.xb = X.b; t.ya = Y.a; t.yb = Y.b;
     return t;
 }
+
+__device__ __forceinline__ Taps st_taps(float xn, float yn, int H, int W) { return st_taps(st_axis(xn, W), st_axis(yn, H)); }
 
 __device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, int oy, double dsx, double dsy, int Hi, int Wi)
 {
@@ -226,6 +239,24 @@ __device__ __forceinline__ void st_tps_coeff(const StSrc &S, int n, float *cf)
     }
 }
 
+// point i of the linspace(-1, 1) sampling grid whose step is `step` (StSrc::sx, sy)
+__device__ __forceinline__ float st_grid_t(int i, float step) { return -1.0f + (float)i * step; }
+
+// Affine / ProjectiveTransformer at grid point (xt, yt): T_g = theta . (x_t, y_t, 1), the projective one divided by safe_z (ST:598).
+// xh, yh, zs (1 for the affine one) are the values before the division, which the backward's chain rule needs.
+__device__ __forceinline__ void st_theta_coords(const float *th, int tdim, float xt, float yt, float &xh, float &yh, float &zs, float &xs, float &ys)
+{
+    xh = (th[0] * xt + th[1] * yt) + th[2];
+    yh = (th[3] * xt + th[4] * yt) + th[5];
+    zs = 1.0f; xs = xh; ys = yh;
+    if (tdim == 8) {
+        zs = (th[6] * xt + th[7] * yt) + 1.0f;
+        if (zs == 0.0f) zs = zs + 1e-8f;
+        xs = xh / zs;
+        ys = yh / zs;
+    }
+}
+
 // normalised source coordinates of grid point (gx, gy) of sample n
 template <int SRC>
 __device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const float *cf, int n, int gx, int gy, float &xs, float &ys)
@@ -235,7 +266,7 @@ __device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const
         xs = S.x[i]; ys = S.y[i];
         return;
     }
-    const float xt = -1.0f + (float)gx * S.sx, yt = -1.0f + (float)gy * S.sy;
+    const float xt = st_grid_t(gx, S.sx), yt = st_grid_t(gy, S.sy);
     if (SRC == XS_TPS) {
         const int K = S.g * S.g, K3 = K + 3;
         float ax = (cf[0] * xt + cf[1] * yt) + cf[2];
@@ -251,14 +282,14 @@ __device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const
         xs = ax; ys = ay;
         return;
     }
+    if (SRC == XS_THETA) {
+        float xh, yh, zs;
+        st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
+        return;
+    }
     xs = (th[0] * xt + th[1] * yt) + th[2];
     ys = (th[3] * xt + th[4] * yt) + th[5];
-    if (SRC == XS_THETA && S.tdim == 8) {                // ProjectiveTransformer: safe_z (ST:598)
-        float zs = (th[6] * xt + th[7] * yt) + 1.0f;
-        if (zs == 0.0f) zs = zs + 1e-8f;
-        xs = xs / zs;
-        ys = ys / zs;
-    } else if (SRC == XS_SYM && S.kind == 1) {           // ProjectiveSymmetryTransformer divides by z as is (ST:710-711)
+    if (SRC == XS_SYM && S.kind == 1) {           // ProjectiveSymmetryTransformer divides by z as is (ST:710-711)
         const float zs = (th[6] * xt + th[7] * yt) + th[8];
         xs = xs / zs;
         ys = ys / zs;
@@ -605,6 +636,269 @@ hipError_t launch_st_elastic_transform(const float *img, int B, int H, int W, in
     S.theta = theta; S.g = g; S.linv_t = linv_t;
     if (interp == XI_BILINEAR) return launch_st<XS_TPS, XI_BILINEAR>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
     return launch_st<XS_TPS, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
+}
+
+// ---------------------------------------------------------------------------------
+// Backward of the BILINEAR sampler for the theta (affine / projective) and explicit-coordinate sources: what TensorFlow's autodiff
+// gives for ST:902-964 and ST:438-452 / 578-608.  The coordinates, taps and weights are the forward's (st_theta_coords, st_axis,
+// st_taps), so the backward's tap decisions are the forward's.
+//   d img    the adjoint of the gather, w_k * dout added to the four taps (none to a tap on the zero border), by float atomics:
+//            the result DEPENDS ON ATOMIC ARRIVAL ORDER IN ITS LAST BITS.  Four global atomics per pixel-channel, for any channel
+//            count and any theta.  A form that sums a tile's contributions in an LDS window first is NOT built.
+//   d x, d y per pixel: floor and the int casts have zero derivative, so per channel d out / d x = (I01 - I00) (y1f - y) +
+//            (I11 - I10) (y - y0f) in padded-pixel units (st_slope), summed over the channels times dout, passed by the clip where
+//            -1 <= x <= W inclusive (0 for NaN), times (W - 1) / 2.  Stored for explicit coordinates.
+//   d theta  the per-pixel products (gx x_t, gx y_t, gx, gy x_t, gy y_t, gy; the projective chain through x_h / safe_z in double
+//            from the forward's fp32 x_h, y_h, safe_z) summed over the pixels in double: per thread, per wave (shuffles), per
+//            workgroup (LDS) into part[workgroup][8], then st_theta_final_kernel in a fixed order -- bit-reproducible, no atomics.
+// ---------------------------------------------------------------------------------
+// one channel's share of d out / d (x, y), in padded-pixel units, times its dout
+__device__ __forceinline__ void st_slope(const Axis &X, const Axis &Y, float I00, float I01, float I10, float I11, float g, float &gx, float &gy)
+{
+    gx = gx + ((I01 - I00) * Y.hi + (I11 - I10) * Y.lo) * g;
+    gy = gy + ((I10 - I00) * X.hi + (I11 - I01) * X.lo) * g;
+}
+
+// the clip's gradient rule and the chain through (v + 1) / 2 * (n - 1)
+__device__ __forceinline__ float st_axis_chain(const Axis &A, float g, int n) { return A.pass ? g * (((float)n - 1.0f) / 2.0f) : 0.0f; }
+
+// a pixel's share of d theta, added to acc[8] in double: d x_h = gx / z, d y_h = gy / z, d z = -(gx x_h + gy y_h) / z^2
+__device__ __forceinline__ void st_theta_accum(double *acc, int tdim, float gxn, float gyn, float xt, float yt, float xh, float yh, float zs)
+{
+    if (gxn == 0.0f && gyn == 0.0f) return;
+    double gx = (double)gxn, gy = (double)gyn;
+    if (tdim == 8) {
+        const double iz = 1.0 / (double)zs;
+        const double gz = -(gx * (double)xh + gy * (double)yh) * iz * iz;
+        gx *= iz; gy *= iz;
+        acc[6] += gz * (double)xt; acc[7] += gz * (double)yt;
+    }
+    acc[0] += gx * (double)xt; acc[1] += gx * (double)yt; acc[2] += gx;
+    acc[3] += gy * (double)xt; acc[4] += gy * (double)yt; acc[5] += gy;
+}
+
+// acc[8] of every thread of a 256-thread workgroup -> part[8]: xor-shuffles inside a wave, the four waves added in wave order
+__device__ __forceinline__ void st_theta_reduce(double *acc, double (*red)[8], double *__restrict__ part)
+{
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) red[wave][k] = acc[k];
+    __syncthreads();
+    if (threadIdx.x < 8) part[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// d theta[n, k] = sum of sample n's `wgs` partials: thread t adds partials t, t + 256, ..., then st_theta_reduce's order
+__global__ __launch_bounds__(256) void st_theta_final_kernel(const double *__restrict__ part, int wgs, int tdim, float *__restrict__ d_theta)
+{
+    __shared__ double red[4][8], tot[8];
+    const int n = blockIdx.x;
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = threadIdx.x; i < wgs; i += 256)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += part[((long long)n * wgs + i) * 8 + k];
+    st_theta_reduce(acc, red, tot);
+    __syncthreads();
+    if ((int)threadIdx.x < tdim) d_theta[(long long)n * tdim + threadIdx.x] = (float)tot[threadIdx.x];
+}
+
+struct StBwd {
+    const float *dout;             // [B, FH, FW, C]
+    float *d_img;                  // [B, H, W, C], added to (null: not wanted)
+    float *d_x, *d_y;              // XS_COORDS [B*FH*FW] (each nullable)
+    double *part;                  // XS_THETA [workgroups][8] (null: d theta not wanted)
+};
+
+// any channel count, one thread per pixel (st_pixel_kernel's layout); d img the plain way
+template <int SRC, bool DIMG, bool DCOORD>
+__global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restrict__ img, int H, int W, int C, StSrc S, StBwd G, int FH, int FW, unsigned bps)
+{
+    __shared__ double red[4][8];
+    const int n = (int)(blockIdx.x / bps);
+    float th[9];
+    st_matrix_wg<SRC>(S, n, th, nullptr);
+    const long long p = (long long)(blockIdx.x - (unsigned)n * bps) * 256 + threadIdx.x;
+    const bool ok = p < (long long)FH * FW;
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ok) {
+        const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+        float xs, ys, xh = 0.f, yh = 0.f, zs = 1.f;
+        const float xt = st_grid_t(fx, S.sx), yt = st_grid_t(fy, S.sy);
+        if (SRC == XS_THETA) st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
+        else st_coords<SRC>(S, th, nullptr, n, fx, fy, xs, ys);
+        const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
+        const Taps t = st_taps(X, Y);
+        const long long i00 = ((long long)t.ya * W + t.xa) * C, i01 = ((long long)t.ya * W + t.xb) * C;
+        const long long i10 = ((long long)t.yb * W + t.xa) * C, i11 = ((long long)t.yb * W + t.xb) * C;
+        const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+        const float *__restrict__ b = img + (long long)n * H * W * C;
+        const float *__restrict__ g = G.dout + ((long long)n * FH * FW + p) * C;
+        float *di = DIMG ? G.d_img + (long long)n * H * W * C : nullptr;
+        float gx = 0.f, gy = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float gc = g[c];
+            if (DCOORD) st_slope(X, Y, v00 ? b[i00 + c] : 0.f, v01 ? b[i01 + c] : 0.f, v10 ? b[i10 + c] : 0.f, v11 ? b[i11 + c] : 0.f, gc, gx, gy);
+            if (DIMG) {
+                if (v00) atomicAdd(di + i00 + c, t.w0 * gc);
+                if (v01) atomicAdd(di + i01 + c, t.w1 * gc);
+                if (v10) atomicAdd(di + i10 + c, t.w2 * gc);
+                if (v11) atomicAdd(di + i11 + c, t.w3 * gc);
+            }
+        }
+        if (DCOORD) {
+            const float gxn = st_axis_chain(X, gx, W), gyn = st_axis_chain(Y, gy, H);
+            if (SRC == XS_COORDS) {
+                if (G.d_x) G.d_x[(long long)n * FH * FW + p] = gxn;
+                if (G.d_y) G.d_y[(long long)n * FH * FW + p] = gyn;
+            } else {
+                st_theta_accum(acc, S.tdim, gxn, gyn, xt, yt, xh, yh, zs);
+            }
+        }
+    }
+    if (DCOORD && SRC == XS_THETA) st_theta_reduce(acc, red, G.part + (long long)blockIdx.x * 8);
+}
+
+// 3-channel frames on the tile skeleton (st3_tile_kernel's pixels: a wave instruction works on a 4 x 16 patch)
+template <int SRC, bool DIMG, bool DCOORD>
+__global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restrict__ img, int H, int W, StSrc S, StBwd G, int FH, int FW,
+                                                           int tiles_x, int tiles_y)
+{
+    constexpr int PPT = StTile::PPT;
+    __shared__ double red[4][8];
+    const StTile tile(tiles_x, tiles_y);
+    const int n = tile.n;
+    float th[9];
+    st_matrix_wg<SRC>(S, n, th, nullptr);
+    const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + (long long)n * H * W;     // 3 B H W < 2^31 (host)
+    float *di = DIMG ? G.d_img + (long long)n * H * W * 3 : nullptr;
+    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        if (!(tile.y(j) < FH && tile.x(j) < FW)) continue;
+        const int fy = tile.y(j), fx = tile.x(j);
+        float xs, ys, xh = 0.f, yh = 0.f, zs = 1.f;
+        const float xt = st_grid_t(fx, S.sx), yt = st_grid_t(fy, S.sy);
+        if (SRC == XS_THETA) st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
+        else st_coords<SRC>(S, th, nullptr, n, fx, fy, xs, ys);
+        const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
+        const Taps t = st_taps(X, Y);
+        const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+        const long long po = ((long long)n * FH + fy) * FW + fx;
+        const rgb3 g = reinterpret_cast<const rgb3 *>(G.dout)[po];
+        if (DCOORD) {
+            const rgb3 z = {0.f, 0.f, 0.f};
+            const rgb3 I00 = v00 ? b[t.ya * W + t.xa] : z, I01 = v01 ? b[t.ya * W + t.xb] : z;
+            const rgb3 I10 = v10 ? b[t.yb * W + t.xa] : z, I11 = v11 ? b[t.yb * W + t.xb] : z;
+            float gx = 0.f, gy = 0.f;
+            st_slope(X, Y, I00.r, I01.r, I10.r, I11.r, g.r, gx, gy);
+            st_slope(X, Y, I00.g, I01.g, I10.g, I11.g, g.g, gx, gy);
+            st_slope(X, Y, I00.b, I01.b, I10.b, I11.b, g.b, gx, gy);
+            const float gxn = st_axis_chain(X, gx, W), gyn = st_axis_chain(Y, gy, H);
+            if (SRC == XS_COORDS) {
+                if (G.d_x) G.d_x[po] = gxn;
+                if (G.d_y) G.d_y[po] = gyn;
+            } else {
+                st_theta_accum(acc, S.tdim, gxn, gyn, xt, yt, xh, yh, zs);
+            }
+        }
+        if (DIMG) {
+            auto add = [&](int y, int x, bool valid, float w) {
+                if (!valid) return;
+                float *q = di + ((long long)y * W + x) * 3;
+                atomicAdd(q, w * g.r); atomicAdd(q + 1, w * g.g); atomicAdd(q + 2, w * g.b);
+            };
+            add(t.ya, t.xa, v00, t.w0); add(t.ya, t.xb, v01, t.w1); add(t.yb, t.xa, v10, t.w2); add(t.yb, t.xb, v11, t.w3);
+        }
+    }
+    if (DCOORD && SRC == XS_THETA) {
+        const int tidx = (tile.ty0 / StTile::TH) * tiles_x + tile.tx0 / StTile::TW;
+        st_theta_reduce(acc, red, G.part + ((long long)n * tiles_x * tiles_y + tidx) * 8);
+    }
+}
+
+// workgroups per sample of the backward launch of this shape (the d theta partials are [B * workgroups][8] doubles), and whether it
+// is the tile kernel's
+static bool st_bwd_plan(int B, int H, int W, int C, int FH, int FW, int &tx, int &ty, dim3 &grid, long long &wgs)
+{
+    if (C == 3 && StTile::plan(B, FH, FW, 3 * std::max((long long)B * H * W, (long long)B * FH * FW), tx, ty, grid)) {
+        wgs = (long long)tx * ty;
+        return true;
+    }
+    wgs = ((long long)FH * FW + 255) / 256;
+    return false;
+}
+
+size_t st_transform_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow)
+{
+    int tx, ty;
+    dim3 grid;
+    long long wgs;
+    st_bwd_plan(B, H, W, C, oh, ow, tx, ty, grid, wgs);
+    return (size_t)wgs * B * 8 * sizeof(double);
+}
+
+template <int SRC>
+static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, StSrc S, StBwd G, int FH, int FW, hipStream_t stream)
+{
+    S.B = B;
+    S.sx = S.gw > 1 ? 2.0f / (float)(S.gw - 1) : 0.0f; S.sy = S.gh > 1 ? 2.0f / (float)(S.gh - 1) : 0.0f;
+    const bool dimg = G.d_img != nullptr, dcoord = SRC == XS_THETA ? G.part != nullptr : (G.d_x || G.d_y);
+    int tx, ty;
+    dim3 grid;
+    long long wgs;
+    if (st_bwd_plan(B, H, W, C, FH, FW, tx, ty, grid, wgs)) {
+#define ST_BWD_TILE(D, K) st3_tile_bwd_kernel<SRC, D, K><<<grid, dim3(256), 0, stream>>>(img, H, W, S, G, FH, FW, tx, ty)
+        if (dimg && dcoord) ST_BWD_TILE(true, true);
+        else if (dimg) ST_BWD_TILE(true, false);
+        else ST_BWD_TILE(false, true);
+#undef ST_BWD_TILE
+        return hipGetLastError();
+    }
+    if (wgs * B >= (1ll << 31)) return hipErrorInvalidValue;
+    const dim3 pgrid((unsigned)(wgs * B));
+#define ST_BWD_PIXEL(D, K) st_pixel_bwd_kernel<SRC, D, K><<<pgrid, dim3(256), 0, stream>>>(img, H, W, C, S, G, FH, FW, (unsigned)wgs)
+    if (dimg && dcoord) ST_BWD_PIXEL(true, true);
+    else if (dimg) ST_BWD_PIXEL(true, false);
+    else ST_BWD_PIXEL(false, true);
+#undef ST_BWD_PIXEL
+    return hipGetLastError();
+}
+
+hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int tdim, const float *dout, int oh,
+                                        int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream)
+{
+    if (d_img && !accumulate) {
+        const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
+        if (e != hipSuccess) return e;
+    }
+    StSrc S = st_plain(oh, ow);
+    S.theta = theta; S.tdim = tdim;
+    StBwd G{dout, d_img, nullptr, nullptr, d_theta ? part : nullptr};
+    const hipError_t e = launch_st_bwd<XS_THETA>(img, B, H, W, C, S, G, oh, ow, stream);
+    if (e != hipSuccess || !d_theta) return e;
+    int tx, ty;
+    dim3 grid;
+    long long wgs;
+    st_bwd_plan(B, H, W, C, oh, ow, tx, ty, grid, wgs);
+    st_theta_final_kernel<<<dim3((unsigned)B), dim3(256), 0, stream>>>(part, (int)wgs, tdim, d_theta);
+    return hipGetLastError();
+}
+
+hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y, const float *dout, int oh,
+                                     int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream)
+{
+    if (d_img && !accumulate) {
+        const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
+        if (e != hipSuccess) return e;
+    }
+    StSrc S = st_plain(oh, ow);
+    S.x = x; S.y = y;
+    StBwd G{dout, d_img, d_x, d_y, nullptr};
+    return launch_st_bwd<XS_COORDS>(img, B, H, W, C, S, G, oh, ow, stream);
 }
 
 }  // namespace vstab

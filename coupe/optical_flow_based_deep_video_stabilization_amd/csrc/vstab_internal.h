@@ -395,6 +395,13 @@ hipError_t launch_st_symmetry_transform(const float *img, int B, int H, int W, i
                                         float *out, int oh, int ow, hipStream_t stream);
 hipError_t launch_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                        int interp, float *out, int oh, int ow, hipStream_t stream);
+// backward of launch_st_transform / launch_st_interp (bilinear sampler).  d_img (nullable) is zero-filled on `stream` first unless
+// `accumulate`; `part`: st_transform_backward_ws_bytes of scratch for the d theta partials
+size_t st_transform_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow);
+hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int tdim, const float *dout, int oh,
+                                        int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream);
+hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y, const float *dout, int oh,
+                                     int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream);
 
 // clip driver helpers (clip_ops.hip)
 hipError_t launch_resize_u8(const unsigned char *src, int B, int sh, int sw, unsigned char *dst, int dh, int dw, hipStream_t stream);

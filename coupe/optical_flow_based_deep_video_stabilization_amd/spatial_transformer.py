@@ -4,13 +4,20 @@
 (:611-716), `_meshgrid` (:755-779), `_repeat` (:782-785), `_interpolate` (:787-792), `bilinear_interp` (:902-964)
 and `bicubic_interp` (:966-1072).  None of them is executed by the reference's runnable scripts (they are only
 imported, main:4 and cell.py:2); the arithmetic runs in HIP kernels (csrc/sampler_ops.hip).  The 3-D classes
-(`AffineVolumeTransformer`, `bilinear_interp3d`, `_meshgrid3d`, `_interpolate3d`) are not provided."""
+(`AffineVolumeTransformer`, `bilinear_interp3d`, `_meshgrid3d`, `_interpolate3d`) are not provided.
+
+Differentiable (torch.autograd, HIP backward kernels): `AffineTransformer.transform`, `ProjectiveTransformer.transform` and
+`transformer()` with the bilinear sampler, with respect to the image and `theta`, and `bilinear_interp` with respect to the image,
+`x` and `y`.  The gradient of the image is summed by float atomics (last bits may differ between runs); those of `theta`, `x`, `y`
+are bit-reproducible.  NOT differentiable -- the result has no `grad_fn`, whatever requires grad: `bicubic_interp` and
+`interp_method='bicubic'`, the symmetric-pad transformers, `ElasticTransformer`."""
 from __future__ import annotations
 
 import ctypes
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
 
@@ -39,9 +46,42 @@ def _repeat(x, n_repeats):
     return x.reshape(-1, 1).repeat(1, int(n_repeats)).reshape(-1)
 
 
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def _bilinear_interp_call(im, x, y, oh, ow):
+    B, H, W, Cc = im.shape
+    out = torch.empty((B * oh * ow, Cc), dtype=torch.float32, device=im.device)
+    with torch.cuda.device(im.device):
+        _lib.check(_lib.lib().vstab_st_bilinear_interp(im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow,
+                                                       out.data_ptr(), runtime.stream_ptr()))
+    return out
+
+
+class _BilinearInterpFn(torch.autograd.Function):
+    """bilinear_interp with its HIP backward (training.st_bilinear_interp_backward)."""
+
+    @staticmethod
+    def forward(ctx, im, x, y, oh, ow):
+        ctx.save_for_backward(im, x, y)
+        ctx.out_size = (oh, ow)
+        return _bilinear_interp_call(im, x, y, oh, ow)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        im, x, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_im, d_x, d_y = training.st_bilinear_interp_backward(im, x, y, dout, ctx.out_size, need_img=need[0], need_x=need[1], need_y=need[2])
+        return d_im, d_x, d_y, None, None
+
+
 def bilinear_interp(im, x, y, out_size):
     """im [B,H,W,C]; x, y flat [B*out_h*out_w] normalised to [-1,1] -> [B*out_h*out_w, C].
-    The image is zero-padded by one pixel; coordinates are clipped to [-1, W] / [-1, H]."""
+    The image is zero-padded by one pixel; coordinates are clipped to [-1, W] / [-1, H].
+    Differentiable with respect to im, x and y (module docstring)."""
     im = _f32_cuda(im, "im")
     B, H, W, Cc = im.shape
     x = _f32_cuda(x.to(torch.float32), "x").reshape(-1)
@@ -50,17 +90,15 @@ def bilinear_interp(im, x, y, out_size):
     npix = oh * ow
     if x.numel() != B * npix or y.numel() != B * npix:
         raise ValueError(f"x/y must have B*out_h*out_w = {B * npix} elements")
-    out = torch.empty((B * npix, Cc), dtype=torch.float32, device=im.device)
-    with torch.cuda.device(im.device):
-        _lib.check(_lib.lib().vstab_st_bilinear_interp(im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow,
-                                                       out.data_ptr(), runtime.stream_ptr()))
-    return out
+    if _wants_grad(im, x, y):
+        return _BilinearInterpFn.apply(im, x, y, oh, ow)
+    return _bilinear_interp_call(im, x, y, oh, ow)
 
 
 def bicubic_interp(im, x, y, out_size):
     """im [B,H,W,C]; x, y flat [B*out_h*out_w] normalised to [-1,1] -> [B*out_h*out_w, C].
     Coordinates are clipped to [-1, 1] before the scaling (NaN reads as -1); 4 x 4 taps, edges replicate
-    (no zero border), alpha = -0.75."""
+    (no zero border), alpha = -0.75.  Not differentiable."""
     im = _f32_cuda(im, "im")
     B, H, W, Cc = im.shape
     x = _f32_cuda(x.to(torch.float32), "x").reshape(-1)
@@ -90,6 +128,38 @@ def _interp_code(method):
     return _INTERP[method]
 
 
+def _theta_transform_call(inp, theta, param_dim, oh, ow, interp):
+    B, H, W, Cc = inp.shape
+    out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
+    with torch.cuda.device(inp.device):
+        if interp == 0:
+            _lib.check(_lib.lib().vstab_st_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), param_dim,
+                                                     out.data_ptr(), oh, ow, runtime.stream_ptr()))
+        else:
+            _lib.check(_lib.lib().vstab_st_transform_interp(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), param_dim,
+                                                            interp, out.data_ptr(), oh, ow, runtime.stream_ptr()))
+    return out
+
+
+class _ThetaTransformFn(torch.autograd.Function):
+    """Affine / ProjectiveTransformer.transform (bilinear) with its HIP backward (training.st_transform_backward); theta flat."""
+
+    @staticmethod
+    def forward(ctx, inp, theta, param_dim, oh, ow):
+        ctx.save_for_backward(inp, theta)
+        ctx.out_size = (oh, ow)
+        return _theta_transform_call(inp, theta, param_dim, oh, ow, 0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        inp, theta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_inp, d_theta = training.st_transform_backward(inp, theta, dout, ctx.out_size, need_img=need[0], need_theta=need[1])
+        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None
+
+
 class _ThetaTransformer(object):
     param_dim = 0
 
@@ -113,19 +183,14 @@ class _ThetaTransformer(object):
         if theta.numel() != B * self.param_dim:
             raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
         oh, ow = self.out_size
-        out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
-        with torch.cuda.device(inp.device):
-            if interp == 0:
-                _lib.check(_lib.lib().vstab_st_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.param_dim,
-                                                         out.data_ptr(), oh, ow, runtime.stream_ptr()))
-            else:
-                _lib.check(_lib.lib().vstab_st_transform_interp(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.param_dim,
-                                                                interp, out.data_ptr(), oh, ow, runtime.stream_ptr()))
-        return out
+        if interp == 0 and _wants_grad(inp, theta):          # bilinear only: the bicubic sampler has no backward
+            return _ThetaTransformFn.apply(inp, theta, self.param_dim, oh, ow)
+        return _theta_transform_call(inp, theta, self.param_dim, oh, ow, interp)
 
 
 class AffineTransformer(_ThetaTransformer):
-    """theta [B,6] = row-major 2x3 matrix acting on (x_t, y_t, 1), x_t, y_t in [-1,1]."""
+    """theta [B,6] = row-major 2x3 matrix acting on (x_t, y_t, 1), x_t, y_t in [-1,1].  With the bilinear sampler `transform` is
+    differentiable with respect to the image and theta."""
     param_dim = 6
 
     def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', **kwargs):
@@ -134,7 +199,8 @@ class AffineTransformer(_ThetaTransformer):
 
 class ProjectiveTransformer(_ThetaTransformer):
     """theta [B,8] = first 8 entries of a 3x3 homography (last entry 1); divides by z,
-    z == 0 replaced by 1e-8 (:598)."""
+    z == 0 replaced by 1e-8 (:598).  With the bilinear sampler `transform` is differentiable with respect to the image and theta
+    (8 entries per sample: the ninth is the constant 1)."""
     param_dim = 8
 
     def __init__(self, out_size, name='SpatialProjectiveTransformer', interp_method='bilinear', **kwargs):
@@ -145,7 +211,7 @@ class _SymmetryTransformer(object):
     """The symmetric-pad transformers (ST:311-371, 454-517, 611-716): the input padded by 100 px per side in SYMMETRIC mode
     (H, W >= 100, as tf.pad requires; never materialised), sampled on the linspace grid of (oh+200) x (ow+200) points, then
     tf.image.resize_image_with_crop_or_pad(out, out_size[1], out_size[0]) -- target height ow, width oh: the result is
-    [B, ow, oh, C].  For square outputs the swap does not show."""
+    [B, ow, oh, C].  For square outputs the swap does not show.  Not differentiable."""
     param_dim = 0
     kind = -1
 
@@ -220,7 +286,7 @@ class ElasticTransformer(object):
     """Thin-plate spline transformer (ST:40-224).  param_dim = g, the side of the g x g control grid (linspace(-1,1,g)
     meshgrid, x fastest); theta [B, 2*g*g] = x offsets then y offsets of the control points.  L_inv is computed once at
     construction, in double, and kept on the device as fp32 transpose(L_inv[:,3:]); the kernel computes each sample's
-    coefficients once and U = r^2 ln r^2 per output pixel.  Output [B, oh, ow, C]."""
+    coefficients once and U = r^2 ln r^2 per output pixel.  Output [B, oh, ow, C].  Not differentiable."""
 
     def __init__(self, out_size, param_dim, name='SpatialElasticTransformer', interp_method='bilinear', **kwargs):
         g = int(param_dim)

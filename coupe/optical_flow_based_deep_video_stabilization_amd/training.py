@@ -1,7 +1,8 @@
 """Building blocks of the training step, one thin wrapper per library entry point: the objective
 `lossterm` / `masked_MSE` (main:188-210, "main" = main_flownetS_pyramid_noprevloss_dataloader.py), the total-variation
 terms and `loss_main` (main:213-275) with their gradient with respect to every predicted flow; filter / input gradients
-of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and its backward; the resamplers' adjoints.
+of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and its backward; the resamplers' adjoints; the
+gradients of the bilinear spatial transformers (`st_transform_backward`, `st_bilinear_interp_backward`).
 `train_step.Trainer` strings them into the whole step (forward, loss, backward, Adam: main:184-185, 333-335).
 
 Everything runs in the HIP library (csrc/train_ops.hip); there is no CPU path."""
@@ -216,6 +217,66 @@ def resize_bilinear_backward(dout, in_hw, gain: float = 1.0, din=None):
         _lib.check(_lib.lib().vstab_resize_bilinear_backward(dout.data_ptr(), B, oh, ow, C, din.data_ptr(), din.shape[1], din.shape[2],
                                                              float(gain), 1 if acc else 0, runtime.stream_ptr()))
     return din
+
+
+def _st_backward_args(img, dout, out_hw, d_img, need_img):
+    if not torch.is_tensor(img) or not img.is_cuda or img.dtype != torch.float32 or img.dim() != 4:
+        raise ValueError("img must be a float32 CUDA tensor [B,H,W,C]")
+    img = img.contiguous()
+    B, H, W, C = img.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    if not torch.is_tensor(dout) or dout.device != img.device or dout.dtype != torch.float32 or dout.numel() != B * oh * ow * C:
+        raise ValueError(f"dout must be a float32 tensor of {B}*{oh}*{ow}*{C} elements beside img")
+    acc = d_img is not None
+    if acc and (d_img.shape != img.shape or d_img.dtype != torch.float32 or d_img.device != img.device or not d_img.is_contiguous()):
+        raise ValueError("d_img must be a contiguous float32 tensor of img's shape beside it")
+    if d_img is None and need_img:
+        d_img = torch.empty_like(img)
+    return img, dout.contiguous(), (B, H, W, C, oh, ow), d_img, acc
+
+
+def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, need_theta: bool = True, d_img=None):
+    """Gradients of AffineTransformer / ProjectiveTransformer.transform (bilinear sampler) for the output gradient dout
+    [B,oh,ow,C]: (d img [B,H,W,C] or None, d theta [B,6|8] or None).  A given d_img is added into (the `accumulate` convention),
+    otherwise it is allocated and overwritten.  need_img / need_theta False skips that gradient's work.  d img is summed by float
+    atomics (its last bits may differ between runs); d theta is bit-reproducible."""
+    need_img = need_img or d_img is not None
+    img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
+    theta = theta.contiguous()
+    if not theta.is_cuda or theta.dtype != torch.float32 or theta.numel() not in (6 * B, 8 * B):
+        raise ValueError("theta must be a float32 CUDA tensor [B,6] or [B,8]")
+    tdim = theta.numel() // B
+    L = _lib.lib()
+    d_theta, ws, n = None, None, 0
+    if need_theta:
+        d_theta = torch.empty((B, tdim), dtype=torch.float32, device=img.device)
+        n = int(L.vstab_st_transform_backward_workspace_bytes(B, H, W, C, oh, ow))
+        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.check(L.vstab_st_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), tdim, dout.data_ptr(), oh, ow,
+                                                 d_img.data_ptr() if need_img else None, 1 if acc else 0,
+                                                 d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
+                                                 runtime.stream_ptr()))
+    return (d_img if need_img else None), d_theta
+
+
+def st_bilinear_interp_backward(img, x, y, dout, out_size, need_img: bool = True, need_x: bool = True, need_y: bool = True, d_img=None):
+    """Gradients of bilinear_interp(img, x, y, out_size) for dout [B*oh*ow, C]: (d img or None, d x [B*oh*ow] or None, d y or None);
+    d_img as in st_transform_backward."""
+    need_img = need_img or d_img is not None
+    img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
+    x, y = x.contiguous().reshape(-1), y.contiguous().reshape(-1)
+    for t in (x, y):
+        if not t.is_cuda or t.dtype != torch.float32 or t.numel() != B * oh * ow:
+            raise ValueError(f"x / y must be float32 CUDA tensors of B*out_h*out_w = {B * oh * ow} elements")
+    d_x = torch.empty_like(x) if need_x else None
+    d_y = torch.empty_like(y) if need_y else None
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.lib().vstab_st_bilinear_interp_backward(img.data_ptr(), B, H, W, C, x.data_ptr(), y.data_ptr(), dout.data_ptr(), oh, ow,
+                                                                d_img.data_ptr() if need_img else None, 1 if acc else 0,
+                                                                d_x.data_ptr() if need_x else None, d_y.data_ptr() if need_y else None,
+                                                                runtime.stream_ptr()))
+    return (d_img if need_img else None), d_x, d_y
 
 
 def pad_nearest_upsample(src, H: int, W: int):

@@ -209,6 +209,27 @@ VSTAB_API int vstab_host_tps_linv(int g, float *linv_t, int cap);
  * vstab_host_tps_linv; the thin-plate spline maps the linspace grid of (oh, ow) to source coordinates.  out [B,oh,ow,C]. */
 VSTAB_API int vstab_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                          int interp, float *out, int oh, int ow, void *stream);
+/* ---- backward of the BILINEAR sampler: vstab_st_transform (affine and projective) and vstab_st_bilinear_interp.  These two are the
+ * differentiable samplers; bicubic, the symmetric-pad transformers, the thin-plate spline and the homography warps have no backward.
+ * What TensorFlow's autodiff gives for ST:902-964 / 438-452 / 578-608: floor and the casts have zero derivative, the clip passes the
+ * gradient where -1 <= x <= W inclusive (0 outside and for NaN), taps on the zero border receive nothing; coordinates and taps are
+ * the forward's fp32 values.  img, B, H, W, C, theta | x, y, oh, ow as in the forward (B <= 65535, B*H*W*C < 2^31);
+ * dout [B,oh,ow,C] the gradient of the output.
+ *   d_img   [B,H,W,C] (nullable): zero-filled on `stream` by the call itself when accumulate == 0, added into when accumulate == 1.
+ *           Summed by float atomics: its last bits DEPEND ON ATOMIC ARRIVAL ORDER and may differ between two runs.
+ *   d_theta [B,theta_dim] (nullable; the projective 3x3's constant ninth entry has no gradient): overwritten; the sum over pixels is
+ *           taken in double in a fixed order -- two runs on the same inputs are bit-equal.  Needs
+ *           vstab_st_transform_backward_workspace_bytes() of 8-byte aligned workspace (VSTAB_E_NOMEM when too small; not read when
+ *           d_theta is NULL); the call makes no allocation.
+ *   d_x, d_y [B*oh*ow] (each nullable): overwritten, reproducible.
+ * A NULL output skips that gradient's work; all outputs NULL is VSTAB_E_SHAPE. */
+VSTAB_API size_t vstab_st_transform_backward_workspace_bytes(int B, int H, int W, int C, int oh, int ow);
+VSTAB_API int vstab_st_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim,
+                                          const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
+                                          void *workspace, size_t workspace_bytes, void *stream);
+VSTAB_API int vstab_st_bilinear_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y,
+                                                const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x,
+                                                float *d_y, void *stream);
 /* warp.transformImage / transformCropImage (warp.py:46-86, 89-129): M [B,9] = refMtrx . pMtrx maps the canonical
  * linspace(-1,1) grid of the OUTPUT size to source pixel coordinates; floor/ceil taps, zero outside. */
 VSTAB_API int vstab_homography_warp(const float *img, int B, int Hi, int Wi, int C, const float *M, float *out, int oh,
