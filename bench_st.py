@@ -4,7 +4,10 @@ over HIP events (>= 20 timed calls after warm-up), algorithmic bytes (12 read + 
 of 8 TB/s.  Prints one JSON line.  AffineTransformer with the bilinear sampler is the existing kernel, the yardstick.
 --backward adds the gradients of the affine bilinear transformer at the same shape (rows "backward"): d img (four global atomics
 per pixel-channel), d theta, both together, and torch's own grid_sample backward (NCHW, bilinear, zeros, align_corners=True) for scale -- an independent implementation of a comparable op,
-not a gate."""
+not a gate.
+--volume adds the 3-D volume transformer (rows "volume"): AffineVolumeTransformer at B = 4, 256^3, C = 1 under an oblique rotation of
+about 10 degrees plus a small shift -- forward by theta, d vol, d theta, both gradients -- with torch's 5-D grid_sample (bilinear,
+zeros, align_corners=True) forward timed interleaved for scale.  The forward counts 8 algorithmic bytes per output voxel."""
 import argparse
 import json
 import os
@@ -75,6 +78,38 @@ def backward_rows(img, th6, out_size, iters, warmup):
             for k, v in us.items()}
 
 
+def volume_rows(iters, warmup, B=4, n=256):
+    """forward: 4 B gathered + 4 B written per output voxel = 8; d vol: dout read, the zero fill and the add = 12; d theta: dout and
+    the volume read = 8; both: 16.  The fraction of 8 TB/s is algorithmic bytes over the HIP-event median."""
+    import math
+    from coupe.optical_flow_based_deep_video_stabilization_amd import training
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(3)
+    vol = torch.rand(B, n, n, n, 1, generator=g).cuda()
+    dout = torch.rand(B, n, n, n, 1, generator=g).cuda()
+    # about 10 degrees about the oblique axis (1, 2, 3) / sqrt(14) (Rodrigues), plus a small shift
+    a, k = math.radians(10.0), torch.tensor([1.0, 2.0, 3.0]) / math.sqrt(14.0)
+    K = torch.tensor([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = torch.eye(3) + math.sin(a) * K + (1 - math.cos(a)) * (K @ K)
+    theta = torch.cat([R, torch.tensor([[0.02], [-0.015], [0.01]])], 1).reshape(1, 12).repeat(B, 1).cuda()
+    out_size = (n, n, n)
+    tr = st.AffineVolumeTransformer(out_size)
+
+    def bwd(need_vol, need_theta):
+        return lambda: training.st3d_transform_backward(vol, theta, dout, out_size, need_vol=need_vol, need_theta=need_theta)
+
+    x = vol.permute(0, 4, 1, 2, 3).contiguous()
+    grid = F.affine_grid(theta.reshape(B, 3, 4), (B, 1, n, n, n), align_corners=True)
+    fns = {"forward_theta": lambda: tr.transform(vol, theta), "d_vol": bwd(True, False), "d_theta": bwd(False, True), "both": bwd(True, True),
+           "torch_grid_sample_forward": lambda: F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=True)}
+    us = time_interleaved(fns, iters, warmup)
+    nvox = B * n * n * n
+    nbytes = {"forward_theta": 8.0, "d_vol": 12.0, "d_theta": 8.0, "both": 16.0, "torch_grid_sample_forward": 8.0 + 12.0}     # + the grid read
+    rows = {k: {"us": round(v, 1), "alg_bytes": int(nbytes[k] * nvox), "frac_8TBs": round(nbytes[k] * nvox / (v * 1e-6) / 1e9 / PEAK_GBS, 3)}
+            for k, v in us.items()}
+    return {"batch": B, "depth": n, "height": n, "width": n, "channels": 1, "rows": rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -84,6 +119,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", default="", help="comma-separated variant names (default: all)")
     ap.add_argument("--backward", action="store_true", help="add the affine bilinear transformer's gradients (rows 'backward')")
+    ap.add_argument("--volume", action="store_true", help="add the 3-D volume transformer at B = 4, 256^3, C = 1 (rows 'volume')")
     args = ap.parse_args()
     if args.iters < 20:
         ap.error("--iters must be >= 20")
@@ -122,6 +158,8 @@ def main():
               "iters": args.iters, "device": torch.cuda.get_device_name(0), "variants": rows}
     if args.backward:
         result["backward"] = backward_rows(img, th6, out_size, args.iters, args.warmup)
+    if args.volume:
+        result["volume"] = volume_rows(args.iters, args.warmup)
     print(json.dumps(result))
 
 

@@ -62,6 +62,14 @@ EXPORTS = {
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "vstab_st_bilinear_interp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_st3d_meshgrid": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "vstab_st3d_bilinear_interp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "vstab_st3d_transform": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "vstab_st3d_transform_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 8),
+    "vstab_st3d_transform_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p] + [C.c_int] * 3 +
+                                      [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_st3d_bilinear_interp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int] * 4 +
+                                            [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "vstab_transform_image": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p]),
     "vstab_vec2mtrx": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_vgg16_load": (C.c_int, [C.c_void_p, C.POINTER(VstabTensor), C.c_int]),

@@ -408,6 +408,84 @@ extern "C" int vstab_st_bilinear_interp_backward(const float *img, int B, int H,
     return VSTAB_OK;
 }
 
+// ---- the 3-D volume transformer (sampler3d_ops.hip).  The shape is judged before the pointers: a shape outside the contract is
+// VSTAB_E_SHAPE whatever else is wrong with the call.
+static bool st3d_shape_ok(int B, int D, int H, int W, int C, int od, int oh, int ow, int edge)
+{
+    const long long lim = 1ll << 24, cap = 1ll << 40;          // fp32 holds every padded index; element counts far inside 63 bits
+    if (B < 1 || B > 65535 || D < 1 || H < 1 || W < 1 || C < 1 || od < 1 || oh < 1 || ow < 1 || edge < 0 || edge > (1 << 22)) return false;
+    if (D + 2ll * edge > lim || H + 2ll * edge > lim || W + 2ll * edge > lim || od > lim || oh > lim || ow > lim || C > lim) return false;
+    const long long vin = (long long)D * H, vout = (long long)od * oh;                   // < 2^48 each
+    if (vin > cap / W || vout > cap / ow) return false;
+    if (vin * W > cap / C / B || vout * ow > cap / C / B) return false;
+    int nbx, nby, nbz;
+    long long bricks;
+    return st3d_plan(B, od, oh, ow, nbx, nby, nbz, bricks);
+}
+
+extern "C" int vstab_st3d_meshgrid(float *out, int od, int oh, int ow, void *stream)
+{
+    if (od < 1 || oh < 1 || ow < 1 || od > (1 << 24) || oh > (1 << 24) || ow > (1 << 24) || (long long)od * oh > (1ll << 38) / ow)
+        return fail(nullptr, VSTAB_E_SHAPE, "st3d_meshgrid: bad shape (at most 2^38 voxels)");
+    if (!out) return fail(nullptr, VSTAB_E_STATE, "st3d_meshgrid: NULL buffer");
+    HIP_TRY(nullptr, launch_st3d_meshgrid(out, od, oh, ow, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st3d_bilinear_interp(const float *vol, int B, int D, int H, int W, int C, const float *x, const float *y, const float *z,
+                                          int od, int oh, int ow, int edge_size, float *out, void *stream)
+{
+    if (!st3d_shape_ok(B, D, H, W, C, od, oh, ow, edge_size)) return fail(nullptr, VSTAB_E_SHAPE, "st3d_bilinear_interp: bad shape (edge_size >= 0, B <= 65535)");
+    if (!vol || !x || !y || !z || !out) return fail(nullptr, VSTAB_E_STATE, "st3d_bilinear_interp: NULL buffer");
+    HIP_TRY(nullptr, launch_st3d_interp(vol, B, D, H, W, C, x, y, z, od, oh, ow, edge_size, out, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st3d_transform(const float *vol, int B, int D, int H, int W, int C, const float *theta, float *out, int od, int oh, int ow,
+                                    void *stream)
+{
+    if (!st3d_shape_ok(B, D, H, W, C, od, oh, ow, 1)) return fail(nullptr, VSTAB_E_SHAPE, "st3d_transform: bad shape (B <= 65535)");
+    if (!vol || !theta || !out) return fail(nullptr, VSTAB_E_STATE, "st3d_transform: NULL buffer");
+    HIP_TRY(nullptr, launch_st3d_transform(vol, B, D, H, W, C, theta, out, od, oh, ow, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" size_t vstab_st3d_transform_backward_workspace_bytes(int B, int D, int H, int W, int C, int od, int oh, int ow)
+{
+    if (!st3d_shape_ok(B, D, H, W, C, od, oh, ow, 1)) return 0;
+    return st3d_transform_backward_ws_bytes(B, od, oh, ow);
+}
+
+extern "C" int vstab_st3d_transform_backward(const float *vol, int B, int D, int H, int W, int C, const float *theta, const float *dout, int od,
+                                             int oh, int ow, float *d_vol, int accumulate, float *d_theta, void *workspace,
+                                             size_t workspace_bytes, void *stream)
+{
+    if (!st3d_shape_ok(B, D, H, W, C, od, oh, ow, 1)) return fail(nullptr, VSTAB_E_SHAPE, "st3d_transform_backward: bad shape (B <= 65535)");
+    if (!vol || !theta || !dout) return fail(nullptr, VSTAB_E_STATE, "st3d_transform_backward: NULL buffer");
+    if (!d_vol && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "st3d_transform_backward: d_vol and d_theta are both NULL");
+    if (d_theta) {
+        const size_t need = st3d_transform_backward_ws_bytes(B, od, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "st3d_transform_backward: workspace needs %zu bytes", need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "st3d_transform_backward: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(nullptr, launch_st3d_transform_backward(vol, B, D, H, W, C, theta, dout, od, oh, ow, d_vol, accumulate ? 1 : 0, d_theta,
+                                                    (double *)workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st3d_bilinear_interp_backward(const float *vol, int B, int D, int H, int W, int C, const float *x, const float *y,
+                                                   const float *z, int od, int oh, int ow, int edge_size, const float *dout, float *d_vol,
+                                                   int accumulate, float *dx, float *dy, float *dz, void *stream)
+{
+    if (!st3d_shape_ok(B, D, H, W, C, od, oh, ow, edge_size))
+        return fail(nullptr, VSTAB_E_SHAPE, "st3d_bilinear_interp_backward: bad shape (edge_size >= 0, B <= 65535)");
+    if (!vol || !x || !y || !z || !dout) return fail(nullptr, VSTAB_E_STATE, "st3d_bilinear_interp_backward: NULL buffer");
+    if (!d_vol && !dx && !dy && !dz) return fail(nullptr, VSTAB_E_SHAPE, "st3d_bilinear_interp_backward: d_vol, dx, dy and dz are all NULL");
+    HIP_TRY(nullptr, launch_st3d_interp_backward(vol, B, D, H, W, C, x, y, z, od, oh, ow, edge_size, dout, d_vol, accumulate ? 1 : 0, dx, dy, dz,
+                                                 (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
 extern "C" int vstab_vec2mtrx(const float *p, int B, int dim, int warp_approx, float *out, void *stream)
 {
     if (!p || !out) return fail(nullptr, VSTAB_E_STATE, "vec2mtrx: NULL buffer");

@@ -3,23 +3,17 @@
 // ONE family of kernels, templated on where a pixel's source coordinates come from (XS_*) and on the sampler (XI_*):
 // st3_tile_kernel for 3-channel frames (tile3.h's skeleton: 2-D tiles, 3-dword tap gathers, rows leaving as 16-byte stores),
 // st_pixel_kernel (one thread per pixel) for other channel counts.  Each piece of the reference's arithmetic is one device
-// function (st_axis, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta and
+// function (st_axis in st_axis.h, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta and
 // explicit-coordinate sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel, at the end of the file) that calls the same
 // functions; its d img is summed by float atomics and depends on their arrival order in its last bits, its d theta is reproducible.
 // -ffp-contract=off keeps the weight arithmetic the reference's op-by-op fp32 sequence.
 #include "vstab_internal.h"
 #include "hbm_profile.h"
 #include "tile3.h"
+#include "st_axis.h"
 #include <algorithm>
 
 namespace vstab {
-
-// tf.linspace(-1, 1, n)[i] in fp32 (start + i*step, step = 2/(n-1); a single point is -1)
-__device__ __forceinline__ float lin11(int i, int n)
-{
-    const float step = n > 1 ? 2.0f / (float)(n - 1) : 0.0f;
-    return -1.0f + (float)i * step;
-}
 
 // _meshgrid(out_size) (spatial_transformer.py:755-779): flat [3*oh*ow] = x_t row, y_t row, ones
 __global__ __launch_bounds__(256) void st_meshgrid_kernel(float *__restrict__ out, int oh, int ow)
@@ -80,30 +74,6 @@ struct StSrc {
 // the four taps of one output pixel: image coordinates clamped into the image (what is addressed), validity per axis (what
 // counts: an invalid tap reads as zero) and the blend weights (ST: w00, w01, w10, w11; homography: xr, yr)
 struct Taps { int xa, xb, ya, yb; bool vxa, vxb, vya, vyb; float w0, w1, w2, w3; };
-
-// One axis of bilinear_interp (spatial_transformer.py:902-964): v = (v+1)/2*(n-1), clipped to [-1, n], shifted by the one-pixel zero
-// pad; v0 = floor, v1 = min(v0+1, n+1) as index but the weights use the UNclipped v0+1.  lo = v - v0, hi = (v0+1) - v
-// (both exact in fp32); a, b the two image indices clamped into the image (what is addressed), va, vb whether they count (a tap on
-// the zero border reads as zero).  pass: the clip lets a gradient through, -1 <= v <= n inclusive, not for NaN (the backward's rule).
-struct Axis { float lo, hi; int a, b; bool va, vb, pass; };
-
-__device__ __forceinline__ Axis st_axis(float vn, int n)
-{
-    const float nf = (float)n;
-    float v = (vn + 1.0f) / 2.0f * (nf - 1.0f);
-    Axis A;
-    A.pass = v >= -1.0f && v <= nf - 1.0f + 1.0f;
-    v = fminf(fmaxf(v, -1.0f), nf - 1.0f + 1.0f);       // clip_by_value(x, -edge, W-1+edge); NaN -> -1
-    v += 1.0f;
-    const float v0f = floorf(v), v1f = v0f + 1.0f;
-    const int v0 = (int)v0f;                             // in [0, n+1] after the clip
-    const int v1 = (int)fminf(v1f, nf - 1.0f + 2.0f);
-    A.lo = v - v0f; A.hi = v1f - v;
-    // padded index p in [0, n+1]: image index p-1, zero on the border
-    A.va = v0 >= 1 && v0 <= n; A.vb = v1 >= 1 && v1 <= n;
-    A.a = min(max(v0 - 1, 0), n - 1); A.b = min(max(v1 - 1, 0), n - 1);
-    return A;
-}
 
 __device__ __forceinline__ Taps st_taps(const Axis &X, const Axis &Y)
 {
@@ -238,9 +208,6 @@ __device__ __forceinline__ void st_tps_coeff(const StSrc &S, int n, float *cf)
         cf[e] = acc;
     }
 }
-
-// point i of the linspace(-1, 1) sampling grid whose step is `step` (StSrc::sx, sy)
-__device__ __forceinline__ float st_grid_t(int i, float step) { return -1.0f + (float)i * step; }
 
 // Affine / ProjectiveTransformer at grid point (xt, yt): T_g = theta . (x_t, y_t, 1), the projective one divided by safe_z (ST:598).
 // xh, yh, zs (1 for the affine one) are the values before the division, which the backward's chain rule needs.
@@ -659,9 +626,6 @@ __device__ __forceinline__ void st_slope(const Axis &X, const Axis &Y, float I00
     gy = gy + ((I10 - I00) * X.hi + (I11 - I01) * X.lo) * g;
 }
 
-// the clip's gradient rule and the chain through (v + 1) / 2 * (n - 1)
-__device__ __forceinline__ float st_axis_chain(const Axis &A, float g, int n) { return A.pass ? g * (((float)n - 1.0f) / 2.0f) : 0.0f; }
-
 // a pixel's share of d theta, added to acc[8] in double: d x_h = gx / z, d y_h = gy / z, d z = -(gx x_h + gy y_h) / z^2
 __device__ __forceinline__ void st_theta_accum(double *acc, int tdim, float gxn, float gyn, float xt, float yt, float xh, float yh, float zs)
 {
@@ -675,35 +639,6 @@ __device__ __forceinline__ void st_theta_accum(double *acc, int tdim, float gxn,
     }
     acc[0] += gx * (double)xt; acc[1] += gx * (double)yt; acc[2] += gx;
     acc[3] += gy * (double)xt; acc[4] += gy * (double)yt; acc[5] += gy;
-}
-
-// acc[8] of every thread of a 256-thread workgroup -> part[8]: xor-shuffles inside a wave, the four waves added in wave order
-__device__ __forceinline__ void st_theta_reduce(double *acc, double (*red)[8], double *__restrict__ part)
-{
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) red[wave][k] = acc[k];
-    __syncthreads();
-    if (threadIdx.x < 8) part[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
-
-// d theta[n, k] = sum of sample n's `wgs` partials: thread t adds partials t, t + 256, ..., then st_theta_reduce's order
-__global__ __launch_bounds__(256) void st_theta_final_kernel(const double *__restrict__ part, int wgs, int tdim, float *__restrict__ d_theta)
-{
-    __shared__ double red[4][8], tot[8];
-    const int n = blockIdx.x;
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = threadIdx.x; i < wgs; i += 256)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] += part[((long long)n * wgs + i) * 8 + k];
-    st_theta_reduce(acc, red, tot);
-    __syncthreads();
-    if ((int)threadIdx.x < tdim) d_theta[(long long)n * tdim + threadIdx.x] = (float)tot[threadIdx.x];
 }
 
 struct StBwd {
@@ -884,7 +819,7 @@ hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, i
     dim3 grid;
     long long wgs;
     st_bwd_plan(B, H, W, C, oh, ow, tx, ty, grid, wgs);
-    st_theta_final_kernel<<<dim3((unsigned)B), dim3(256), 0, stream>>>(part, (int)wgs, tdim, d_theta);
+    st_theta_final_kernel<8><<<dim3((unsigned)B), dim3(256), 0, stream>>>(part, (int)wgs, tdim, d_theta);
     return hipGetLastError();
 }
 

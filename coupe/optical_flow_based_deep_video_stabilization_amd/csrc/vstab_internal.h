@@ -403,6 +403,22 @@ hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, i
 hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y, const float *dout, int oh,
                                      int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream);
 
+// The 3-D volume transformer (sampler3d_ops.hip): AffineVolumeTransformer / bilinear_interp3d / _meshgrid3d and their backward.
+// st3d_plan: bricks along each axis and per sample of a [B, od, oh, ow] output; false when the launch grid does not fit.  d_vol
+// (nullable) is zero-filled on `stream` first unless `accumulate`; `part`: st3d_transform_backward_ws_bytes of scratch.
+bool st3d_plan(int B, int od, int oh, int ow, int &nbx, int &nby, int &nbz, long long &bricks);
+hipError_t launch_st3d_meshgrid(float *out, int od, int oh, int ow, hipStream_t stream);
+hipError_t launch_st3d_interp(const float *vol, int B, int D, int H, int W, int C, const float *x, const float *y, const float *z, int od, int oh,
+                              int ow, int edge, float *out, hipStream_t stream);
+hipError_t launch_st3d_transform(const float *vol, int B, int D, int H, int W, int C, const float *theta, float *out, int od, int oh, int ow,
+                                 hipStream_t stream);
+size_t st3d_transform_backward_ws_bytes(int B, int od, int oh, int ow);
+hipError_t launch_st3d_transform_backward(const float *vol, int B, int D, int H, int W, int C, const float *theta, const float *dout, int od, int oh,
+                                          int ow, float *d_vol, int accumulate, float *d_theta, double *part, hipStream_t stream);
+hipError_t launch_st3d_interp_backward(const float *vol, int B, int D, int H, int W, int C, const float *x, const float *y, const float *z,
+                                       int od, int oh, int ow, int edge, const float *dout, float *d_vol, int accumulate, float *d_x, float *d_y,
+                                       float *d_z, hipStream_t stream);
+
 // clip driver helpers (clip_ops.hip)
 hipError_t launch_resize_u8(const unsigned char *src, int B, int sh, int sw, unsigned char *dst, int dh, int dw, hipStream_t stream);
 hipError_t launch_resize_f32_to_u8(const float *src, int B, int sh, int sw, unsigned char *dst, int dh, int dw, hipStream_t stream);

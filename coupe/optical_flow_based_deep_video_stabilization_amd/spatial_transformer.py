@@ -1,15 +1,15 @@
 """Drop-ins for the 2-D samplers of the reference's `spatial_transformer.py`: `transformer` (:34-38),
-`ElasticTransformer` (:40-224), `SimilarityTransformer` (:311-371), `AffineTransformer` (:373-452),
+`ElasticTransformer` (:40-224), `AffineVolumeTransformer` (:227-308), `SimilarityTransformer` (:311-371), `AffineTransformer` (:373-452),
 `AffineSymmetryTransformer` (:454-517), `ProjectiveTransformer` (:519-608), `ProjectiveSymmetryTransformer`
-(:611-716), `_meshgrid` (:755-779), `_repeat` (:782-785), `_interpolate` (:787-792), `bilinear_interp` (:902-964)
-and `bicubic_interp` (:966-1072).  None of them is executed by the reference's runnable scripts (they are only
-imported, main:4 and cell.py:2); the arithmetic runs in HIP kernels (csrc/sampler_ops.hip).  The 3-D classes
-(`AffineVolumeTransformer`, `bilinear_interp3d`, `_meshgrid3d`, `_interpolate3d`) are not provided.
+(:611-716), `_meshgrid3d` (:725-753), `_meshgrid` (:755-779), `_repeat` (:782-785), `_interpolate` (:787-792), `_interpolate3d` (:794-795),
+`bilinear_interp3d` (:797-899), `bilinear_interp` (:902-964) and `bicubic_interp` (:966-1072).  None of them is executed by the reference's runnable scripts (they are only
+imported, main:4 and cell.py:2); the arithmetic runs in HIP kernels (csrc/sampler_ops.hip, csrc/sampler3d_ops.hip for the volume transformer).
 
 Differentiable (torch.autograd, HIP backward kernels): `AffineTransformer.transform`, `ProjectiveTransformer.transform` and
 `transformer()` with the bilinear sampler, with respect to the image and `theta`, and `bilinear_interp` with respect to the image,
-`x` and `y`.  The gradient of the image is summed by float atomics (last bits may differ between runs); those of `theta`, `x`, `y`
-are bit-reproducible.  NOT differentiable -- the result has no `grad_fn`, whatever requires grad: `bicubic_interp` and
+`x` and `y`; `AffineVolumeTransformer.transform` with respect to the volume and `theta`, `bilinear_interp3d` with respect to the
+volume, `x`, `y` and `z`.  The gradient of the image or volume is summed by float atomics (last bits may differ between runs); those of `theta`, `x`, `y`,
+`z` are bit-reproducible.  NOT differentiable -- the result has no `grad_fn`, whatever requires grad: `bicubic_interp` and
 `interp_method='bicubic'`, the symmetric-pad transformers, `ElasticTransformer`."""
 from __future__ import annotations
 
@@ -320,6 +320,142 @@ class ElasticTransformer(object):
                                                              self.L_inv.data_ptr(), interp, out.data_ptr(), oh, ow,
                                                              runtime.stream_ptr()))
         return out
+
+
+# ---------------------------------------------------------------------------------------------------- the 3-D volume transformer
+def _out_size3(out_size):
+    if len(out_size) != 3:
+        raise ValueError("out_size must be (depth, height, width)")
+    return int(out_size[0]), int(out_size[1]), int(out_size[2])
+
+
+def _vol5(vol, name):
+    vol = _f32_cuda(vol, name)
+    if vol.dim() != 5:
+        raise ValueError(f"{name} must be [B,D,H,W,C]")
+    return vol
+
+
+def _meshgrid3d(out_size, device=None):
+    """Flat [4*D*H*W] sampling grid: linspace(-1,1,W) as x (fastest), linspace(-1,1,H) as y, linspace(-1,1,D) as z (slowest), ones."""
+    runtime._require_gpu()
+    od, oh, ow = _out_size3(out_size)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    out = torch.empty(4 * od * oh * ow, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vstab_st3d_meshgrid(out.data_ptr(), od, oh, ow, runtime.stream_ptr()))
+    return out
+
+
+def _bilinear_interp3d_call(vol, x, y, z, out_size, edge_size):
+    B, D, H, W, Cc = vol.shape
+    od, oh, ow = out_size
+    out = torch.empty((B * od * oh * ow, Cc), dtype=torch.float32, device=vol.device)
+    with torch.cuda.device(vol.device):
+        _lib.check(_lib.lib().vstab_st3d_bilinear_interp(vol.data_ptr(), B, D, H, W, Cc, x.data_ptr(), y.data_ptr(), z.data_ptr(), od, oh, ow,
+                                                         edge_size, out.data_ptr(), runtime.stream_ptr()))
+    return out
+
+
+class _BilinearInterp3dFn(torch.autograd.Function):
+    """bilinear_interp3d with its HIP backward (training.st3d_bilinear_interp_backward)."""
+
+    @staticmethod
+    def forward(ctx, vol, x, y, z, out_size, edge_size):
+        ctx.save_for_backward(vol, x, y, z)
+        ctx.out_size, ctx.edge_size = out_size, edge_size
+        return _bilinear_interp3d_call(vol, x, y, z, out_size, edge_size)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        vol, x, y, z = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = training.st3d_bilinear_interp_backward(vol, x, y, z, dout, ctx.out_size, edge_size=ctx.edge_size, need_vol=need[0],
+                                                       need_x=need[1], need_y=need[2], need_z=need[3])
+        return (*grads, None, None)
+
+
+def bilinear_interp3d(vol, x, y, z, out_size, edge_size=1):
+    """vol [B,D,H,W,C]; x, y, z flat [B*od*oh*ow] normalised to [-1,1]; out_size = (od, oh, ow) -> [B*od*oh*ow, C].
+    The volume is zero-padded by edge_size voxels (never materialised); coordinates are clipped to [-edge_size, n-1+edge_size].
+    Differentiable with respect to vol, x, y and z (module docstring)."""
+    vol = _vol5(vol, "vol")
+    B = vol.shape[0]
+    out_size = _out_size3(out_size)
+    edge_size = int(edge_size)
+    if edge_size < 0:
+        raise ValueError("edge_size must be >= 0")
+    nvox = B * out_size[0] * out_size[1] * out_size[2]
+    x, y, z = (_f32_cuda(t.to(torch.float32), n).reshape(-1) for t, n in ((x, "x"), (y, "y"), (z, "z")))
+    if x.numel() != nvox or y.numel() != nvox or z.numel() != nvox:
+        raise ValueError(f"x/y/z must have B*out_d*out_h*out_w = {nvox} elements")
+    if _wants_grad(vol, x, y, z):
+        return _BilinearInterp3dFn.apply(vol, x, y, z, out_size, edge_size)
+    return _bilinear_interp3d_call(vol, x, y, z, out_size, edge_size)
+
+
+def _interpolate3d(vol, x, y, z, out_size, method='bilinear'):
+    return bilinear_interp3d(vol, x, y, z, out_size)            # `method` is ignored, as in the reference (:795)
+
+
+def _volume_transform_call(inp, theta, out_size):
+    B, D, H, W, Cc = inp.shape
+    od, oh, ow = out_size
+    out = torch.empty((B, od, oh, ow, Cc), dtype=torch.float32, device=inp.device)
+    with torch.cuda.device(inp.device):
+        _lib.check(_lib.lib().vstab_st3d_transform(inp.data_ptr(), B, D, H, W, Cc, theta.data_ptr(), out.data_ptr(), od, oh, ow,
+                                                   runtime.stream_ptr()))
+    return out
+
+
+class _VolumeTransformFn(torch.autograd.Function):
+    """AffineVolumeTransformer.transform with its HIP backward (training.st3d_transform_backward); theta flat."""
+
+    @staticmethod
+    def forward(ctx, inp, theta, out_size):
+        ctx.save_for_backward(inp, theta)
+        ctx.out_size = out_size
+        return _volume_transform_call(inp, theta, out_size)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        inp, theta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_inp, d_theta = training.st3d_transform_backward(inp, theta, dout, ctx.out_size, need_vol=need[0], need_theta=need[1])
+        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None
+
+
+class AffineVolumeTransformer(object):
+    """theta [B,12] = row-major 3x4 matrix acting on (x_t, y_t, z_t, 1), each in [-1,1]; out_size = (depth, height, width).
+    inp [B,D,H,W,C] -> [B,od,oh,ow,C], sampled by bilinear_interp3d with edge_size = 1 whatever `interp_method` says (the
+    reference ignores it, :794-795).  `transform` is differentiable with respect to the volume and theta."""
+    param_dim = 12
+
+    def __init__(self, out_size, name='SpatialAffineVolumeTransformer', interp_method='bilinear', **kwargs):
+        self.name = name
+        self.out_size = _out_size3(out_size)
+        self.interp_method = interp_method
+        self._grid = None
+
+    @property
+    def voxel_grid(self):
+        if self._grid is None:
+            self._grid = _meshgrid3d(self.out_size)
+        return self._grid
+
+    def transform(self, inp, theta):
+        inp = _vol5(inp, "inp")
+        B = inp.shape[0]
+        theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
+        if theta.numel() != B * self.param_dim:
+            raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
+        if _wants_grad(inp, theta):
+            return _VolumeTransformFn.apply(inp, theta, self.out_size)
+        return _volume_transform_call(inp, theta, self.out_size)
 
 
 def transformer(inp, theta, out_size, name='SpatialTransformer', **kwargs):

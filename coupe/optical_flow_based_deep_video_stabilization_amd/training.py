@@ -279,6 +279,67 @@ def st_bilinear_interp_backward(img, x, y, dout, out_size, need_img: bool = True
     return (d_img if need_img else None), d_x, d_y
 
 
+def _st3d_backward_args(vol, dout, out_size, d_vol, need_vol):
+    if not torch.is_tensor(vol) or not vol.is_cuda or vol.dtype != torch.float32 or vol.dim() != 5:
+        raise ValueError("vol must be a float32 CUDA tensor [B,D,H,W,C]")
+    vol = vol.contiguous()
+    B, D, H, W, C = vol.shape
+    od, oh, ow = int(out_size[0]), int(out_size[1]), int(out_size[2])
+    if not torch.is_tensor(dout) or dout.device != vol.device or dout.dtype != torch.float32 or dout.numel() != B * od * oh * ow * C:
+        raise ValueError(f"dout must be a float32 tensor of {B}*{od}*{oh}*{ow}*{C} elements beside vol")
+    acc = d_vol is not None
+    if acc and (d_vol.shape != vol.shape or d_vol.dtype != torch.float32 or d_vol.device != vol.device or not d_vol.is_contiguous()):
+        raise ValueError("d_vol must be a contiguous float32 tensor of vol's shape beside it")
+    if d_vol is None and need_vol:
+        d_vol = torch.empty_like(vol)
+    return vol, dout.contiguous(), (B, D, H, W, C, od, oh, ow), d_vol, acc
+
+
+def st3d_transform_backward(vol, theta, dout, out_size, need_vol: bool = True, need_theta: bool = True, d_vol=None):
+    """Gradients of AffineVolumeTransformer.transform for the output gradient dout [B,od,oh,ow,C]: (d vol [B,D,H,W,C] or None,
+    d theta [B,12] or None).  A given d_vol is added into, otherwise it is allocated and overwritten; need_vol / need_theta False
+    skips that gradient's work.  d vol is summed by float atomics (its last bits may differ between runs); d theta is
+    bit-reproducible."""
+    need_vol = need_vol or d_vol is not None
+    vol, dout, (B, D, H, W, C, od, oh, ow), d_vol, acc = _st3d_backward_args(vol, dout, out_size, d_vol, need_vol)
+    theta = theta.contiguous()
+    if not theta.is_cuda or theta.dtype != torch.float32 or theta.numel() != 12 * B:
+        raise ValueError("theta must be a float32 CUDA tensor [B,12]")
+    L = _lib.lib()
+    d_theta, ws, n = None, None, 0
+    if need_theta:
+        d_theta = torch.empty((B, 12), dtype=torch.float32, device=vol.device)
+        n = int(L.vstab_st3d_transform_backward_workspace_bytes(B, D, H, W, C, od, oh, ow))
+        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=vol.device)
+    with torch.cuda.device(vol.device):
+        _lib.check(L.vstab_st3d_transform_backward(vol.data_ptr(), B, D, H, W, C, theta.data_ptr(), dout.data_ptr(), od, oh, ow,
+                                                   d_vol.data_ptr() if need_vol else None, 1 if acc else 0,
+                                                   d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
+                                                   runtime.stream_ptr()))
+    return (d_vol if need_vol else None), d_theta
+
+
+def st3d_bilinear_interp_backward(vol, x, y, z, dout, out_size, edge_size: int = 1, need_vol: bool = True, need_x: bool = True,
+                                  need_y: bool = True, need_z: bool = True, d_vol=None):
+    """Gradients of bilinear_interp3d(vol, x, y, z, out_size, edge_size) for dout [B*od*oh*ow, C]: (d vol or None, d x [B*od*oh*ow]
+    or None, d y or None, d z or None); d_vol as in st3d_transform_backward."""
+    need_vol = need_vol or d_vol is not None
+    vol, dout, (B, D, H, W, C, od, oh, ow), d_vol, acc = _st3d_backward_args(vol, dout, out_size, d_vol, need_vol)
+    x, y, z = x.contiguous().reshape(-1), y.contiguous().reshape(-1), z.contiguous().reshape(-1)
+    for t in (x, y, z):
+        if not t.is_cuda or t.dtype != torch.float32 or t.numel() != B * od * oh * ow:
+            raise ValueError(f"x / y / z must be float32 CUDA tensors of B*out_d*out_h*out_w = {B * od * oh * ow} elements")
+    d_x = torch.empty_like(x) if need_x else None
+    d_y = torch.empty_like(y) if need_y else None
+    d_z = torch.empty_like(z) if need_z else None
+    ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
+    with torch.cuda.device(vol.device):
+        _lib.check(_lib.lib().vstab_st3d_bilinear_interp_backward(vol.data_ptr(), B, D, H, W, C, x.data_ptr(), y.data_ptr(), z.data_ptr(), od, oh,
+                                                                  ow, int(edge_size), dout.data_ptr(), d_vol.data_ptr() if need_vol else None,
+                                                                  1 if acc else 0, ptr(d_x), ptr(d_y), ptr(d_z), runtime.stream_ptr()))
+    return (d_vol if need_vol else None), d_x, d_y, d_z
+
+
 def pad_nearest_upsample(src, H: int, W: int):
     """PadLayer(1) -> nearest resize (align_corners=True) to HxW (model.py:795-802, 882-884); C % 4 == 0."""
     src = src.contiguous()

@@ -230,6 +230,45 @@ VSTAB_API int vstab_st_transform_backward(const float *img, int B, int H, int W,
 VSTAB_API int vstab_st_bilinear_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y,
                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x,
                                                 float *d_y, void *stream);
+/* ---- the 3-D volume transformer (spatial_transformer.py:227-308, 725-753, 794-899), forward and backward.  vol [B,D,H,W,C];
+ * out_size = (od, oh, ow) = (depth, height, width) as the reference passes it.  One thread per output voxel, any C; a workgroup
+ * owns a VSTAB_ST3D_BRICK_Z x _Y x _X brick of one sample's output.  64-bit element offsets: the limits are B <= 65535, every
+ * extent (plus 2 * edge_size) <= 2^24 (fp32 holds the indices exactly), at most 2^40 elements per tensor, and a launch grid of
+ * B * bricks < 2^31; anything else is VSTAB_E_SHAPE, checked before the pointers are looked at. */
+#ifndef VSTAB_ST3D_BRICK_Z            /* a measurement build may choose another brick */
+#define VSTAB_ST3D_BRICK_Z 2
+#define VSTAB_ST3D_BRICK_Y 8
+#define VSTAB_ST3D_BRICK_X 16
+#endif
+/* _meshgrid3d(out_size) (ST:725-753): out[4*od*oh*ow] = x_t row, y_t row, z_t row, ones; x fastest, z slowest. */
+VSTAB_API int vstab_st3d_meshgrid(float *out, int od, int oh, int ow, void *stream);
+/* bilinear_interp3d(vol, x, y, z, out_size, edge_size) / _interpolate3d (ST:794-899): x, y, z flat [B*od*oh*ow] normalised to
+ * [-1,1]; per axis v = (v+1)/2*(n-1) clipped to [-e, n-1+e] (NaN reads as -e) against a volume zero-padded by e = edge_size >= 0
+ * voxels (never materialised); weights (wz*wy)*wx, the eight products summed in the order 000 ... 111 (x last).  out [B*od*oh*ow, C]. */
+VSTAB_API int vstab_st3d_bilinear_interp(const float *vol, int B, int D, int H, int W, int C, const float *x, const float *y,
+                                         const float *z, int od, int oh, int ow, int edge_size, float *out, void *stream);
+/* AffineVolumeTransformer.transform (ST:252-308): theta [B,12] = row-major 3x4 acting on (x_t, y_t, z_t, 1) of the linspace(-1,1)
+ * grid of the OUTPUT size, ((t0 x + t1 y) + t2 z) + t3 with every product and sum rounded to fp32; edge_size = 1.
+ * out [B,od,oh,ow,C]. */
+VSTAB_API int vstab_st3d_transform(const float *vol, int B, int D, int H, int W, int C, const float *theta, float *out, int od,
+                                   int oh, int ow, void *stream);
+/* Backward of the two, what TensorFlow's autodiff gives: floor and the casts have zero derivative, the clip passes the gradient where
+ * -e <= v <= n-1+e inclusive (0 outside and for NaN), chain factor (n-1)/2 per axis, taps on the pad receive nothing; coordinates
+ * and taps are the forward's fp32 values.  dout [B,od,oh,ow,C].
+ *   d_vol   [B,D,H,W,C] (nullable): zero-filled on `stream` by the call when accumulate == 0, added into when accumulate == 1.
+ *           Eight float atomics per voxel-channel: its last bits DEPEND ON ATOMIC ARRIVAL ORDER and may differ between two runs.
+ *   d_theta [B,12] (nullable): overwritten; summed in double in a fixed order -- two runs are bit-equal.  Needs
+ *           vstab_st3d_transform_backward_workspace_bytes() of 8-byte aligned workspace (VSTAB_E_NOMEM when too small; not read
+ *           when d_theta is NULL); the call makes no allocation.
+ *   dx, dy, dz [B*od*oh*ow] (each nullable): overwritten, reproducible.
+ * A NULL output skips that gradient's work; all outputs NULL is VSTAB_E_SHAPE. */
+VSTAB_API size_t vstab_st3d_transform_backward_workspace_bytes(int B, int D, int H, int W, int C, int od, int oh, int ow);
+VSTAB_API int vstab_st3d_transform_backward(const float *vol, int B, int D, int H, int W, int C, const float *theta, const float *dout,
+                                            int od, int oh, int ow, float *d_vol, int accumulate, float *d_theta, void *workspace,
+                                            size_t workspace_bytes, void *stream);
+VSTAB_API int vstab_st3d_bilinear_interp_backward(const float *vol, int B, int D, int H, int W, int C, const float *x, const float *y,
+                                                  const float *z, int od, int oh, int ow, int edge_size, const float *dout,
+                                                  float *d_vol, int accumulate, float *dx, float *dy, float *dz, void *stream);
 /* warp.transformImage / transformCropImage (warp.py:46-86, 89-129): M [B,9] = refMtrx . pMtrx maps the canonical
  * linspace(-1,1) grid of the OUTPUT size to source pixel coordinates; floor/ceil taps, zero outside. */
 VSTAB_API int vstab_homography_warp(const float *img, int B, int Hi, int Wi, int C, const float *M, float *out, int oh,
