@@ -226,7 +226,8 @@ def _bn_ref(z, beta, eps=1e-5):
     return z, y, mean, var
 
 
-@pytest.mark.parametrize("B,H,W,cs,c_off,C", [(2, 9, 11, 64, 0, 64), (3, 16, 16, 40, 8, 24), (1, 33, 47, 128, 0, 128), (8, 32, 32, 68, 4, 64)])
+@pytest.mark.parametrize("B,H,W,cs,c_off,C", [(2, 9, 11, 64, 0, 64), (3, 16, 16, 40, 8, 24), (1, 33, 47, 128, 0, 128), (8, 32, 32, 68, 4, 64),
+                                              (1, 300, 331, 8, 4, 4)])      # 99300 rows: the workload's 768 chunks (130 rows each, 764..767 empty)
 def test_bn_lrelu_train_forward_backward(B, H, W, cs, c_off, C):
     g0 = torch.Generator().manual_seed(C + H)
     zfull = torch.randn(B, H, W, cs, generator=g0) * 2 + 0.5
