@@ -32,6 +32,7 @@ EXPORTS = {
     "vstab_workspace_layout_ctx": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(VstabWsEntry), C.c_int]),
     "vstab_set_plan_batch": (C.c_int, [C.c_void_p, C.c_int]),
     "vstab_set_plan_flags": (C.c_int, [C.c_void_p, C.c_uint]),
+    "vstab_conv1_forward": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vstab_workspace_bytes_ctx": (C.c_size_t, [C.c_void_p] + [C.c_int] * 4),
     "vstab_flownets_forward": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 5 +
                                [C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -102,6 +102,7 @@ extern "C" int vstab_create(vstab_ctx **out, int device)
     HIP_TRY(nullptr, hipSetDevice(device));
     HIP_TRY(nullptr, conv_set_attributes());
     HIP_TRY(nullptr, rowwin_set_attributes());
+    HIP_TRY(nullptr, conv1_bf16x3_set_attributes());
     HIP_TRY(nullptr, tap_panel_set_attributes());
     HIP_TRY(nullptr, wino_gemm_stream_set_attributes());
     vstab_ctx *c = new (std::nothrow) vstab_ctx();

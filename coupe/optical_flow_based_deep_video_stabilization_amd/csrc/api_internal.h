@@ -23,6 +23,7 @@ struct vstab_ctx {
     // float offsets into dev_weights
     size_t enc_w[10], enc_b[10];
     size_t enc0_rw = 0;                  // layer-1 weights in the row-window layout (conv_rowwin.hip)
+    size_t enc0_b3 = 0;                  // ... and as three bf16 planes per K-group of 16 (conv1_bf16x3.hip); 0 = not packed (Cout != 64)
     size_t zero_b = 0;                   // 1024 zeros
     size_t wino_w[10] = {0};             // Winograd-domain operands of the 3x3 stride-1 stages (winograd_ops.hip)
     size_t dec_w[4], dec_b[4];

@@ -2,6 +2,7 @@
 // its per-launch profiling, and the entry points that run the evaluator's tail in the forward's last launch.
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 
 #include "flownet_plan.h"
 
@@ -56,6 +57,11 @@ extern "C" int vstab_load_weights(vstab_ctx *ctx, const vstab_tensor *t, int cou
             const int lead = rowwin_lead(-e.p, cin), segp = rowwin_segp(-e.p, e.k, cin);
             ctx->enc0_rw = reserve((size_t)e.k * (segp / 32) * npad * 32);
             pack_conv_rowwin(W->data, scale.data(), e.k, e.k, cin, e.cout, npad, lead, segp, host.data() + ctx->enc0_rw);
+            ctx->enc0_b3 = 0;
+            if (npad == 64) {                    // the same K order as three bf16 planes (two bf16 per float of the blob)
+                ctx->enc0_b3 = reserve((size_t)e.k * (segp / 16) * 3 * 64 * 16 / 2);
+                pack_conv1_bf16x3(W->data, scale.data(), e.k, e.k, cin, e.cout, lead, segp, reinterpret_cast<uint16_t *>(host.data() + ctx->enc0_b3));
+            }
         }
     }
     // decoder
@@ -182,6 +188,82 @@ static int forward_impl(vstab_ctx *ctx, const float *feats, int B, int H, int W,
     return VSTAB_OK;
 }
 
+// The first layer on a row-window kernel, when its alignment conditions hold (*launched): six bf16 piece-products per multiply on the
+// bf16 MFMA (conv1_bf16x3.hip) when the plan says so, else the fp32 MFMA (conv_rowwin.hip) -- same tiles, same window, same output
+// addressing, other operands.  out = [B][Ho][Wo][cs_out], channels c_off .. c_off + N; tickets != NULL: the launch zeroes them.
+static int conv1_rowwin(vstab_ctx *ctx, bool bf16x3, const float *feats, int B, int H, int W, int Cin, int Ho, int Wo, int N, int Npad,
+                        float *out, int cs_out, int c_off, unsigned *tickets, hipStream_t stream, hipEvent_t ev_a, hipEvent_t ev_b,
+                        const char **kname, bool *launched)
+{
+    const Layer &e = NET[0];
+    const float *dw = ctx->dev_weights;
+    *launched = false;
+    RowWinParams r{};
+    r.in = feats; r.out = out; r.wpk = dw + ctx->enc0_rw; r.bias = dw + ctx->enc_b[0];
+    const long long in_bytes = (long long)B * H * W * Cin * 4;
+    r.in_bytes = (unsigned)std::min<long long>(in_bytes, 0xFFFFFFFFLL);
+    r.B = B; r.Hi = H; r.Wi = W; r.Cs_in = Cin; r.KH = e.k;
+    r.SEGP = rowwin_segp(-e.p, e.k, Cin);
+    r.s_in = e.s; r.off_y = -e.p;
+    r.e_off = -e.p * Cin - rowwin_lead(-e.p, Cin);
+    r.w_a = ((r.e_off % 4) + 4) % 4;
+    r.MB = rowwin_mb(B, Ho, Wo);
+    r.WLEN = round_up(r.s_in * Cin * (64 * r.MB - 1) + r.w_a + r.SEGP, 4);
+    r.Ho = Ho; r.Wo = Wo; r.Cs_out = cs_out; r.c_off = c_off; r.N = N; r.Npad = Npad; r.act = 1;
+    if (in_bytes >= 0x80000000LL || !rowwin_applicable(r)) return VSTAB_OK;
+    const bool b3 = bf16x3 && ctx->enc0_b3 != 0 && conv1_bf16x3_applicable(r);
+    if (b3) r.wpk = dw + ctx->enc0_b3;
+    auto launch1 = [&](const RowWinParams &q, hipEvent_t a, hipEvent_t b) {
+        return b3 ? launch_conv1_bf16x3(q, stream, a, b) : launch_conv_rowwin(q, stream, a, b);
+    };
+    if (tickets) { r.clear_words = tickets; r.clear_n = SKINNY_MAX_TILES; }
+    *launched = true;
+    const int rem = Wo % 128;
+    if (r.MB == 2 && Wo > 128 && rem >= 1 && rem <= 64) {
+        // 128 k + (1..64) columns: k full tiles, then the rest as ONE 64-pixel tile (second launch; events span both)
+        RowWinParams t = r;
+        r.ntile_x = Wo / 128;
+        t.MB = 1; t.ox_base = r.ntile_x * 128; t.ntile_x = 1; t.clear_n = 0;
+        t.WLEN = round_up(t.s_in * Cin * 63 + t.w_a + t.SEGP, 4);
+        if (rowwin_applicable(t)) {
+            HIP_TRY(ctx, launch1(r, ev_a, nullptr));
+            HIP_TRY(ctx, launch1(t, nullptr, ev_b));
+            *kname = b3 ? "conv1_bf16x3_kernel<7, 2> + <4, 1> tail" : "conv_rowwin_kernel<7, 2> + <4, 1> tail";
+            return VSTAB_OK;
+        }
+        r.ntile_x = 0;
+    }
+    HIP_TRY(ctx, launch1(r, ev_a, ev_b));
+    if (b3) *kname = r.MB == 2 ? "conv1_bf16x3_kernel<7, 2>" : "conv1_bf16x3_kernel<4, 1>";
+    else *kname = r.MB == 2 ? "conv_rowwin_kernel<7, 2>" : "conv_rowwin_kernel<4, 1>";
+    return VSTAB_OK;
+}
+
+// conv1 alone (diagnostic: tests of the layer's two forms), as the forward of this context would run it
+extern "C" int vstab_conv1_forward(vstab_ctx *ctx, const float *feats, int B, int H, int W, int Cin, float *out, int cs_out, int c_off,
+                                   void *stream_)
+{
+    if (!ctx) return fail(nullptr, VSTAB_E_STATE, "conv1_forward: ctx is NULL");
+    if (!ctx->loaded) return fail(ctx, VSTAB_E_STATE, "conv1_forward: vstab_load_weights has not been called");
+    if (Cin != ctx->cin) return fail(ctx, VSTAB_E_SHAPE, "conv1_forward: feats has %d channels, weights expect %d", Cin, ctx->cin);
+    if (!feats || !out) return fail(ctx, VSTAB_E_STATE, "conv1_forward: NULL buffer");
+    const PlanPin pin = pin_of(ctx);
+    std::unique_ptr<Plan> pl(new (std::nothrow) Plan);
+    if (!pl) return fail(ctx, VSTAB_E_NOMEM, "conv1_forward: out of host memory");
+    if (B < 1 || !make_plan(B, H, W, Cin, *pl, &pin)) return fail(ctx, VSTAB_E_SHAPE, "conv1_forward: unsupported problem %dx%dx%dx%d", B, H, W, Cin);
+    const ConvParams &p = pl->cp[0];
+    if (c_off < 0 || cs_out < c_off + p.N || (long long)B * p.Ho * p.Wo * cs_out * 4 >= 0x80000000LL)
+        return fail(ctx, VSTAB_E_SHAPE, "conv1_forward: output slice %d + %d of %d channels", c_off, p.N, cs_out);
+    if (((uintptr_t)feats & 15) || ((uintptr_t)out & 3)) return fail(ctx, VSTAB_E_ALIGN, "conv1_forward: feats must be 16-byte aligned");
+    const char *kname = nullptr;
+    bool launched = false;
+    const int rc = conv1_rowwin(ctx, pl->conv1_bf16x3, feats, B, H, W, Cin, p.Ho, p.Wo, p.N, p.Npad, out, cs_out, c_off, nullptr,
+                                (hipStream_t)stream_, nullptr, nullptr, &kname, &launched);
+    if (rc != VSTAB_OK) return rc;
+    if (!launched) return fail(ctx, VSTAB_E_SHAPE, "conv1_forward: the row-window kernels do not take this geometry");
+    return VSTAB_OK;
+}
+
 static int forward_chunk(vstab_ctx *ctx, const float *feats, int B, int H, int W, int Cin, float *pf6, float *pf5,
                          float *pf4, float *pf3, float *pf2, void *workspace, size_t workspace_bytes, void *stream_, FusedTail *tail)
 {
@@ -245,39 +327,12 @@ static int forward_chunk(vstab_ctx *ctx, const float *feats, int B, int H, int W
         TraceRange layer_range(e.name);
         ConvParams p = pl.cp[i];
         if (i == 0) {           // first layer: row-window kernel when its alignment conditions hold
-            RowWinParams r{};
-            r.in = feats; r.out = buf(B_CONV1); r.wpk = dw + ctx->enc0_rw; r.bias = dw + ctx->enc_b[0];
-            const long long in_bytes = (long long)B * H * W * Cin * 4;
-            r.in_bytes = (unsigned)std::min<long long>(in_bytes, 0xFFFFFFFFLL);
-            r.B = B; r.Hi = H; r.Wi = W; r.Cs_in = Cin; r.KH = e.k;
-            r.SEGP = rowwin_segp(-e.p, e.k, Cin);
-            r.s_in = e.s; r.off_y = -e.p;
-            r.e_off = -e.p * Cin - rowwin_lead(-e.p, Cin);
-            r.w_a = ((r.e_off % 4) + 4) % 4;
-            r.MB = rowwin_mb(B, p.Ho, p.Wo);
-            r.WLEN = round_up(r.s_in * Cin * (64 * r.MB - 1) + r.w_a + r.SEGP, 4);
-            r.Ho = p.Ho; r.Wo = p.Wo; r.Cs_out = p.Cs_out; r.c_off = 0; r.N = p.N; r.Npad = p.Npad; r.act = 1;
-            if (in_bytes < 0x80000000LL && rowwin_applicable(r)) {
-                if (!tickets_cleared) { r.clear_words = tickets; r.clear_n = SKINNY_MAX_TILES; tickets_cleared = true; }
-                const int rem = p.Wo % 128;
-                if (r.MB == 2 && p.Wo > 128 && rem >= 1 && rem <= 64) {
-                    // 128 k + (1..64) columns: k full tiles, then the rest as ONE 64-pixel tile (second launch; events span both)
-                    RowWinParams t = r;
-                    r.ntile_x = p.Wo / 128;
-                    t.MB = 1; t.ox_base = r.ntile_x * 128; t.ntile_x = 1; t.clear_n = 0;
-                    t.WLEN = round_up(t.s_in * Cin * 63 + t.w_a + t.SEGP, 4);
-                    if (rowwin_applicable(t)) {
-                        HIP_TRY(ctx, launch_conv_rowwin(r, stream, EV_A(0), nullptr));
-                        HIP_TRY(ctx, launch_conv_rowwin(t, stream, nullptr, EV_B(0)));
-                        PROF_NAME(0, "conv_rowwin_kernel<7, 2> + <4, 1> tail");
-                        continue;
-                    }
-                    r.ntile_x = 0;
-                }
-                HIP_TRY(ctx, launch_conv_rowwin(r, stream, EV_A(0), EV_B(0)));
-                PROF_NAME(0, r.MB == 2 ? "conv_rowwin_kernel<7, 2>" : "conv_rowwin_kernel<4, 1>");
-                continue;
-            }
+            const char *kname = nullptr;
+            bool launched = false;
+            const int rc = conv1_rowwin(ctx, pl.conv1_bf16x3, feats, B, H, W, Cin, p.Ho, p.Wo, p.N, p.Npad, buf(B_CONV1), p.Cs_out, 0,
+                                        tickets_cleared ? nullptr : tickets, stream, EV_A(0), EV_B(0), &kname, &launched);
+            if (rc != VSTAB_OK) return rc;
+            if (launched) { tickets_cleared = true; PROF_NAME(0, kname); continue; }
         }
         if (!tickets_cleared) { HIP_TRY(ctx, hipMemsetAsync(tickets, 0, pl.bytes[B_TICKETS], stream)); tickets_cleared = true; }
         if (pl.wino[i]) {       // transform, 16-position GEMM on the MFMA kernel, inverse transform (+ bias, leaky relu)

@@ -232,6 +232,10 @@ bool make_plan(int B, int H, int W, int Cin, Plan &pl, const PlanPin *pin)
         }
         if (p.ksplit > 1) partial_floats = std::max(partial_floats, (size_t)p.ksplit * p.Mmax * p.Npad);
     }
+    // ---- the first layer on the bf16 MFMA with three-piece operands (conv1_bf16x3.hip).  It changes the arithmetic of a sample, so it
+    // is a pinned decision: taken from the filter's geometry and the plan flags alone, never from the batch or the image size
+    pl.conv1_bf16x3 = ref ? ref->conv1_bf16x3
+                          : (!(flags & VSTAB_PLAN_CONV1_FP32) && NET[0].cout == 64 && rowwin_segp(-NET[0].p, NET[0].k, Cin) <= 192);
     // ---- Winograd form of the 3x3 stride-1 stages: a 16-phase 1x1 GEMM over the transformed tiles (winograd_ops.hip)
     size_t wino_v = 0, wino_m = 0;
     for (int i = 0; i < 10; ++i) {
@@ -363,7 +367,7 @@ extern "C" int vstab_set_plan_batch(vstab_ctx *ctx, int batch)
 extern "C" int vstab_set_plan_flags(vstab_ctx *ctx, unsigned flags)
 {
     if (!ctx) return fail(nullptr, VSTAB_E_STATE, "set_plan_flags: ctx is NULL");
-    if (flags & ~(unsigned)(VSTAB_PLAN_NO_SKINNY | VSTAB_PLAN_NO_DUAL | VSTAB_PLAN_NO_TAIL | VSTAB_PLAN_NO_WDEC | VSTAB_PLAN_FORCE_WDEC)) return fail(ctx, VSTAB_E_SHAPE, "set_plan_flags: unknown flag bits 0x%x", flags);
+    if (flags & ~(unsigned)(VSTAB_PLAN_NO_SKINNY | VSTAB_PLAN_NO_DUAL | VSTAB_PLAN_NO_TAIL | VSTAB_PLAN_NO_WDEC | VSTAB_PLAN_FORCE_WDEC | VSTAB_PLAN_CONV1_FP32)) return fail(ctx, VSTAB_E_SHAPE, "set_plan_flags: unknown flag bits 0x%x", flags);
     ctx->plan_flags = flags;
     return VSTAB_OK;
 }

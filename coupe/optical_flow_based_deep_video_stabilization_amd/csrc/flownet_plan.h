@@ -69,6 +69,8 @@ struct Plan {
     vstab::ConvParams cp[N_LAYER];
     vstab::ConvTile tile[N_LAYER];
     bool vec4[N_LAYER];
+    bool conv1_bf16x3;      // the first layer's products as six bf16 piece-products on the bf16 MFMA (conv1_bf16x3.hip) when its row-window
+                            // conditions hold at launch time; false: the fp32 MFMA (VSTAB_PLAN_CONV1_FP32, or a filter the form is not built for)
     bool skinny[N_LAYER];   // few-row layers as weight streams (conv_skinny.hip): tile[i] == TILE_SKINNY, cp[i].ksplit = its own factor
     // Winograd F(2x2,3x3) form of the 3x3 stride-1 encoder stages (cp[i] stays the direct form: host-plan tests, fallback)
     bool wino[10];

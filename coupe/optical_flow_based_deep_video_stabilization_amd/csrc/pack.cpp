@@ -94,6 +94,48 @@ void pack_conv_rowwin(const float *W, const double *scale, int kh, int kw, int c
             }
 }
 
+// fp32 -> bf16 bits, round to nearest even (NaN stays a quiet NaN): what the kernel's conversions do to the inputs
+static inline uint16_t bf16_rne(float x)
+{
+    uint32_t u;
+    std::memcpy(&u, &x, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+static inline float bf16_float(uint16_t b)
+{
+    const uint32_t u = (uint32_t)b << 16;
+    float x;
+    std::memcpy(&x, &u, 4);
+    return x;
+}
+
+// conv1_bf16x3.hip: the row-window K order (lead dummy + kx*cin + ci per filter row, padded to segp) in K-groups of 16, every
+// weight (BatchNorm scale folded in double, rounded to fp32 as in pack_conv_rowwin) split into three bf16 pieces whose sum is the
+// fp32 weight exactly; [kh*segp/16][3 planes][64 columns][16 k] bf16 = the B fragments of v_mfma_f32_32x32x16_bf16 (lane (i,h) of a
+// 32-column block: 8 consecutive k from 8h of column i).  Padding lanes and columns carry zeros.
+void pack_conv1_bf16x3(const float *W, const double *scale, int kh, int kw, int cin, int cout, int lead, int segp, uint16_t *wpk)
+{
+    const int kg = segp / 16;
+    std::memset(wpk, 0, sizeof(uint16_t) * (size_t)kh * kg * 3 * 64 * 16);
+    for (int ky = 0; ky < kh; ++ky)
+        for (int kx = 0; kx < kw; ++kx)
+            for (int ci = 0; ci < cin; ++ci) {
+                const int k = lead + kx * cin + ci;
+                uint16_t *grp = wpk + ((size_t)ky * kg + k / 16) * 3 * 64 * 16;
+                for (int n = 0; n < cout && n < 64; ++n) {
+                    const float w = (float)((double)W[(((size_t)ky * kw + kx) * cin + ci) * cout + n] * scale[n]);
+                    const uint16_t h = bf16_rne(w);
+                    const float r1 = w - bf16_float(h);
+                    const uint16_t m = bf16_rne(r1);
+                    const float r2 = r1 - bf16_float(m);
+                    const uint16_t l = bf16_rne(r2);
+                    const size_t at = (size_t)n * 16 + (k & 15);
+                    grp[at] = h; grp[64 * 16 + at] = m; grp[2 * 64 * 16 + at] = l;
+                }
+            }
+}
+
 void pack_deconv(const float *W, const double *scale, int cin, int cs_in, int cout, int npad, float *wpk)
 {
     const KLayout L = klayout_deconv(cs_in);

@@ -225,6 +225,15 @@ inline int rowwin_segp(int off_x, int kw, int cs) { return round_up_c(rowwin_lea
 void pack_conv_rowwin(const float *W, const double *scale, int kh, int kw, int cin, int cout, int npad,
                       int lead, int segp, float *wpk);
 
+// The same layer on the bf16 MFMA with every operand split into three bf16 pieces, six piece-products per multiply, fp32
+// accumulation (conv1_bf16x3.hip).  Same RowWinParams (wpk = the planes of pack_conv1_bf16x3), same tiles, window and epilogue.
+bool conv1_bf16x3_applicable(const RowWinParams &p);
+hipError_t conv1_bf16x3_set_attributes();
+hipError_t launch_conv1_bf16x3(const RowWinParams &p, hipStream_t stream, hipEvent_t ev_start = nullptr,
+                               hipEvent_t ev_stop = nullptr);
+// Conv weights W[kh][kw][Cin][Cout] (Cout <= 64) -> [kh*segp/16][3][64][16] bf16: kh*segp/16 * 3072 uint16
+void pack_conv1_bf16x3(const float *W, const double *scale, int kh, int kw, int cin, int cout, int lead, int segp, uint16_t *wpk);
+
 // ---------------------------------------------------------------------------------
 // Winograd F(2x2,3x3) transforms around the MFMA kernel (winograd_ops.hip) and the weight transform + packing:
 // U_xi = (G g G^T)_xi with the BatchNorm scale folded in, 16 blocks of a 1x1-conv operand (klayout_run(1,1,cin)).

@@ -519,7 +519,15 @@ VSTAB_API int vstab_warp_perspective_u8(const uint8_t *src, int B, int sh, int s
 #define VSTAB_PLAN_NO_TAIL 4u      /* vstab_stabilise_originalsize: predict_flow2's gather and the glue + warp as two launches (bit-identical) */
 #define VSTAB_PLAN_NO_WDEC 8u      /* transposed convolutions as four direct sub-pixel phases, never in Winograd F(2x2,2x2) form (round 6) */
 #define VSTAB_PLAN_FORCE_WDEC 16u  /* deconv4 / deconv3 in Winograd F(2x2,2x2) form whatever their size (tests: small shapes) */
+#define VSTAB_PLAN_CONV1_FP32 32u  /* conv1 on the fp32 MFMA (conv_rowwin.hip) instead of six bf16 piece-products per multiply on the bf16 MFMA
+                                    * (conv1_bf16x3.hip: fp32 operands split into three bf16 pieces, fp32 accumulation); the A side of its A/B */
 VSTAB_API int vstab_set_plan_flags(vstab_ctx *ctx, unsigned flags);
+
+/* conv1 alone, in the form this context's plan flags choose (six bf16 piece-products on the bf16 MFMA, or VSTAB_PLAN_CONV1_FP32's fp32 MFMA):
+ * feats [B][H][W][Cin] -> channels c_off .. c_off + 64 of out [B][Ho][Wo][cs_out]; the other channels of a pixel are not touched.
+ * VSTAB_E_SHAPE when the geometry is one the row-window kernels do not take (the forward then runs the generic kernel). */
+VSTAB_API int vstab_conv1_forward(vstab_ctx *ctx, const float *feats, int B, int H, int W, int Cin, float *out, int cs_out, int c_off,
+                                  void *stream);
 
 /* ---- measurement support.  With profiling enabled every conv-like launch of
  * vstab_flownets_forward (15 per forward: encoder stages 1..6_1, deconv5..2, predict2 tap
