@@ -4,7 +4,8 @@ over HIP events (>= 20 timed calls after warm-up), algorithmic bytes (12 read + 
 of 8 TB/s.  Prints one JSON line.  AffineTransformer with the bilinear sampler is the existing kernel, the yardstick.
 --backward adds the gradients of the affine bilinear transformer at the same shape (rows "backward"): d img (four global atomics
 per pixel-channel), d theta, both together, and torch's own grid_sample backward (NCHW, bilinear, zeros, align_corners=True) for scale -- an independent implementation of a comparable op,
-not a gate.
+not a gate; and the gradients of ElasticTransformer (g = 4, bilinear) at the same shape (rows "elastic_g4_*": time and algorithmic
+bytes only -- the thin-plate spline is bound by logf, not by HBM, so a fraction of 8 TB/s would say nothing).
 --volume adds the 3-D volume transformer (rows "volume"): AffineVolumeTransformer at B = 4, 256^3, C = 1 under an oblique rotation of
 about 10 degrees plus a small shift -- forward by theta, d vol, d theta, both gradients -- with torch's 5-D grid_sample (bilinear,
 zeros, align_corners=True) forward timed interleaved for scale.  The forward counts 8 algorithmic bytes per output voxel."""
@@ -74,8 +75,18 @@ def backward_rows(img, th6, out_size, iters, warmup):
     us = time_interleaved(fns, iters, warmup)
     nbytes = {"d_img": 36.0, "d_theta": 24.0, "both": 48.0,
               "torch_grid_sample_backward": 48.0 + 16.0}                      # + the grid read and its gradient written
-    return {k: {"us": round(v, 1), "alg_bytes": int(nbytes[k] * npix), "frac_8TBs": round(nbytes[k] * npix / (v * 1e-6) / 1e9 / PEAK_GBS, 3)}
+    rows = {k: {"us": round(v, 1), "alg_bytes": int(nbytes[k] * npix), "frac_8TBs": round(nbytes[k] * npix / (v * 1e-6) / 1e9 / PEAK_GBS, 3)}
             for k, v in us.items()}
+    # ElasticTransformer, g = 4: the same bytes per pixel as the affine rows (theta, linv_t and the partial rows are noise)
+    tps = st.ElasticTransformer(out_size, 4)
+    th_tps = ((torch.rand(B, tps.param_dim, generator=torch.Generator().manual_seed(4)) - 0.5) * 0.1).cuda()
+
+    def run_tps(need_img, need_theta):
+        return lambda: training.st_elastic_transform_backward(img, th_tps, dout, out_size, 4, tps.L_inv, need_img=need_img, need_theta=need_theta)
+
+    us = time_interleaved({"d_img": run_tps(True, False), "d_theta": run_tps(False, True), "both": run_tps(True, True)}, iters, warmup)
+    rows.update({f"elastic_g4_{k}": {"us": round(v, 1), "alg_bytes": int(nbytes[k] * npix)} for k, v in us.items()})
+    return rows
 
 
 def volume_rows(iters, warmup, B=4, n=256):
@@ -118,7 +129,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", default="", help="comma-separated variant names (default: all)")
-    ap.add_argument("--backward", action="store_true", help="add the affine bilinear transformer's gradients (rows 'backward')")
+    ap.add_argument("--backward", action="store_true", help="add the gradients of the affine and the elastic (g = 4) bilinear transformers (rows 'backward')")
     ap.add_argument("--volume", action="store_true", help="add the 3-D volume transformer at B = 4, 256^3, C = 1 (rows 'volume')")
     args = ap.parse_args()
     if args.iters < 20:

@@ -409,6 +409,43 @@ extern "C" int vstab_st_bilinear_interp_backward(const float *img, int B, int H,
     return VSTAB_OK;
 }
 
+// ---- ElasticTransformer: the coordinates the forward samples at, and the backward of its bilinear sampler
+static bool tps_g_ok(int g) { return g >= 2 && g <= VSTAB_TPS_GMAX; }
+
+extern "C" int vstab_st_elastic_coords(const float *theta, int B, int g, const float *linv_t, int oh, int ow, float *x_out, float *y_out,
+                                       void *stream)
+{
+    if (!theta || !linv_t || !x_out || !y_out) return fail(nullptr, VSTAB_E_STATE, "st_elastic_coords: NULL buffer");
+    if (!stx_shape_ok(B, 1, 1, 1, oh, ow) || !tps_g_ok(g))
+        return fail(nullptr, VSTAB_E_SHAPE, "st_elastic_coords: bad shape (B <= 65535, grid side must be in [2, %d])", VSTAB_TPS_GMAX);
+    HIP_TRY(nullptr, launch_st_elastic_coords(theta, B, g, linv_t, oh, ow, x_out, y_out, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" size_t vstab_st_elastic_transform_backward_workspace_bytes(int B, int H, int W, int C, int g, int oh, int ow)
+{
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || !tps_g_ok(g)) return 0;
+    return st_elastic_backward_ws_bytes(B, H, W, C, g, oh, ow);
+}
+
+extern "C" int vstab_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
+                                                   const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
+                                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!img || !theta || !linv_t || !dout) return fail(nullptr, VSTAB_E_STATE, "st_elastic_transform_backward: NULL buffer");
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL || !tps_g_ok(g))
+        return fail(nullptr, VSTAB_E_SHAPE, "st_elastic_transform_backward: bad shape (B <= 65535, grid side must be in [2, %d])", VSTAB_TPS_GMAX);
+    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "st_elastic_transform_backward: d_img and d_theta are both NULL");
+    if (d_theta) {
+        const size_t need = st_elastic_backward_ws_bytes(B, H, W, C, g, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "st_elastic_transform_backward: workspace needs %zu bytes", need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "st_elastic_transform_backward: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(nullptr, launch_st_elastic_transform_backward(img, B, H, W, C, theta, g, linv_t, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
+                                                          (double *)workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
 // ---- the 3-D volume transformer (sampler3d_ops.hip).  The shape is judged before the pointers: a shape outside the contract is
 // VSTAB_E_SHAPE whatever else is wrong with the call.
 static bool st3d_shape_ok(int B, int D, int H, int W, int C, int od, int oh, int ow, int edge)

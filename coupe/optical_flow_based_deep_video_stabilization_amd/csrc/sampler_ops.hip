@@ -3,9 +3,10 @@
 // ONE family of kernels, templated on where a pixel's source coordinates come from (XS_*) and on the sampler (XI_*):
 // st3_tile_kernel for 3-channel frames (tile3.h's skeleton: 2-D tiles, 3-dword tap gathers, rows leaving as 16-byte stores),
 // st_pixel_kernel (one thread per pixel) for other channel counts.  Each piece of the reference's arithmetic is one device
-// function (st_axis in st_axis.h, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta and
-// explicit-coordinate sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel, at the end of the file) that calls the same
-// functions; its d img is summed by float atomics and depends on their arrival order in its last bits, its d theta is reproducible.
+// function (st_axis in st_axis.h, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta,
+// explicit-coordinate and thin-plate-spline sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel and, for the spline,
+// st3_tile_tps_bwd_kernel / st_pixel_tps_bwd_kernel, at the end of the file) that calls the same functions; its d img is summed by
+// float atomics and depends on their arrival order in its last bits, its d theta is reproducible.
 // -ffp-contract=off keeps the weight arithmetic the reference's op-by-op fp32 sequence.
 #include "vstab_internal.h"
 #include "hbm_profile.h"
@@ -209,6 +210,15 @@ __device__ __forceinline__ void st_tps_coeff(const StSrc &S, int n, float *cf)
     }
 }
 
+// U_func (ST:162-172) of grid point (xt, yt) against the control point (cx, cy): r^2 ln r^2, log 0 = -inf replaced by 0 (ST:166-168).
+// The forward's per-pixel loop and the backward's column loop both call it: one fp32 sequence, one set of bits.
+__device__ __forceinline__ float st_tps_U(float xt, float yt, float cx, float cy)
+{
+    const float dx = xt - cx, dy = yt - cy;
+    const float r2 = dx * dx + dy * dy;
+    return r2 == 0.0f ? 0.0f : r2 * logf(r2);
+}
+
 // Affine / ProjectiveTransformer at grid point (xt, yt): T_g = theta . (x_t, y_t, 1), the projective one divided by safe_z (ST:598).
 // xh, yh, zs (1 for the affine one) are the values before the division, which the backward's chain rule needs.
 __device__ __forceinline__ void st_theta_coords(const float *th, int tdim, float xt, float yt, float &xh, float &yh, float &zs, float &xs, float &ys)
@@ -240,9 +250,7 @@ __device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const
         float ay = (cf[K3] * xt + cf[K3 + 1] * yt) + cf[K3 + 2];
         const float *cpx = cf + 2 * K3, *cpy = cpx + K;
         for (int k = 0; k < K; ++k) {
-            const float dx = xt - cpx[k], dy = yt - cpy[k];
-            const float r2 = dx * dx + dy * dy;
-            const float U = r2 == 0.0f ? 0.0f : r2 * logf(r2);          // log 0 = -inf is replaced by 0 (ST:166-168)
+            const float U = st_tps_U(xt, yt, cpx[k], cpy[k]);
             ax = ax + cf[3 + k] * U;
             ay = ay + cf[K3 + 3 + k] * U;
         }
@@ -469,6 +477,12 @@ __global__ __launch_bounds__(256) void st3_tile_kernel(const float *__restrict__
     if (STAGE) tile.template store_rows<3>(lds, out, FH, FW);          // FW % 4 == 0 (host): a tile row is TW*12 bytes from a 16-byte aligned address
 }
 
+// a source's fp32 linspace steps 2/(n-1), divided once on the host (the same IEEE quotient lin11 computes)
+static void st_steps(StSrc &S)
+{
+    S.sx = S.gw > 1 ? 2.0f / (float)(S.gw - 1) : 0.0f; S.sy = S.gh > 1 ? 2.0f / (float)(S.gh - 1) : 0.0f;
+}
+
 // Picks the kernel of a launch: the tile kernel for 3-channel frames of a shape that is its own, the pixel kernel otherwise.
 // `slot` / `px_bytes`: the launch_timed slot and algorithmic bytes per output pixel of the tile launch (slot < 0: not timed).
 template <int SRC, int INTERP>
@@ -476,7 +490,7 @@ static hipError_t launch_st(int slot, double px_bytes, const float *img, int B, 
                             hipStream_t stream)
 {
     S.B = B;
-    S.sx = S.gw > 1 ? 2.0f / (float)(S.gw - 1) : 0.0f; S.sy = S.gh > 1 ? 2.0f / (float)(S.gh - 1) : 0.0f;
+    st_steps(S);
     S.dsx = S.gw > 1 ? 2.0 / (double)(S.gw - 1) : 0.0; S.dsy = S.gh > 1 ? 2.0 / (double)(S.gh - 1) : 0.0;
     int tx, ty;
     dim3 grid;
@@ -605,6 +619,42 @@ hipError_t launch_st_elastic_transform(const float *img, int B, int H, int W, in
     return launch_st<XS_TPS, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
 }
 
+// ElasticTransformer's normalised source coordinates themselves (the x_s_flat, y_s_flat of ST:140-158), [B*oh*ow] each: st_tps_coeff
+// and st_coords<XS_TPS>, called as the sampling kernels call them, so these are the values the forward samples at bit for bit.
+// st_pixel_kernel's layout: workgroups [n * bps, (n + 1) * bps) belong to sample n.
+__global__ __launch_bounds__(256) void st_tps_coords_kernel(StSrc S, float *__restrict__ x_out, float *__restrict__ y_out, int FH, int FW, unsigned bps)
+{
+    __shared__ float cf[2 * (ST_TPS_KMAX + 3) + 2 * ST_TPS_KMAX];
+    const int n = (int)(blockIdx.x / bps);
+    st_tps_coeff(S, n, cf);
+    __syncthreads();
+    const long long p = (long long)(blockIdx.x - (unsigned)n * bps) * 256 + threadIdx.x;
+    if (p >= (long long)FH * FW) return;
+    const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+    float xs, ys;
+    st_coords<XS_TPS>(S, nullptr, cf, n, fx, fy, xs, ys);
+    x_out[(long long)n * FH * FW + p] = xs;
+    y_out[(long long)n * FH * FW + p] = ys;
+}
+
+static StSrc st_elastic_src(int B, const float *theta, int g, const float *linv_t, int oh, int ow)
+{
+    StSrc S = st_plain(oh, ow);
+    S.theta = theta; S.g = g; S.linv_t = linv_t; S.B = B;
+    st_steps(S);
+    return S;
+}
+
+hipError_t launch_st_elastic_coords(const float *theta, int B, int g, const float *linv_t, int oh, int ow, float *x_out, float *y_out,
+                                    hipStream_t stream)
+{
+    const long long bps = ((long long)oh * ow + 255) / 256;
+    if (bps * B >= (1ll << 31)) return hipErrorInvalidValue;
+    st_tps_coords_kernel<<<dim3((unsigned)(bps * B)), dim3(256), 0, stream>>>(st_elastic_src(B, theta, g, linv_t, oh, ow), x_out, y_out, oh, ow,
+                                                                              (unsigned)bps);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------
 // Backward of the BILINEAR sampler for the theta (affine / projective) and explicit-coordinate sources: what TensorFlow's autodiff
 // gives for ST:902-964 and ST:438-452 / 578-608.  The coordinates, taps and weights are the forward's (st_theta_coords, st_axis,
@@ -648,6 +698,62 @@ struct StBwd {
     double *part;                  // XS_THETA [workgroups][8] (null: d theta not wanted)
 };
 
+// The bilinear backward of ONE output pixel sampled at (xs, ys), stated once for every source of coordinates.  b, di: the sample's
+// image and its gradient; g: the pixel's dout.  DIMG: w_k * dout added to the four taps (none to a tap on the zero border).  DCOORD:
+// gxn, gyn = d out / d (xs, ys) summed over the channels times dout, through the clip and the pixel scaling (0 otherwise).
+// Any channel count:
+template <bool DIMG, bool DCOORD>
+__device__ __forceinline__ void st_bwd_point(const float *__restrict__ b, float *di, const float *__restrict__ g, int H, int W, int C, float xs,
+                                             float ys, float &gxn, float &gyn)
+{
+    const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
+    const Taps t = st_taps(X, Y);
+    const long long i00 = ((long long)t.ya * W + t.xa) * C, i01 = ((long long)t.ya * W + t.xb) * C;
+    const long long i10 = ((long long)t.yb * W + t.xa) * C, i11 = ((long long)t.yb * W + t.xb) * C;
+    const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+    float gx = 0.f, gy = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float gc = g[c];
+        if (DCOORD) st_slope(X, Y, v00 ? b[i00 + c] : 0.f, v01 ? b[i01 + c] : 0.f, v10 ? b[i10 + c] : 0.f, v11 ? b[i11 + c] : 0.f, gc, gx, gy);
+        if (DIMG) {
+            if (v00) atomicAdd(di + i00 + c, t.w0 * gc);
+            if (v01) atomicAdd(di + i01 + c, t.w1 * gc);
+            if (v10) atomicAdd(di + i10 + c, t.w2 * gc);
+            if (v11) atomicAdd(di + i11 + c, t.w3 * gc);
+        }
+    }
+    gxn = DCOORD ? st_axis_chain(X, gx, W) : 0.0f;
+    gyn = DCOORD ? st_axis_chain(Y, gy, H) : 0.0f;
+}
+
+// 3-channel frames (3 H W < 2^31: host):
+template <bool DIMG, bool DCOORD>
+__device__ __forceinline__ void st3_bwd_point(const rgb3 *b, float *di, const rgb3 g, int H, int W, float xs, float ys, float &gxn, float &gyn)
+{
+    const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
+    const Taps t = st_taps(X, Y);
+    const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+    gxn = gyn = 0.0f;
+    if (DCOORD) {
+        const rgb3 z = {0.f, 0.f, 0.f};
+        const rgb3 I00 = v00 ? b[t.ya * W + t.xa] : z, I01 = v01 ? b[t.ya * W + t.xb] : z;
+        const rgb3 I10 = v10 ? b[t.yb * W + t.xa] : z, I11 = v11 ? b[t.yb * W + t.xb] : z;
+        float gx = 0.f, gy = 0.f;
+        st_slope(X, Y, I00.r, I01.r, I10.r, I11.r, g.r, gx, gy);
+        st_slope(X, Y, I00.g, I01.g, I10.g, I11.g, g.g, gx, gy);
+        st_slope(X, Y, I00.b, I01.b, I10.b, I11.b, g.b, gx, gy);
+        gxn = st_axis_chain(X, gx, W); gyn = st_axis_chain(Y, gy, H);
+    }
+    if (DIMG) {
+        auto add = [&](int y, int x, bool valid, float w) {
+            if (!valid) return;
+            float *q = di + ((long long)y * W + x) * 3;
+            atomicAdd(q, w * g.r); atomicAdd(q + 1, w * g.g); atomicAdd(q + 2, w * g.b);
+        };
+        add(t.ya, t.xa, v00, t.w0); add(t.ya, t.xb, v01, t.w1); add(t.yb, t.xa, v10, t.w2); add(t.yb, t.xb, v11, t.w3);
+    }
+}
+
 // any channel count, one thread per pixel (st_pixel_kernel's layout); d img the plain way
 template <int SRC, bool DIMG, bool DCOORD>
 __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restrict__ img, int H, int W, int C, StSrc S, StBwd G, int FH, int FW, unsigned bps)
@@ -665,27 +771,10 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
         const float xt = st_grid_t(fx, S.sx), yt = st_grid_t(fy, S.sy);
         if (SRC == XS_THETA) st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
         else st_coords<SRC>(S, th, nullptr, n, fx, fy, xs, ys);
-        const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
-        const Taps t = st_taps(X, Y);
-        const long long i00 = ((long long)t.ya * W + t.xa) * C, i01 = ((long long)t.ya * W + t.xb) * C;
-        const long long i10 = ((long long)t.yb * W + t.xa) * C, i11 = ((long long)t.yb * W + t.xb) * C;
-        const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
-        const float *__restrict__ b = img + (long long)n * H * W * C;
-        const float *__restrict__ g = G.dout + ((long long)n * FH * FW + p) * C;
-        float *di = DIMG ? G.d_img + (long long)n * H * W * C : nullptr;
-        float gx = 0.f, gy = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float gc = g[c];
-            if (DCOORD) st_slope(X, Y, v00 ? b[i00 + c] : 0.f, v01 ? b[i01 + c] : 0.f, v10 ? b[i10 + c] : 0.f, v11 ? b[i11 + c] : 0.f, gc, gx, gy);
-            if (DIMG) {
-                if (v00) atomicAdd(di + i00 + c, t.w0 * gc);
-                if (v01) atomicAdd(di + i01 + c, t.w1 * gc);
-                if (v10) atomicAdd(di + i10 + c, t.w2 * gc);
-                if (v11) atomicAdd(di + i11 + c, t.w3 * gc);
-            }
-        }
+        float gxn, gyn;
+        st_bwd_point<DIMG, DCOORD>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
+                                   G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
         if (DCOORD) {
-            const float gxn = st_axis_chain(X, gx, W), gyn = st_axis_chain(Y, gy, H);
             if (SRC == XS_COORDS) {
                 if (G.d_x) G.d_x[(long long)n * FH * FW + p] = gxn;
                 if (G.d_y) G.d_y[(long long)n * FH * FW + p] = gyn;
@@ -719,34 +808,16 @@ __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restri
         const float xt = st_grid_t(fx, S.sx), yt = st_grid_t(fy, S.sy);
         if (SRC == XS_THETA) st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
         else st_coords<SRC>(S, th, nullptr, n, fx, fy, xs, ys);
-        const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
-        const Taps t = st_taps(X, Y);
-        const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
         const long long po = ((long long)n * FH + fy) * FW + fx;
-        const rgb3 g = reinterpret_cast<const rgb3 *>(G.dout)[po];
+        float gxn, gyn;
+        st3_bwd_point<DIMG, DCOORD>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[po], H, W, xs, ys, gxn, gyn);
         if (DCOORD) {
-            const rgb3 z = {0.f, 0.f, 0.f};
-            const rgb3 I00 = v00 ? b[t.ya * W + t.xa] : z, I01 = v01 ? b[t.ya * W + t.xb] : z;
-            const rgb3 I10 = v10 ? b[t.yb * W + t.xa] : z, I11 = v11 ? b[t.yb * W + t.xb] : z;
-            float gx = 0.f, gy = 0.f;
-            st_slope(X, Y, I00.r, I01.r, I10.r, I11.r, g.r, gx, gy);
-            st_slope(X, Y, I00.g, I01.g, I10.g, I11.g, g.g, gx, gy);
-            st_slope(X, Y, I00.b, I01.b, I10.b, I11.b, g.b, gx, gy);
-            const float gxn = st_axis_chain(X, gx, W), gyn = st_axis_chain(Y, gy, H);
             if (SRC == XS_COORDS) {
                 if (G.d_x) G.d_x[po] = gxn;
                 if (G.d_y) G.d_y[po] = gyn;
             } else {
                 st_theta_accum(acc, S.tdim, gxn, gyn, xt, yt, xh, yh, zs);
             }
-        }
-        if (DIMG) {
-            auto add = [&](int y, int x, bool valid, float w) {
-                if (!valid) return;
-                float *q = di + ((long long)y * W + x) * 3;
-                atomicAdd(q, w * g.r); atomicAdd(q + 1, w * g.g); atomicAdd(q + 2, w * g.b);
-            };
-            add(t.ya, t.xa, v00, t.w0); add(t.ya, t.xb, v01, t.w1); add(t.yb, t.xa, v10, t.w2); add(t.yb, t.xb, v11, t.w3);
         }
     }
     if (DCOORD && SRC == XS_THETA) {
@@ -780,7 +851,7 @@ template <int SRC>
 static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, StSrc S, StBwd G, int FH, int FW, hipStream_t stream)
 {
     S.B = B;
-    S.sx = S.gw > 1 ? 2.0f / (float)(S.gw - 1) : 0.0f; S.sy = S.gh > 1 ? 2.0f / (float)(S.gh - 1) : 0.0f;
+    st_steps(S);
     const bool dimg = G.d_img != nullptr, dcoord = SRC == XS_THETA ? G.part != nullptr : (G.d_x || G.d_y);
     int tx, ty;
     dim3 grid;
@@ -834,6 +905,218 @@ hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int 
     S.x = x; S.y = y;
     StBwd G{dout, d_img, d_x, d_y, nullptr};
     return launch_st_bwd<XS_COORDS>(img, B, H, W, C, S, G, oh, ow, stream);
+}
+
+// ---------------------------------------------------------------------------------
+// Backward of ElasticTransformer.transform (thin-plate spline, BILINEAR sampler).  The coefficients go into LDS through st_tps_coeff
+// and the coordinates come from st_coords<XS_TPS>, as in the forward, so every tap decision is the forward's; a pixel's d img
+// scatter and its gxn, gyn are st_bwd_point / st3_bwd_point, as for the other sources.
+//   d theta  U_k depends on the grid alone, so with R = [x_t, y_t, 1, U_1..U_K]: d cf[r][j] = sum over the pixels of g_r R_j, 2 (K + 3)
+//            sums per sample, then d theta[n, r K + k] = sum_j d cf[r][j] linv_t[k][j].  Products and sums in double, fp32 once.
+//   layout   K + 3 reaches 259, so there are no per-thread accumulator arrays and no partial row per tile: sample n is walked by `wps`
+//            workgroups (st_tps_bwd_plan), workgroup w taking the steps (tiles, or runs of 256 pixels) [w T / wps, (w + 1) T / wps)
+//            in order.  A step: every thread does its pixels and stages (gxn, gyn, x_t, y_t) in LDS; then thread t OWNS control
+//            point t % K and slice t / K of the staged pixels (256 / K slices) and adds g_r U_k into two doubles of its own, U_k
+//            evaluated again by st_tps_U from the staged x_t, y_t (the forward's bits).  A column's sum never crosses lanes until
+//            the workgroup is done: the slices are then added in slice order through LDS.  The three affine columns go per pixel
+//            into st_theta_accum's six doubles and through st_theta_reduce (shuffles, then the four waves in order).  One partial
+//            row [6 + 2 K] per workgroup: (gx x_t, gx y_t, gx, gy x_t, gy y_t, gy), the K x columns, the K y columns.
+//            st_tps_theta_final_kernel adds a sample's rows in row order and applies linv_t.  No atomics: bit-reproducible.
+// ---------------------------------------------------------------------------------
+constexpr int ST_TPS_WG_TOTAL = 1024, ST_TPS_WPS_MIN = 16;      // workgroups per sample: max(16, 1024 / B), at most one per step
+
+struct StTpsBwd {
+    const float *dout;             // [B, FH, FW, C]
+    float *d_img;                  // [B, H, W, C], added to (null: not wanted)
+    double *part;                  // [B * wps][6 + 2 K] (null: d theta not wanted)
+    int wps;
+};
+
+template <int P>                   // P pixels per step
+struct StTpsLds {
+    float cf[2 * (ST_TPS_KMAX + 3) + 2 * ST_TPS_KMAX];          // st_tps_coeff: coefficients, control points
+    f32x4 px[P];                                                 // a step's pixels: gxn, gyn, x_t, y_t (identical addresses broadcast)
+    double col[2][256], red[4][6];
+};
+
+// the staged pixels' share of this thread's column: control point k = t % K, pixels sl, sl + nsl, ... for slice sl = t / K
+template <int P>
+__device__ __forceinline__ void st_tps_columns(const f32x4 *px, const float *cf, int K, double &ax, double &ay)
+{
+    const int nsl = 256 / K, k = (int)threadIdx.x % K, sl = (int)threadIdx.x / K;
+    if (sl >= nsl) return;
+    const float cx = cf[2 * (K + 3) + k], cy = cf[2 * (K + 3) + K + k];
+    for (int p = sl; p < P; p += nsl) {
+        const f32x4 v = px[p];
+        if (v.x == 0.0f && v.y == 0.0f) continue;                // outside the clip, or beyond the output
+        const double U = (double)st_tps_U(v.z, v.w, cx, cy);
+        ax += (double)v.x * U;
+        ay += (double)v.y * U;
+    }
+}
+
+// a workgroup's sums -> its partial row
+template <int P>
+__device__ __forceinline__ void st_tps_part(StTpsLds<P> &L, double *acc, double ax, double ay, int K, double *__restrict__ row)
+{
+    st_theta_reduce<6>(acc, L.red, row);
+    L.col[0][threadIdx.x] = ax; L.col[1][threadIdx.x] = ay;      // a thread without a slice holds zeros
+    __syncthreads();
+    if ((int)threadIdx.x < K) {
+        double sx = 0.0, sy = 0.0;
+        for (int sl = 0; sl < 256 / K; ++sl) { sx += L.col[0][sl * K + threadIdx.x]; sy += L.col[1][sl * K + threadIdx.x]; }
+        row[6 + threadIdx.x] = sx; row[6 + K + threadIdx.x] = sy;
+    }
+}
+
+// any channel count: a step is a run of 256 pixels, one per thread
+template <bool DIMG, bool DTHETA>
+__global__ __launch_bounds__(256) void st_pixel_tps_bwd_kernel(const float *__restrict__ img, int H, int W, int C, StSrc S, StTpsBwd G, int FH, int FW,
+                                                               int steps)
+{
+    __shared__ StTpsLds<256> L;
+    const int n = (int)blockIdx.x / G.wps, w = (int)blockIdx.x - n * G.wps, K = S.g * S.g;
+    st_tps_coeff(S, n, L.cf);
+    __syncthreads();
+    const int s0 = (int)((long long)w * steps / G.wps), s1 = (int)((long long)(w + 1) * steps / G.wps);
+    double acc[6] = {0, 0, 0, 0, 0, 0}, ax = 0.0, ay = 0.0;
+    for (int s = s0; s < s1; ++s) {
+        const long long p = (long long)s * 256 + threadIdx.x;
+        float gxn = 0.f, gyn = 0.f, xt = 0.f, yt = 0.f;
+        if (p < (long long)FH * FW) {
+            const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+            xt = st_grid_t(fx, S.sx); yt = st_grid_t(fy, S.sy);
+            float xs, ys;
+            st_coords<XS_TPS>(S, nullptr, L.cf, n, fx, fy, xs, ys);
+            st_bwd_point<DIMG, DTHETA>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
+                                       G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
+            if (DTHETA) st_theta_accum(acc, 6, gxn, gyn, xt, yt, 0.f, 0.f, 1.f);
+        }
+        if (DTHETA) {
+            L.px[threadIdx.x] = f32x4{gxn, gyn, xt, yt};
+            __syncthreads();
+            st_tps_columns<256>(L.px, L.cf, K, ax, ay);
+            __syncthreads();
+        }
+    }
+    if (DTHETA) st_tps_part(L, acc, ax, ay, K, G.part + (long long)blockIdx.x * (6 + 2 * K));
+}
+
+// 3-channel frames: a step is a tile of the tile skeleton (a wave instruction works on a 4 x 16 patch)
+template <bool DIMG, bool DTHETA>
+__global__ __launch_bounds__(256) void st3_tile_tps_bwd_kernel(const float *__restrict__ img, int H, int W, StSrc S, StTpsBwd G, int FH, int FW,
+                                                               int tiles_x, int tiles_y)
+{
+    constexpr int PPT = StTile::PPT, P = StTile::TH * StTile::TW;
+    __shared__ StTpsLds<P> L;
+    const int n = (int)blockIdx.x / G.wps, w = (int)blockIdx.x - n * G.wps, K = S.g * S.g, steps = tiles_x * tiles_y;
+    st_tps_coeff(S, n, L.cf);
+    __syncthreads();
+    StTile tile(tiles_x, tiles_y, false);
+    const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + (long long)n * H * W;     // 3 B H W < 2^31 (host)
+    float *di = DIMG ? G.d_img + (long long)n * H * W * 3 : nullptr;
+    const int s0 = (int)((long long)w * steps / G.wps), s1 = (int)((long long)(w + 1) * steps / G.wps);
+    double acc[6] = {0, 0, 0, 0, 0, 0}, ax = 0.0, ay = 0.0;
+    for (int s = s0; s < s1; ++s) {
+        tile.seat(n, s, tiles_x);
+#pragma unroll
+        for (int j = 0; j < PPT; ++j) {
+            float gxn = 0.f, gyn = 0.f, xt = 0.f, yt = 0.f;
+            if (tile.y(j) < FH && tile.x(j) < FW) {
+                const int fy = tile.y(j), fx = tile.x(j);
+                xt = st_grid_t(fx, S.sx); yt = st_grid_t(fy, S.sy);
+                float xs, ys;
+                st_coords<XS_TPS>(S, nullptr, L.cf, n, fx, fy, xs, ys);
+                const long long po = ((long long)n * FH + fy) * FW + fx;
+                st3_bwd_point<DIMG, DTHETA>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[po], H, W, xs, ys, gxn, gyn);
+                if (DTHETA) st_theta_accum(acc, 6, gxn, gyn, xt, yt, 0.f, 0.f, 1.f);
+            }
+            if (DTHETA) L.px[tile.staged(j)] = f32x4{gxn, gyn, xt, yt};
+        }
+        if (DTHETA) {
+            __syncthreads();
+            st_tps_columns<P>(L.px, L.cf, K, ax, ay);
+            __syncthreads();
+        }
+    }
+    if (DTHETA) st_tps_part(L, acc, ax, ay, K, G.part + (long long)blockIdx.x * (6 + 2 * K));
+}
+
+// d theta[n, r K + k] = sum_j d cf[r][j] linv_t[k][j] in double: sample n's `wps` partial rows added in row order, a thread per column,
+// into LDS; then a thread per offset, the three affine products and the K others in j order; rounded to fp32 once
+__global__ __launch_bounds__(256) void st_tps_theta_final_kernel(const double *__restrict__ part, int wps, int K, const float *__restrict__ linv_t,
+                                                                 float *__restrict__ d_theta)
+{
+    __shared__ double dcf[6 + 2 * ST_TPS_KMAX];
+    const int n = blockIdx.x, RW = 6 + 2 * K;
+    for (int c = threadIdx.x; c < RW; c += 256) {
+        double s = 0.0;
+        for (int w = 0; w < wps; ++w) s += part[((long long)n * wps + w) * RW + c];
+        dcf[c] = s;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 2 * K; e += 256) {
+        const int r = e / K, k = e - r * K;
+        const float *lk = linv_t + (long long)k * (K + 3);
+        double s = (dcf[3 * r] * (double)lk[0] + dcf[3 * r + 1] * (double)lk[1]) + dcf[3 * r + 2] * (double)lk[2];
+        for (int j = 0; j < K; ++j) s += dcf[6 + r * K + j] * (double)lk[3 + j];
+        d_theta[(long long)n * 2 * K + e] = (float)s;
+    }
+}
+
+// the walking launch of this shape: steps per sample (st_bwd_plan's tiles, or runs of 256 pixels), workgroups per sample, and whether
+// it is the tile kernel's
+static bool st_tps_bwd_plan(int B, int H, int W, int C, int FH, int FW, int &tx, int &ty, long long &steps, int &wps)
+{
+    dim3 grid;
+    const bool tiled = st_bwd_plan(B, H, W, C, FH, FW, tx, ty, grid, steps);
+    wps = (int)std::min<long long>(steps, std::max(ST_TPS_WPS_MIN, ST_TPS_WG_TOTAL / B));
+    return tiled;
+}
+
+// B * wps rows of 2 (K + 3) doubles with wps = min(steps, max(16, 1024 / B)): whatever the frame size, at most
+// max(1024, 16 B) * 2 (K + 3) * 8 bytes -- 4 MiB at K = 256 up to B = 64
+size_t st_elastic_backward_ws_bytes(int B, int H, int W, int C, int g, int oh, int ow)
+{
+    int tx, ty, wps;
+    long long steps;
+    st_tps_bwd_plan(B, H, W, C, oh, ow, tx, ty, steps, wps);
+    return (size_t)B * wps * (6 + 2 * g * g) * sizeof(double);
+}
+
+hipError_t launch_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
+                                                const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part,
+                                                hipStream_t stream)
+{
+    if (d_img && !accumulate) {
+        const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
+        if (e != hipSuccess) return e;
+    }
+    const StSrc S = st_elastic_src(B, theta, g, linv_t, oh, ow);
+    int tx, ty, wps;
+    long long steps;
+    const bool tiled = st_tps_bwd_plan(B, H, W, C, oh, ow, tx, ty, steps, wps);
+    if (steps >= (1ll << 31)) return hipErrorInvalidValue;
+    const StTpsBwd G{dout, d_img, d_theta ? part : nullptr, wps};
+    const bool dimg = d_img != nullptr, dtheta = d_theta != nullptr;
+    const dim3 grid((unsigned)((long long)B * wps));
+    if (tiled) {
+#define ST_TPS_TILE(D, T) st3_tile_tps_bwd_kernel<D, T><<<grid, dim3(256), 0, stream>>>(img, H, W, S, G, oh, ow, tx, ty)
+        if (dimg && dtheta) ST_TPS_TILE(true, true);
+        else if (dimg) ST_TPS_TILE(true, false);
+        else ST_TPS_TILE(false, true);
+#undef ST_TPS_TILE
+    } else {
+#define ST_TPS_PIXEL(D, T) st_pixel_tps_bwd_kernel<D, T><<<grid, dim3(256), 0, stream>>>(img, H, W, C, S, G, oh, ow, (int)steps)
+        if (dimg && dtheta) ST_TPS_PIXEL(true, true);
+        else if (dimg) ST_TPS_PIXEL(true, false);
+        else ST_TPS_PIXEL(false, true);
+#undef ST_TPS_PIXEL
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !dtheta) return e;
+    st_tps_theta_final_kernel<<<dim3((unsigned)B), dim3(256), 0, stream>>>(part, wps, g * g, linv_t, d_theta);
+    return hipGetLastError();
 }
 
 }  // namespace vstab

@@ -38,6 +38,8 @@ struct Tile3 {
         ty0 = (trem / tiles_x) * TH; tx0 = (trem - (trem / tiles_x) * tiles_x) * TW;
         wave = threadIdx.x >> 6; lane = threadIdx.x & 63;
     }
+    // the workgroup moved to tile t (row-major) of a sample: kernels whose workgroups walk several tiles
+    __device__ __forceinline__ void seat(int sample, int t, int tiles_x) { n = sample; ty0 = (t / tiles_x) * TH; tx0 = (t - (t / tiles_x) * tiles_x) * TW; }
     // pass j of this thread: row / column inside the tile, output pixel, pixel offset in the staging tile
     __device__ __forceinline__ int row(int j) const { return ((j * 4 + wave) / PPR) * WH + lane / WW; }
     __device__ __forceinline__ int col(int j) const { return ((j * 4 + wave) % PPR) * WW + lane % WW; }

@@ -411,6 +411,14 @@ hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, i
                                         int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream);
 hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y, const float *dout, int oh,
                                      int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream);
+// ElasticTransformer: the source coordinates the forward samples at, x_out, y_out [B*oh*ow]; and the backward of its bilinear
+// sampler, conventions as launch_st_transform_backward, `part`: st_elastic_backward_ws_bytes of scratch for the d theta partials
+hipError_t launch_st_elastic_coords(const float *theta, int B, int g, const float *linv_t, int oh, int ow, float *x_out, float *y_out,
+                                    hipStream_t stream);
+size_t st_elastic_backward_ws_bytes(int B, int H, int W, int C, int g, int oh, int ow);
+hipError_t launch_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
+                                                const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part,
+                                                hipStream_t stream);
 
 // The 3-D volume transformer (sampler3d_ops.hip): AffineVolumeTransformer / bilinear_interp3d / _meshgrid3d and their backward.
 // st3d_plan: bricks along each axis and per sample of a [B, od, oh, ow] output; false when the launch grid does not fit.  d_vol

@@ -5,12 +5,12 @@
 `bilinear_interp3d` (:797-899), `bilinear_interp` (:902-964) and `bicubic_interp` (:966-1072).  None of them is executed by the reference's runnable scripts (they are only
 imported, main:4 and cell.py:2); the arithmetic runs in HIP kernels (csrc/sampler_ops.hip, csrc/sampler3d_ops.hip for the volume transformer).
 
-Differentiable (torch.autograd, HIP backward kernels): `AffineTransformer.transform`, `ProjectiveTransformer.transform` and
-`transformer()` with the bilinear sampler, with respect to the image and `theta`, and `bilinear_interp` with respect to the image,
-`x` and `y`; `AffineVolumeTransformer.transform` with respect to the volume and `theta`, `bilinear_interp3d` with respect to the
+Differentiable (torch.autograd, HIP backward kernels): `AffineTransformer.transform`, `ProjectiveTransformer.transform`,
+`ElasticTransformer.transform` and `transformer()` with the bilinear sampler, with respect to the image and `theta` (for the
+elastic one: the control-point offsets), and `bilinear_interp` with respect to the image, `x` and `y`; `AffineVolumeTransformer.transform` with respect to the volume and `theta`, `bilinear_interp3d` with respect to the
 volume, `x`, `y` and `z`.  The gradient of the image or volume is summed by float atomics (last bits may differ between runs); those of `theta`, `x`, `y`,
 `z` are bit-reproducible.  NOT differentiable -- the result has no `grad_fn`, whatever requires grad: `bicubic_interp` and
-`interp_method='bicubic'`, the symmetric-pad transformers, `ElasticTransformer`."""
+`interp_method='bicubic'` (on `ElasticTransformer` too), the symmetric-pad transformers, `ElasticTransformer.transform_coords`."""
 from __future__ import annotations
 
 import ctypes
@@ -282,11 +282,40 @@ def _tps_linv(g):
     return buf
 
 
+def _elastic_transform_call(inp, theta, g, linv_t, oh, ow, interp):
+    B, H, W, Cc = inp.shape
+    out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
+    with torch.cuda.device(inp.device):
+        _lib.check(_lib.lib().vstab_st_elastic_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), g, linv_t.data_ptr(), interp,
+                                                         out.data_ptr(), oh, ow, runtime.stream_ptr()))
+    return out
+
+
+class _ElasticTransformFn(torch.autograd.Function):
+    """ElasticTransformer.transform (bilinear) with its HIP backward (training.st_elastic_transform_backward); theta flat."""
+
+    @staticmethod
+    def forward(ctx, inp, theta, g, linv_t, oh, ow):
+        ctx.save_for_backward(inp, theta, linv_t)
+        ctx.g, ctx.out_size = g, (oh, ow)
+        return _elastic_transform_call(inp, theta, g, linv_t, oh, ow, 0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        inp, theta, linv_t = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_inp, d_theta = training.st_elastic_transform_backward(inp, theta, dout, ctx.out_size, ctx.g, linv_t, need_img=need[0], need_theta=need[1])
+        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None
+
+
 class ElasticTransformer(object):
     """Thin-plate spline transformer (ST:40-224).  param_dim = g, the side of the g x g control grid (linspace(-1,1,g)
     meshgrid, x fastest); theta [B, 2*g*g] = x offsets then y offsets of the control points.  L_inv is computed once at
     construction, in double, and kept on the device as fp32 transpose(L_inv[:,3:]); the kernel computes each sample's
-    coefficients once and U = r^2 ln r^2 per output pixel.  Output [B, oh, ow, C].  Not differentiable."""
+    coefficients once and U = r^2 ln r^2 per output pixel.  Output [B, oh, ow, C].  With the bilinear sampler `transform` is
+    differentiable with respect to the image and theta; with the bicubic one it is not (no `grad_fn`)."""
 
     def __init__(self, out_size, param_dim, name='SpatialElasticTransformer', interp_method='bilinear', **kwargs):
         g = int(param_dim)
@@ -303,23 +332,40 @@ class ElasticTransformer(object):
         runtime._require_gpu()
         self.L_inv = torch.from_numpy(linv).to(torch.device("cuda", torch.cuda.current_device()))
 
+    def _theta(self, theta, B=None):
+        theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
+        if theta.numel() % self.param_dim or (B is not None and theta.numel() != B * self.param_dim) or theta.numel() == 0:
+            raise ValueError(f"theta must have shape [{'B' if B is None else B}, {self.param_dim}]")
+        if self.L_inv.device != theta.device:
+            self.L_inv = self.L_inv.to(theta.device)
+        return theta
+
     def transform(self, inp, theta, forward=True, **kwargs):
         """forward=False gives the same output: the reference computes the same coordinates twice (ST:122-132)."""
         interp = _interp_code(self.interp_method)
         inp = _f32_cuda(inp, "inp")
-        B, H, W, Cc = inp.shape
-        theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
-        if theta.numel() != B * self.param_dim:
-            raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
-        if self.L_inv.device != inp.device:
-            self.L_inv = self.L_inv.to(inp.device)
+        B = inp.shape[0]
+        theta = self._theta(theta, B)
+        if theta.device != inp.device:
+            raise ValueError("theta must be on inp's device")
         oh, ow = self.out_size
-        out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
-        with torch.cuda.device(inp.device):
-            _lib.check(_lib.lib().vstab_st_elastic_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.grid_size,
-                                                             self.L_inv.data_ptr(), interp, out.data_ptr(), oh, ow,
-                                                             runtime.stream_ptr()))
-        return out
+        if interp == 0 and _wants_grad(inp, theta):          # bilinear only: the bicubic sampler has no backward
+            return _ElasticTransformFn.apply(inp, theta, self.grid_size, self.L_inv, oh, ow)
+        return _elastic_transform_call(inp, theta, self.grid_size, self.L_inv, oh, ow, interp)
+
+    def transform_coords(self, theta):
+        """theta [B, 2*g*g] -> (x_s, y_s), each flat [B*oh*ow]: the normalised source coordinates `transform` samples at (the
+        x_s_flat, y_s_flat of ST:140-158), bit for bit -- the same device code computes them; for example the deformation field
+        to draw.  Needs no image.  Forward only: the results carry no graph."""
+        theta = self._theta(theta.detach())
+        B = theta.numel() // self.param_dim
+        oh, ow = self.out_size
+        x_s = torch.empty(B * oh * ow, dtype=torch.float32, device=theta.device)
+        y_s = torch.empty_like(x_s)
+        with torch.cuda.device(theta.device):
+            _lib.check(_lib.lib().vstab_st_elastic_coords(theta.data_ptr(), B, self.grid_size, self.L_inv.data_ptr(), oh, ow,
+                                                          x_s.data_ptr(), y_s.data_ptr(), runtime.stream_ptr()))
+        return x_s, y_s
 
 
 # ---------------------------------------------------------------------------------------------------- the 3-D volume transformer

@@ -2,7 +2,7 @@
 `lossterm` / `masked_MSE` (main:188-210, "main" = main_flownetS_pyramid_noprevloss_dataloader.py), the total-variation
 terms and `loss_main` (main:213-275) with their gradient with respect to every predicted flow; filter / input gradients
 of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and its backward; the resamplers' adjoints; the
-gradients of the bilinear spatial transformers (`st_transform_backward`, `st_bilinear_interp_backward`).
+gradients of the bilinear spatial transformers (`st_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`).
 `train_step.Trainer` strings them into the whole step (forward, loss, backward, Adam: main:184-185, 333-335).
 
 Everything runs in the HIP library (csrc/train_ops.hip); there is no CPU path."""
@@ -257,6 +257,35 @@ def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, nee
                                                  d_img.data_ptr() if need_img else None, 1 if acc else 0,
                                                  d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
                                                  runtime.stream_ptr()))
+    return (d_img if need_img else None), d_theta
+
+
+def st_elastic_transform_backward(img, theta, dout, out_size, g, linv_t, need_img: bool = True, need_theta: bool = True, d_img=None):
+    """Gradients of ElasticTransformer.transform (thin-plate spline, bilinear sampler) for the output gradient dout [B,oh,ow,C]:
+    (d img [B,H,W,C] or None, d theta [B, 2*g*g] or None).  g is the control grid's side, linv_t the transformer's device table
+    [g*g, g*g+3] (ElasticTransformer.L_inv).  d_img, need_img, need_theta as in st_transform_backward; d img is summed by float
+    atomics (its last bits may differ between runs), d theta is bit-reproducible."""
+    need_img = need_img or d_img is not None
+    img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
+    g = int(g)
+    K = g * g
+    theta = theta.contiguous()
+    if not theta.is_cuda or theta.dtype != torch.float32 or theta.numel() != 2 * K * B:
+        raise ValueError(f"theta must be a float32 CUDA tensor [B, {2 * K}]")
+    if not torch.is_tensor(linv_t) or linv_t.device != img.device or linv_t.dtype != torch.float32 or linv_t.numel() != K * (K + 3):
+        raise ValueError(f"linv_t must be a float32 tensor [{K}, {K + 3}] beside img")
+    linv_t = linv_t.contiguous()
+    L = _lib.lib()
+    d_theta, ws, n = None, None, 0
+    if need_theta:
+        d_theta = torch.empty((B, 2 * K), dtype=torch.float32, device=img.device)
+        n = int(L.vstab_st_elastic_transform_backward_workspace_bytes(B, H, W, C, g, oh, ow))
+        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.check(L.vstab_st_elastic_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), g, linv_t.data_ptr(), dout.data_ptr(),
+                                                         oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0,
+                                                         d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
+                                                         runtime.stream_ptr()))
     return (d_img if need_img else None), d_theta
 
 

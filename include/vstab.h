@@ -210,7 +210,8 @@ VSTAB_API int vstab_host_tps_linv(int g, float *linv_t, int cap);
 VSTAB_API int vstab_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                          int interp, float *out, int oh, int ow, void *stream);
 /* ---- backward of the BILINEAR sampler: vstab_st_transform (affine and projective) and vstab_st_bilinear_interp.  These two are the
- * differentiable samplers; bicubic, the symmetric-pad transformers, the thin-plate spline and the homography warps have no backward.
+ * differentiable samplers besides the thin-plate spline (further down); bicubic, the symmetric-pad transformers and the homography
+ * warps have no backward.
  * What TensorFlow's autodiff gives for ST:902-964 / 438-452 / 578-608: floor and the casts have zero derivative, the clip passes the
  * gradient where -1 <= x <= W inclusive (0 outside and for NaN), taps on the zero border receive nothing; coordinates and taps are
  * the forward's fp32 values.  img, B, H, W, C, theta | x, y, oh, ow as in the forward (B <= 65535, B*H*W*C < 2^31);
@@ -230,6 +231,25 @@ VSTAB_API int vstab_st_transform_backward(const float *img, int B, int H, int W,
 VSTAB_API int vstab_st_bilinear_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y,
                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x,
                                                 float *d_y, void *stream);
+/* ---- ElasticTransformer (thin-plate spline): its source coordinates, and the backward of its BILINEAR sampler.  theta, g, linv_t,
+ * oh, ow as in vstab_st_elastic_transform.
+ * vstab_st_elastic_coords: x_out, y_out [B*oh*ow], the normalised source coordinates (x_s_flat, y_s_flat of ST:140-158) that
+ * vstab_st_elastic_transform samples at, bit for bit: the same device code computes them.  Needs no image. */
+VSTAB_API int vstab_st_elastic_coords(const float *theta, int B, int g, const float *linv_t, int oh, int ow, float *x_out, float *y_out,
+                                      void *stream);
+/* vstab_st_elastic_transform_backward: conventions, limits and error codes of vstab_st_transform_backward (d_img by float atomics, zero-
+ * filled on `stream` when accumulate == 0; a NULL output skips that gradient's work, both NULL is VSTAB_E_SHAPE).
+ *   d_theta [B, 2*g*g] (nullable): the gradient of the control-point offsets, x block then y block.  Nothing flows through
+ *           U = r^2 ln r^2 (it depends on the grid alone); the 2 (g*g + 3) coefficient sums over the pixels and their product with
+ *           linv_t are taken in double in a fixed order, without atomics -- two runs are bit-equal -- and rounded to fp32 once.
+ *   workspace: vstab_st_elastic_transform_backward_workspace_bytes(), 8-byte aligned; VSTAB_E_NOMEM when too small, not read when
+ *           d_theta is NULL.  Its size is B * wps * 2 (g*g + 3) * 8 bytes, wps = min(steps, max(16, 1024 / B)) workgroups walking
+ *           each sample, steps = the sample's 16 x 32 output tiles (C == 3) or runs of 256 output pixels: bounded by
+ *           max(1024, 16 B) rows whatever the frame size (about 4 MiB at g = 16 up to B = 64).  0 for a shape outside the contract. */
+VSTAB_API size_t vstab_st_elastic_transform_backward_workspace_bytes(int B, int H, int W, int C, int g, int oh, int ow);
+VSTAB_API int vstab_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g,
+                                                  const float *linv_t, const float *dout, int oh, int ow, float *d_img, int accumulate,
+                                                  float *d_theta, void *workspace, size_t workspace_bytes, void *stream);
 /* ---- the 3-D volume transformer (spatial_transformer.py:227-308, 725-753, 794-899), forward and backward.  vol [B,D,H,W,C];
  * out_size = (od, oh, ow) = (depth, height, width) as the reference passes it.  One thread per output voxel, any C; a workgroup
  * owns a VSTAB_ST3D_BRICK_Z x _Y x _X brick of one sample's output.  64-bit element offsets: the limits are B <= 65535, every

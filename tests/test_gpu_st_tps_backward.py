@@ -1,0 +1,319 @@
+"""ElasticTransformer (thin-plate spline) on the GPU: its coordinate entry point (vstab_st_elastic_coords /
+ElasticTransformer.transform_coords), the gradients of its bilinear sampler (vstab_st_elastic_transform_backward,
+training.st_elastic_transform_backward, spatial_transformer._ElasticTransformFn) and the C ABI's argument checks, against
+tests/st_tps_grad_ref.py.  The reference is fed transform_coords' output -- the coordinates the forward samples at, which the first
+tests establish -- so every floor and clip decision is shared and every element is compared.
+
+Tolerances, with eps = 2^-24 and the reference's count n and absolute companions S per element:
+  coordinates  the bound tests/test_gpu_st_extended.py's _tps_tolerance uses for the kernel's coordinates against
+               st_extended_ref.tps_coords: (K + 16) eps (Tabs + Tcoef) + eps |x|.
+  d img        (n + 2) eps S, with accumulate (n + 3) eps (S + |prior|): tests/test_gpu_st_backward.py's derivation -- the same weights,
+               the same scatter.
+  d theta      (r + C) eps S_theta with r = R_THETA = 17, counted from the sequence the kernels evaluate.  An element is
+               sum_j linv_t[k, j] sum_p g[p] R_j[p]; S_theta is the same sum of |linv_t| S[p] A_j[p] (st_tps_grad_ref's docstring).
+                 7 + C  the per-pixel g: one channel's slope term is 6 roundings, the channel sum at most C - 1, the chain factor
+                        (n - 1) / 2 one product -- test_gpu_st_backward.py's d x, d y count, (7 + C) eps S[p];
+                 9      the fp32 U_k in R_j (the affine columns x_t, y_t, 1 are the reference's own fp32 values: nothing).  dx and dy
+                        are one rounding each, their squares one more each (3 eps relative), the sum one more: r^2 carries 4 eps
+                        relative; that is 4 eps r^2 ABSOLUTE in ln r^2 times r^2 -- the "+ 1" of A = r^2 (|ln r^2| + 1) -- and 4 eps
+                        relative in the factor r^2 of U; logf itself is taken as 2 ulp = 4 eps relative to |ln r^2| ("a few ulp",
+                        inside the 16 eps the forward test grants the whole coordinate sum); the product r^2 * logf is one rounding:
+                        4 eps r^2 + (4 + 4 + 1) eps |U| <= 9 eps A;
+                 1      the final rounding of the sum to fp32 (|d theta| <= S_theta).
+               The products g R_j, the sums over the pixels and over j are taken in double (2^-53: nothing at this scale)."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from coupe.optical_flow_based_deep_video_stabilization_amd import _lib, runtime, spatial_transformer as st, training
+from tests import st_extended_ref as xref
+from tests import st_tps_grad_ref as ref
+from tests.test_gpu_st_backward import _check, _smooth_image
+
+pytestmark = pytest.mark.gpu
+EPS = 2.0 ** -24
+R_THETA = 7 + 9 + 1
+B, H, W, OUT = 2, 48, 64, (40, 56)                     # neither output dimension is a multiple of the 16 x 32 tile
+BIG_OUT = (24, 40)                                     # g = 16
+
+
+@functools.lru_cache(maxsize=None)
+def _tr(g, out=OUT, method='bilinear'):
+    return st.ElasticTransformer(out, g, interp_method=method)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(g, C_, scale=0.15, out=OUT):
+    """(im, theta, dout, the reference's Sampled, its backward) -- computed once per case, shared by the tests, never written to."""
+    gen = torch.Generator().manual_seed(1000 * g + 10 * C_ + int(100 * scale))
+    im = torch.rand(B, H, W, C_, generator=gen)
+    theta = scale * torch.randn(B, 2 * g * g, generator=gen)
+    dout = torch.randn(B, out[0], out[1], C_, generator=gen)
+    tr = _tr(g, out)
+    xs, ys = tr.transform_coords(theta.cuda())
+    s, leaves = ref.elastic(im, xs.cpu(), ys.cpu(), g, out)
+    return im, theta, dout, s, ref.backward(s, leaves, dout, g, tr.L_inv.cpu())
+
+
+def _img_bound(r, prior=None):
+    if prior is None:
+        return (r["n_img"] + 2) * EPS * r["S_img"]
+    return (r["n_img"] + 3) * EPS * (r["S_img"] + prior.double().abs())
+
+
+def _adjoint(g, im, theta, dout, out=OUT, **kw):
+    return training.st_elastic_transform_backward(im.cuda(), theta.cuda(), dout.cuda(), out, g, _tr(g, out).L_inv, **kw)
+
+
+# --------------------------------------------------------------------------------------------------------------- coordinates
+@pytest.mark.parametrize("g", [2, 4, 5])
+def test_transform_coords_are_the_coordinates_the_forward_samples_at(g):
+    K = g * g
+    tr = _tr(g)
+    theta = 0.15 * torch.randn(B, 2 * K, generator=torch.Generator().manual_seed(g))
+    xs, ys = tr.transform_coords(theta.cuda())
+    assert xs.shape == ys.shape == (B * OUT[0] * OUT[1],) and xs.dtype == torch.float32
+    assert xs.grad_fn is None and not xs.requires_grad
+    thg = theta.cuda().requires_grad_(True)
+    assert tr.transform_coords(thg)[0].grad_fn is None                      # forward only, whatever requires grad
+    # within the forward test's bound of the fp64 restatement
+    wx, wy, Tabs, Tcoef = xref.tps_coords(theta.numpy(), g, OUT, tr.L_inv.cpu().numpy())
+    d = (K + 16) * EPS * (Tabs + Tcoef) + EPS * np.abs(np.stack([wx, wy], 1))
+    err = np.abs(np.stack([xs.cpu().numpy().reshape(B, -1).astype(np.float64), ys.cpu().numpy().reshape(B, -1).astype(np.float64)], 1)
+                 - np.stack([wx, wy], 1))
+    print(f"coords g={g}: max err {err.max():.3e}, worst err / bound {(err / d).max():.3f}")
+    assert (err <= d).all()
+    # and exactly what the forward samples at: bilinear_interp on them is transform, bit for bit, tile kernel and pixel kernel
+    for C_ in (3, 1):
+        im = torch.rand(B, H, W, C_, generator=torch.Generator().manual_seed(C_)).cuda()
+        assert torch.equal(st.bilinear_interp(im, xs, ys, OUT).reshape(B, OUT[0], OUT[1], C_), tr.transform(im, theta.cuda()))
+
+
+# ----------------------------------------------------------------------------------------------- gradients against the reference
+def _compare(name, g, C_, scale, out):
+    im, theta, dout, s, r = _case(g, C_, scale, out)
+    d_img, d_theta = _adjoint(g, im, theta, dout, out)
+    assert d_theta.shape == (B, 2 * g * g) and d_img.shape == im.shape
+    _check(f"d_img[{name}]", d_img, r["d_img"], _img_bound(r))
+    _check(f"d_theta[{name}]", d_theta, r["d_theta"], (R_THETA + C_) * EPS * r["S_theta"])
+    assert torch.equal(_adjoint(g, im, theta, dout, out, need_img=False)[1], d_theta)
+    return s
+
+
+@pytest.mark.parametrize("C_", [3, 1, 4])
+@pytest.mark.parametrize("g", [2, 4, 5])
+def test_backward_matches_reference(g, C_):
+    """48 x 64 -> 40 x 56, offsets 0.15 randn: the tile kernel (C = 3) and the pixel kernel (C = 1, 4)."""
+    _compare(f"g={g},C={C_}", g, C_, 0.15, OUT)
+
+
+@pytest.mark.parametrize("C_", [3, 1])
+def test_backward_matches_reference_where_the_clip_blocks_gradients(C_):
+    """Offsets 0.6 randn push a real share of the grid outside [-1, W] x [-1, H]: those pixels pass no gradient."""
+    s = _compare(f"clip,C={C_}", 4, C_, 0.6, OUT)
+    blocked = int((~s.pass_x).sum()), int((~s.pass_y).sum())
+    print(f"pixels the clip blocks: x {blocked[0]}, y {blocked[1]} of {s.pass_x.numel()}")
+    assert blocked[0] > 0 and blocked[1] > 0
+
+
+@pytest.mark.parametrize("C_", [3, 1])
+def test_backward_matches_reference_at_the_largest_grid(C_):
+    """g = 16: K = 256 control points, one column per thread, 518 sums per sample."""
+    _compare(f"g=16,C={C_}", 16, C_, 0.15, BIG_OUT)
+
+
+@pytest.mark.parametrize("shift,C_", [(3, 3), (3, 1), (0, 3)])
+def test_every_coefficient_column_at_the_largest_grid(shift, C_):
+    """g = 16 again, with a SELECTOR table in place of L_inv: linv_t[k][j] = 0.1 [j == k + shift], so d theta[r, k] =
+    0.1 d cf[r][k + shift] -- one coefficient sum per offset, no cancellation between columns (with the real table at K = 256 the
+    bound is about as large as the gradient itself).  shift = 3 covers the K columns of U, shift = 0 the three affine ones (and U's
+    first K - 3 again).  The entry points take any table; the reference is fed the same one; the bound is the same
+    (r + C) eps S_theta.  Offsets -source + 0.3 randn keep half of the coordinates 0.1 sum_k P_k R_k or more inside the image."""
+    g, K = 16, 256
+    table = torch.zeros(K, K + 3)
+    table[torch.arange(K), torch.arange(K) + shift] = 0.1
+    gen = torch.Generator().manual_seed(160 + 10 * shift + C_)
+    im = torch.rand(B, H, W, C_, generator=gen)
+    theta = 0.3 * torch.randn(B, 2 * K, generator=gen) - torch.from_numpy(xref.tps_source_points(g)).reshape(1, 2 * K)
+    dout = torch.randn(B, BIG_OUT[0], BIG_OUT[1], C_, generator=gen)
+    tr = st.ElasticTransformer(BIG_OUT, g)
+    tr.L_inv = table.cuda()
+    xs, ys = tr.transform_coords(theta.cuda())
+    assert torch.equal(st.bilinear_interp(im.cuda(), xs, ys, BIG_OUT).reshape(B, *BIG_OUT, C_), tr.transform(im.cuda(), theta.cuda()))
+    s, leaves = ref.elastic(im, xs.cpu(), ys.cpu(), g, BIG_OUT)
+    r = ref.backward(s, leaves, dout, g, table)
+    assert int((s.pass_x & s.pass_y).sum()) > s.pass_x.numel() // 3          # the fp64 restatement has 1011-1382 of 1920 inside
+    d_img, d_theta = training.st_elastic_transform_backward(im.cuda(), theta.cuda(), dout.cuda(), BIG_OUT, g, tr.L_inv)
+    bound = (R_THETA + C_) * EPS * r["S_theta"]
+    _check(f"d_img[selector {shift},C={C_}]", d_img, r["d_img"], _img_bound(r))
+    _check(f"d_theta[selector {shift},C={C_}]", d_theta, r["d_theta"], bound)
+    strength = r["d_theta"].abs() / bound
+    print(f"|d theta| / bound: median {float(strength.median()):.1f}, min {float(strength.min()):.2f}")
+
+
+# ------------------------------------------------------------------------------------------------------------------ contract
+@pytest.mark.parametrize("C_", [3, 4])
+def test_backward_nullable_outputs_accumulate_and_zero_theta(C_):
+    g = 4
+    im, theta, dout, s, r = _case(g, C_)
+    both_img, both_theta = _adjoint(g, im, theta, dout)
+    only_img, none_theta = _adjoint(g, im, theta, dout, need_theta=False)
+    none_img, only_theta = _adjoint(g, im, theta, dout, need_img=False)
+    assert none_theta is None and none_img is None
+    assert torch.equal(only_theta, both_theta)                                # the same sums in the same order
+    assert torch.equal(_adjoint(g, im, theta, dout)[1], both_theta)           # and again: no atomics
+    assert both_theta.shape == (B, 2 * g * g)
+    _check("d_img alone", only_img, r["d_img"], _img_bound(r))
+    prior = torch.randn(im.shape, generator=torch.Generator().manual_seed(5))
+    acc = prior.clone().cuda()
+    got, _ = _adjoint(g, im, theta, dout, need_theta=False, d_img=acc)
+    assert got.data_ptr() == acc.data_ptr()
+    _check("d_img accumulated", acc, prior.double() + r["d_img"], _img_bound(r, prior))
+    # accumulate = 0 overwrites whatever was there, NaN included
+    L = _lib.lib()
+    buf = torch.full(im.shape, float("nan"), device="cuda")
+    imc, thc, dc, linv = im.cuda(), theta.cuda(), dout.cuda(), _tr(g).L_inv
+    assert L.vstab_st_elastic_transform_backward(imc.data_ptr(), B, H, W, C_, thc.data_ptr(), g, linv.data_ptr(), dc.data_ptr(), OUT[0], OUT[1],
+                                                 buf.data_ptr(), 0, None, None, 0, runtime.stream_ptr()) == 0
+    _check("d_img over NaN", buf, r["d_img"], _img_bound(r))
+    # theta = 0 (the identity map: grid points ON control points, r^2 = 0 and U = 0 there) gives a finite gradient
+    z_img, z_theta = _adjoint(g, im, torch.zeros_like(theta), dout)
+    assert bool(torch.isfinite(z_theta).all()) and bool(torch.isfinite(z_img).all()) and bool((z_theta != 0).any())
+
+
+# ------------------------------------------------------------------------------------------------------------------ autograd
+def test_autograd_through_transform_is_the_explicit_backward():
+    g, C_ = 4, 3
+    im, theta, dout, s, r = _case(g, C_)
+    tr = _tr(g)
+    imc, thc = im.cuda().requires_grad_(True), theta.cuda().requires_grad_(True)
+    y = tr.transform(imc, thc)
+    assert y.grad_fn is not None and y.shape == (B, OUT[0], OUT[1], C_)
+    g_im, g_th = torch.autograd.grad(y, (imc, thc), dout.cuda())
+    e_im, e_th = _adjoint(g, im, theta, dout)
+    assert g_th.shape == theta.shape and torch.equal(g_th, e_th)
+    _check("autograd d_img", g_im, r["d_img"], _img_bound(r))
+    y_back = tr.transform(imc, thc, forward=False)                          # forward=False: the same coordinates, the same graph
+    assert y_back.grad_fn is not None and torch.equal(y_back, y)
+    assert torch.equal(torch.autograd.grad(y_back, thc, dout.cuda())[0], e_th)
+    # no requires_grad anywhere, or no_grad: today's call, today's bits, no graph
+    plain = tr.transform(im.cuda(), theta.cuda())
+    assert plain.grad_fn is None and not plain.requires_grad and torch.equal(plain, y.detach())
+    with torch.no_grad():
+        quiet = tr.transform(imc, thc)
+    assert quiet.grad_fn is None and torch.equal(quiet, y.detach())
+    # bicubic keeps today's behaviour: no graph
+    assert _tr(g, OUT, 'bicubic').transform(imc, thc).grad_fn is None
+
+
+def test_autograd_frozen_image_or_frozen_theta_skips_that_gradient(monkeypatch):
+    g, C_ = 4, 3
+    im, theta, dout, s, r = _case(g, C_)
+    tr = _tr(g)
+    calls = []
+    real = training.st_elastic_transform_backward
+
+    def spy(*a, **k):
+        calls.append((k["need_img"], k["need_theta"]))
+        res = real(*a, **k)
+        calls.append(tuple(t is not None for t in res))
+        return res
+
+    monkeypatch.setattr(training, "st_elastic_transform_backward", spy)
+    imc, thc = im.cuda().requires_grad_(True), theta.cuda().requires_grad_(True)
+    (g_im,) = torch.autograd.grad(tr.transform(imc, theta.cuda()), (imc,), dout.cuda())
+    assert calls == [(True, False), (True, False)]                            # the d theta reduction is not launched
+    calls.clear()
+    (g_th,) = torch.autograd.grad(tr.transform(im.cuda(), thc), (thc,), dout.cuda())
+    assert calls == [(False, True), (False, True)]                            # a frozen image costs no scatter
+    assert torch.equal(g_th, real(im.cuda(), theta.cuda(), dout.cuda(), OUT, g, tr.L_inv, need_img=False)[1])
+    # and the frozen input receives no gradient
+    frozen_th, frozen_im = theta.cuda(), im.cuda()
+    imc.grad = thc.grad = None
+    tr.transform(imc, frozen_th).backward(dout.cuda())
+    tr.transform(frozen_im, thc).backward(dout.cuda())
+    assert frozen_th.grad is None and frozen_im.grad is None
+    assert torch.equal(thc.grad, g_th) and imc.grad is not None
+
+
+def test_a_few_gradient_steps_on_theta_lower_the_loss():
+    """g = 4 on a 32 x 40 x 3 image of a few low-frequency sinusoids: the target is the image warped by known small offsets
+    (0.05 randn), theta starts at zero, five steps of plain gradient descent (step 0.5) on the MSE.  Seed and step were tried with
+    the fp64 reference on the CPU (st_tps_grad_ref.elastic_exact), where the loss falls from 1.06e-2 to 1.24e-3 without rising once.
+    The only claim: the loss ends strictly below where it started."""
+    g, hw = 4, (32, 40)
+    im = _smooth_image(*hw).cuda()
+    tr = st.ElasticTransformer(hw, g)
+    tstar = 0.05 * torch.randn(1, 2 * g * g, generator=torch.Generator().manual_seed(16))
+    target = tr.transform(im, tstar.cuda())
+    theta = torch.zeros(1, 2 * g * g, device="cuda", requires_grad=True)
+    losses = []
+    for _ in range(5):
+        loss = ((tr.transform(im, theta) - target) ** 2).mean()
+        (grad,) = torch.autograd.grad(loss, theta)
+        losses.append(float(loss.detach()))
+        theta = (theta.detach() - 0.5 * grad).requires_grad_(True)
+    final = float(((tr.transform(im, theta.detach()) - target) ** 2).mean())
+    print(f"loss {losses[0]:.4e} -> {final:.4e}: {losses}")
+    assert final < losses[0]
+
+
+# ----------------------------------------------------------------------------------------------------------- argument checks
+def test_elastic_entry_points_reject_bad_arguments():
+    L = _lib.lib()
+    sp = runtime.stream_ptr()
+    Bq, Hq, Wq, C_, oh, ow, g = 1, 8, 9, 3, 6, 7, 4
+    K = g * g
+    im, th = torch.rand(Bq, Hq, Wq, C_, device="cuda"), torch.zeros(Bq, 2 * K, device="cuda")
+    linv = _tr(g).L_inv
+    dout = torch.rand(Bq, oh, ow, C_, device="cuda")
+    d_img, d_th = torch.full_like(im, 7.0), torch.full((Bq, 2 * K), 7.0, device="cuda")
+    xo, yo = torch.full((Bq * oh * ow,), 7.0, device="cuda"), torch.full((Bq * oh * ow,), 7.0, device="cuda")
+    need = L.vstab_st_elastic_transform_backward_workspace_bytes(Bq, Hq, Wq, C_, g, oh, ow)
+    assert need > 0 and need % 8 == 0
+    ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+
+    def tb(img=im.data_ptr(), B=Bq, H=Hq, C_=C_, theta=th.data_ptr(), g=g, lt=linv.data_ptr(), do=dout.data_ptr(), oh=oh, ow=ow,
+           di=d_img.data_ptr(), dt=d_th.data_ptr(), w=ws.data_ptr(), wb=need):
+        return L.vstab_st_elastic_transform_backward(img, B, H, Wq, C_, theta, g, lt, do, oh, ow, di, 0, dt, w, wb, sp)
+
+    def tc(theta=th.data_ptr(), B=Bq, g=g, lt=linv.data_ptr(), oh=oh, ow=ow, x=xo.data_ptr(), y=yo.data_ptr()):
+        return L.vstab_st_elastic_coords(theta, B, g, lt, oh, ow, x, y, sp)
+
+    E_SHAPE, E_NOMEM, E_STATE = -1, -4, -6
+    assert tb(img=None) == E_STATE and tb(theta=None) == E_STATE and tb(do=None) == E_STATE and tb(lt=None) == E_STATE
+    assert b"st_elastic_transform_backward" in L.vstab_last_error(None)
+    assert tb(g=1) == E_SHAPE and tb(g=17) == E_SHAPE
+    assert tb(H=0) == E_SHAPE and tb(C_=0) == E_SHAPE and tb(oh=0) == E_SHAPE and tb(ow=-3) == E_SHAPE          # a zero size
+    assert tb(B=0) == E_SHAPE and tb(B=65536) == E_SHAPE
+    assert b"st_elastic_transform_backward" in L.vstab_last_error(None)
+    assert tb(di=None, dt=None) == E_SHAPE                                                                      # both outputs NULL
+    assert b"both NULL" in L.vstab_last_error(None)
+    assert tb(wb=need - 8) == E_NOMEM and tb(w=None) == E_NOMEM                                                 # short workspace
+    assert b"st_elastic_transform_backward: workspace" in L.vstab_last_error(None)
+    assert L.vstab_st_elastic_transform_backward_workspace_bytes(0, Hq, Wq, C_, g, oh, ow) == 0
+    assert L.vstab_st_elastic_transform_backward_workspace_bytes(Bq, Hq, Wq, C_, 17, oh, ow) == 0
+    assert tc(theta=None) == E_STATE and tc(lt=None) == E_STATE and tc(x=None) == E_STATE and tc(y=None) == E_STATE
+    assert tc(g=1) == E_SHAPE and tc(g=17) == E_SHAPE and tc(oh=0) == E_SHAPE and tc(B=0) == E_SHAPE and tc(B=65536) == E_SHAPE
+    assert b"st_elastic_coords" in L.vstab_last_error(None)
+    torch.cuda.synchronize()
+    for t in (d_img, d_th, xo, yo):
+        assert bool((t == 7.0).all())                                                                           # nothing was written
+    # the workspace rule: rows per sample are bounded whatever the frame size -- min(steps, max(16, 1024 / B)) rows of 2 (K + 3) doubles
+    row = 2 * (K + 3) * 8
+    assert L.vstab_st_elastic_transform_backward_workspace_bytes(1, 720, 1280, 3, g, 720, 1280) == 1024 * row
+    assert L.vstab_st_elastic_transform_backward_workspace_bytes(32, 720, 1280, 3, 16, 720, 1280) == 32 * 32 * 2 * 259 * 8
+    assert L.vstab_st_elastic_transform_backward_workspace_bytes(2, 48, 64, 1, g, 16, 16) == 2 * 1 * row      # one run of 256 pixels
+    # the workspace is not needed, and not looked at, without d theta; the calls themselves work
+    assert tb(dt=None, w=None, wb=0) == 0 and tb(di=None) == 0 and tb() == 0 and tc() == 0
+    with pytest.raises(ValueError):
+        training.st_elastic_transform_backward(im, th[:, :31], dout, (oh, ow), g, linv)
+    with pytest.raises(ValueError):
+        training.st_elastic_transform_backward(im, th, dout, (oh + 1, ow), g, linv)
+    with pytest.raises(ValueError):
+        training.st_elastic_transform_backward(im, th, dout, (oh, ow), g, linv[:, :-1])
+    with pytest.raises(ValueError):
+        _tr(g).transform_coords(th[:, :31])
+    torch.cuda.synchronize()
