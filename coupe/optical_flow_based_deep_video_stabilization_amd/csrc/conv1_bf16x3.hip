@@ -1,6 +1,6 @@
 // The first layer (model.py:807-809: PadLayer(3) + Conv2d 7x7 s2 VALID + BatchNorm + lrelu on the 27-channel frame stack) on the
-// bf16 matrix pipe with fp32 accuracy: the row-window kernel of conv_rowwin.hip (same RowWinParams, same window, same epilogue and
-// output addressing) with every fp32 operand split into three bf16 pieces.
+// bf16 matrix pipe with fp32 accuracy: the row-window kernel of conv_rowwin.hip (the tile, window and epilogue of rowwin_tile.h) with
+// every fp32 operand split into three bf16 pieces.
 //
 //   x = x1 + x2 + x3 exactly:  x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2)   (round to nearest even; both differences
 //   are exact in fp32, and the three 8-bit significands cover fp32's 24)
@@ -18,56 +18,27 @@
 //     whatever the tile height and the batch
 //   * one set of planes per workgroup (3 * WLEN * 2 bytes, 42 KB for 128-pixel tiles): the next filter row's fp32 window is in flight
 //     in registers under the MFMAs of this one, then barrier, split + store, barrier; two or three workgroups per CU cover the gap
-#include <hip/hip_ext.h>
-
-#include "vstab_internal.h"
+#include "rowwin_tile.h"
 
 namespace vstab {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-template <int NWIN4, int MB>   // float4 loads per thread per window; 32-pixel blocks per wave (conv_rowwin.hip)
+template <int NWIN4, int MB>   // float4 loads per thread per window; 32-pixel blocks per wave (rowwin_tile.h)
 __global__ __launch_bounds__(256) void conv1_bf16x3_kernel(const RowWinParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned *planes = reinterpret_cast<unsigned *>(smem);  // [3][WLEN] bf16, addressed in 32-bit words
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;                // 2x2 waves, wave tile 32*MB (pixels) x 32 (channels)
-    const int li = lane & 31, lh = lane >> 5;
-    unsigned bx_, by_, bz_;
-    xcd_remap(bx_, by_, bz_);                               // (row, x tile, sample): a remapped XCD range is a band of output rows
-    // the forward's first launch zeroes the ticket words of the launches that follow it (see conv_rowwin.hip)
-    if (p.clear_n > 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
-        for (int i = tid; i < p.clear_n; i += 256) p.clear_words[i] = 0u;
-    const int oy = (int)bx_;
-    const int ox0 = p.ox_base + (int)by_ * (64 * MB), n = (int)bz_;
-    const int pix_step = p.s_in * p.Cs_in;
-    const int row_floats = p.Wi * p.Cs_in;
-    const int g0 = pix_step * ox0 + p.e_off - p.w_a;       // window start, floats from the row start (multiple of 4)
-
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.in), 0, p.in_bytes, 0x00020000);
-    const unsigned OOB = 0xC0000000u;
+    const RowWinTile<MB> t = rowwin_tile<MB>(p);
+    const int tid = t.tid, wm = t.wm, wn = t.wn, li = t.li, lh = t.lh;
+    const int oy = t.row, pix_step = t.pix_step;
 
     f32x4 wv[NWIN4];
-    auto load_window = [&](int ky) {
-        const int iy = oy * p.s_in + p.off_y + ky;
-        const bool yok = (unsigned)iy < (unsigned)p.Hi;
-        const int rowbase = ((n * p.Hi + iy) * p.Wi) * p.Cs_in;      // element offset (< 2^29, checked on the host)
-#pragma unroll
-        for (int j = 0; j < NWIN4; ++j) {
-            const int c4 = tid + 256 * j;
-            const int g = g0 + 4 * c4;
-            const bool ok = yok && g >= 0 && g < row_floats && 4 * c4 < p.WLEN;
-            const unsigned off = ok ? (unsigned)(rowbase + g) * 4u : OOB;
-            wv[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, 0));
-        }
-    };
+    auto load_window = [&](int ky) { rowwin_load_window(t, p, oy, ky, wv); };
     // the split, once per staged element: three conversions and two (exact) subtractions
     const int plane_w = p.WLEN >> 1;                        // 32-bit words per plane
     auto split_store = [&]() {
@@ -166,87 +137,21 @@ __global__ __launch_bounds__(256) void conv1_bf16x3_kernel(const RowWinParams p)
         }
     }
 
-    // epilogue as in conv_rowwin.hip: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5); the tile leaves through LDS (the planes
-    // are free now) as 16-byte stores of whole 256-byte pixel rows
-    const int col = wn * 32 + li;
-    if (p.out_vec4) {
-        constexpr int TP = 64 * MB;                   // pixels of the tile; sC [TP][64]
-        __syncthreads();
-        float *sC = reinterpret_cast<float *>(smem);
-        const float bv = col < p.N ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sC[(wm * 32 * MB + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * 64 + col] = acc[mb][r] + bv;
-        __syncthreads();
-        const float slope = p.act == 1 ? 0.1f : 0.0f;
-        float *orow = p.out + ((long long)(n * p.Ho + oy) * p.Wo + ox0) * p.Cs_out + p.c_off;
-#pragma unroll 4
-        for (int e = tid; e < TP * 16; e += 256) {
-            const int px = e >> 4, c4 = (e & 15) * 4;
-            if (ox0 + px >= p.Wo || c4 >= p.N) continue;
-            f32x4 v = *reinterpret_cast<const f32x4 *>(sC + px * 64 + c4);
-            if (p.act) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], slope * v[i]);
-            }
-            float *o = orow + (long long)px * p.Cs_out + c4;
-            if (c4 + 4 <= p.N) *reinterpret_cast<f32x4 *>(o) = v;
-            else for (int i = 0; c4 + i < p.N; ++i) o[i] = v[i];
-        }
-    } else if (col < p.N) {
-        const float bv = p.bias[col];
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ox = ox0 + wm * 32 * MB + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (ox < p.Wo) {
-                    float v = acc[mb][r] + bv;
-                    if (p.act) v = fmaxf(v, (p.act == 1 ? 0.1f : 0.0f) * v);
-                    p.out[((long long)(n * p.Ho + oy) * p.Wo + ox) * p.Cs_out + p.c_off + col] = v;
-                }
-            }
-    }
-}
-
-// the row-window kernel's conditions (same window, same loads) and whole trips of two 16-wide K-groups per filter row
-bool conv1_bf16x3_applicable(const RowWinParams &p)
-{
-    return rowwin_applicable(p) && p.KH >= 1 && (p.SEGP % 32) == 0 && p.SEGP >= 32;
+    rowwin_epilogue(t, p, acc, oy, reinterpret_cast<float *>(smem));       // the planes are free now
 }
 
 hipError_t conv1_bf16x3_set_attributes()
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv1_bf16x3_kernel<7, 2>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 7 * 1024 * 2);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(conv1_bf16x3_kernel<4, 1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 4 * 1024 * 2);
+    return rowwin_set_lds_limits(conv1_bf16x3_kernel<7, 2>, 3 * 7 * 1024 * 2, conv1_bf16x3_kernel<4, 1>, 3 * 4 * 1024 * 2);
 }
 
 hipError_t launch_conv1_bf16x3(const RowWinParams &p, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    if (!conv1_bf16x3_applicable(p)) return hipErrorInvalidValue;
-    const int tile = 64 * p.MB;
-    if (p.ox_base < 0 || p.ox_base >= p.Wo || (p.ox_base & 1) || p.ntile_x < 0) return hipErrorInvalidValue;
-    const int ntx = p.ntile_x > 0 ? p.ntile_x : (p.Wo - p.ox_base + tile - 1) / tile;       // x tiles of THIS launch
-    dim3 grid(p.Ho, ntx, p.B), block(256);       // (row, x tile, sample)
+    if (!conv1_bf16x3_geometry_ok(p)) return hipErrorInvalidValue;
     RowWinParams q = p;
-    const size_t lds = (size_t)3 * p.WLEN * 2;
-    // the staged epilogue needs 16-byte friendly output rows and the [tile][64] staging area inside the planes
-    q.out_vec4 = (((uintptr_t)p.out & 15) == 0 && (p.Cs_out & 3) == 0 && (p.c_off & 3) == 0 && lds >= (size_t)tile * 64 * 4) ? 1 : 0;
     q.asm_loop = 0;
     q.stream_rows = 0;
-    const bool timed = ev_start || ev_stop;      // timestamps of the kernel's own dispatch packet (see conv_mfma.hip)
-    if (p.MB == 2) {
-        if (timed) hipExtLaunchKernelGGL((conv1_bf16x3_kernel<7, 2>), grid, block, lds, stream, ev_start, ev_stop, 0, q);
-        else conv1_bf16x3_kernel<7, 2><<<grid, block, lds, stream>>>(q);
-    } else {
-        if (timed) hipExtLaunchKernelGGL((conv1_bf16x3_kernel<4, 1>), grid, block, lds, stream, ev_start, ev_stop, 0, q);
-        else conv1_bf16x3_kernel<4, 1><<<grid, block, lds, stream>>>(q);
-    }
-    return hipGetLastError();
+    return rowwin_launch(q, conv1_bf16x3_kernel<7, 2>, conv1_bf16x3_kernel<4, 1>, (size_t)3 * p.WLEN * 2, stream, ev_start, ev_stop);
 }
 
 }  // namespace vstab

@@ -71,3 +71,32 @@ ConvParams conv_desc_wdec_gemm(int B, const WdecGeom &g, int cs_in, int cout)
     for (int q = 0; q < 9; ++q) { Hg[q] = g.nty[q / 3]; Wg[q] = g.ntx[q % 3]; }
     return conv_desc_planes(B, 9, g.NTy, g.NTx, Hg, Wg, cs_in, 4 * cout);
 }
+
+RowWinDesc rowwin_desc(int B, int H, int W, int cin, int k, int stride, int pad, int Ho, int Wo, int cout, int npad, int cs_out, int c_off,
+                       int act)
+{
+    RowWinDesc d;
+    std::memset(&d, 0, sizeof d);
+    RowWinParams &r = d.main;
+    r.in_bytes = (unsigned)std::min<long long>((long long)B * H * W * cin * 4, 0xFFFFFFFFLL);
+    r.B = B; r.Hi = H; r.Wi = W; r.Cs_in = cin; r.KH = k;
+    r.SEGP = rowwin_segp(-pad, k, cin);
+    r.s_in = stride; r.off_y = -pad;
+    r.e_off = -pad * cin - rowwin_lead(-pad, cin);
+    r.w_a = ((r.e_off % 4) + 4) % 4;
+    r.Ho = Ho; r.Wo = Wo; r.Cs_out = cs_out; r.c_off = c_off; r.N = cout; r.Npad = npad; r.act = act;
+    // window of a tile of 64 MB pixels: from the first pixel's run to the end of the last one's
+    auto tile = [](RowWinParams &q, int MB) { q.MB = MB; q.WLEN = round_up(q.s_in * q.Cs_in * (64 * MB - 1) + q.w_a + q.SEGP, 4); };
+    tile(r, rowwin_mb(B, Ho, Wo));
+    d.ok = rowwin_geometry_ok(r);
+    const int rem = Wo % 128;
+    if (d.ok && r.MB == 2 && Wo > 128 && rem >= 1 && rem <= 64) {
+        RowWinParams &t = d.tail;
+        t = r;
+        tile(t, 1);
+        t.ox_base = (Wo / 128) * 128; t.ntile_x = 1;
+        d.two = rowwin_geometry_ok(t);
+        if (d.two) r.ntile_x = Wo / 128;
+    }
+    return d;
+}

@@ -1,6 +1,8 @@
-// Launch descriptors (ConvParams, vstab_internal.h) of the three problem shapes the implicit-GEMM kernels run, each built in ONE
-// place.  Host only.  Every builder returns a zero-initialised descriptor with the K layout, phases, Mmax, w_off and the
-// buffer-descriptor ranges set and ksplit = 1; the caller adds the pointers, decides the split and keeps its own refusals.
+// Launch descriptors, each built in ONE place.  Host only.  The caller adds the pointers and keeps its own refusals.
+//   * ConvParams (vstab_internal.h) of the three problem shapes the implicit-GEMM kernels run: every builder returns a
+//     zero-initialised descriptor with the K layout, phases, Mmax, w_off and the buffer-descriptor ranges set and ksplit = 1; the
+//     caller decides the split.
+//   * RowWinParams of the first layer's row-window kernels (rowwin_desc, at the end).
 #pragma once
 #include "vstab_internal.h"
 
@@ -45,3 +47,11 @@ vstab::ConvParams conv_desc_planes(int B, int P, int pitch, int Wi, const int *H
 // the 16 positions of F(2x2,3x3) over an H x W image, and the 9 of a transposed conv's F(2x2,2x2) (4 cout columns: one per phase)
 vstab::ConvParams conv_desc_wino_gemm(int B, int H, int W, int cin, int cout);
 vstab::ConvParams conv_desc_wdec_gemm(int B, const vstab::WdecGeom &g, int cs_in, int cout);
+
+// Row-window kernels (conv_rowwin.hip, conv1_bf16x3.hip): k x k, stride, zero pad over all cin channels of the pixel.  main covers the
+// whole row, or, when the row is 128 n + (1..64) pixels long and runs on 128-pixel tiles, its n full tiles, and tail (two = true) the
+// rest as ONE 64-pixel tile in a launch of its own.  ok = rowwin_geometry_ok(main).  Zero-initialised but for the geometry: the caller
+// adds the pointers (and main's clear_words) and keeps its own refusals.
+struct RowWinDesc { vstab::RowWinParams main, tail; bool ok, two; };
+RowWinDesc rowwin_desc(int B, int H, int W, int cin, int k, int stride, int pad, int Ho, int Wo, int cout, int npad, int cs_out, int c_off,
+                       int act);

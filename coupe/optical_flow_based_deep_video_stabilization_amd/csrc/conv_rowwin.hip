@@ -23,67 +23,34 @@
 // the image are loaded as zeros via the buffer descriptor's range check (no branches).
 // Requires (s*C_in) even, (W*C_in) % 4 == 0, 16-byte aligned input; otherwise the generic
 // scalar-gather kernel runs instead.
-#include <hip/hip_ext.h>
-
-#include "vstab_internal.h"
+#include "rowwin_tile.h"
 
 namespace vstab {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 #include "conv_kloop_gfx950.inc"
 
-// MB = 32-pixel blocks per wave: 2 -> 128 output pixels per workgroup (wave tile 64 x 32); 1 -> 64 pixels (wave tile 32 x 32) for
-// launches that would otherwise put fewer than two workgroups on a CU (one sample at 384x512: 384 workgroups on 256 CUs run as
-// two uneven rounds, 91 us; 768 half-size ones are all resident at once)
-template <int NWIN4, int MB>   // float4 loads per thread per window
+// the tile, the window load and the epilogue are rowwin_tile.h's; here: the window's place in LDS, the K loop in C++ and its three
+// assembly forms
+template <int NWIN4, int MB>   // float4 loads per thread per window; 32-pixel blocks per wave
 __global__ __launch_bounds__(256) void conv_rowwin_kernel(const RowWinParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *win = reinterpret_cast<float *>(smem);           // [2][WLEN]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;                // 2x2 waves, wave tile 32*MB (pixels) x 32 (channels)
-    const int li = lane & 31, lh = lane >> 5;
-    // XCD-aware order: grid = (row, x tile, sample) so that a remapped XCD range is a band of consecutive output rows, whose
-    // 7-row input windows overlap by five rows
-    unsigned bx_, by_, bz_;
-    xcd_remap(bx_, by_, bz_);
-    // a chore for the launches that FOLLOW this one in the forward: the first workgroup zeroes the ticket words of the in-launch split-K
-    // reductions (conv_skinny.hip).  As the forward's first launch this kernel finishes before any of them starts (stream order), and the
-    // words ride here instead of in a memset node of their own (4.7 us per forward: 1 ... 1.6 % of a one-sample frame)
-    if (p.clear_n > 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
-        for (int i = tid; i < p.clear_n; i += 256) p.clear_words[i] = 0u;
+    const RowWinTile<MB> t = rowwin_tile<MB>(p);
+    const int tid = t.tid, wm = t.wm, wn = t.wn, li = t.li, lh = t.lh;
     const int stream_r = (MB == 2 && p.asm_loop) ? p.stream_rows : 0;          // > 0: this workgroup computes stream_r output rows (oy, oy + S, oy + 2 S ...)
     // rows between a stream's tiles.  1: the stream walks down CONSECUTIVE rows.  (Interleaving a column's streams -- stride = their
     // number, so that they work on adjacent rows at any time and share input rows in L2 -- brings the launch's HBM reads from 3.2x to 1.9x
     // the one-tile-per-workgroup launch's, and measures the same at B=8 512x512 but 2.5 % SLOWER at 720p / 1080p: profiles/README.md r03p)
     const int stream_s = 1;
-    int oy = stream_r > 0 ? (int)bx_ * stream_r : (int)bx_;
-    const int ox0 = p.ox_base + (int)by_ * (64 * MB), n = (int)bz_;
-    const int pix_step = p.s_in * p.Cs_in;
-    const int row_floats = p.Wi * p.Cs_in;
-    const int g0 = pix_step * ox0 + p.e_off - p.w_a;       // window start, floats from the row start (multiple of 4)
-
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.in), 0, p.in_bytes, 0x00020000);
-    const unsigned OOB = 0xC0000000u;
+    int oy = stream_r > 0 ? t.row * stream_r : t.row;
+    const int ox0 = t.ox0, n = t.n, pix_step = t.pix_step, row_floats = t.row_floats;
 
     f32x4 wv[NWIN4];
-    auto load_window = [&](int ky) {
-        const int iy = oy * p.s_in + p.off_y + ky;
-        const bool yok = (unsigned)iy < (unsigned)p.Hi;
-        const int rowbase = ((n * p.Hi + iy) * p.Wi) * p.Cs_in;      // element offset (< 2^29, checked on the host)
-#pragma unroll
-        for (int j = 0; j < NWIN4; ++j) {
-            const int c4 = tid + 256 * j;
-            const int g = g0 + 4 * c4;
-            const bool ok = yok && g >= 0 && g < row_floats && 4 * c4 < p.WLEN;
-            const unsigned off = ok ? (unsigned)(rowbase + g) * 4u : OOB;
-            wv[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, 0));
-        }
-    };
+    auto load_window = [&](int ky) { rowwin_load_window(t, p, oy, ky, wv); };
     // byte stride of the two window buffers: the assembly loop fetches windows by LDS-DMA, whole 4 KB wave chunks (lanes past the
     // window's end land zeros), so its buffers are a whole number of chunks apart
     constexpr int ASM_BUF = MB == 2 ? VSTAB_ROWWIN_BUF_BYTES : VSTAB_ROWWIN1_BUF_BYTES;
@@ -151,12 +118,11 @@ __global__ __launch_bounds__(256) void conv_rowwin_kernel(const RowWinParams p)
             const unsigned vb = (unsigned)((wn * 32 + li) * 32 + lh * 4) * 4u;
             unsigned w[7];                            // per-lane byte offset of its 16 bytes of every window chunk inside the input row, or out of range
 #pragma unroll
-            for (int j = 0; j < 7; ++j) w[j] = OOB;
+            for (int j = 0; j < 7; ++j) w[j] = ROWWIN_OOB;
 #pragma unroll
             for (int j = 0; j < NWIN4; ++j) {
-                const int c4 = tid + 256 * j;
-                const int g = g0 + 4 * c4;
-                w[j] = (g >= 0 && g < row_floats && 4 * c4 < p.WLEN) ? (unsigned)g * 4u : OOB;
+                int g;
+                if (rowwin_chunk(t, p, j, g)) w[j] = (unsigned)g * 4u;
             }
             const unsigned long long ain = (unsigned long long)(size_t)p.in, awt = (unsigned long long)(size_t)p.wpk;
             i32x4 din, dwt;
@@ -265,77 +231,19 @@ __global__ __launch_bounds__(256) void conv_rowwin_kernel(const RowWinParams p)
     }
     }
 
-    // epilogue: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).  As in conv_mfma.hip the tile leaves through LDS (the window
-    // buffers are free now) as 16-byte stores of whole 256-byte pixel rows instead of 32 four-byte store instructions per wave.
-    const int col = wn * 32 + li;
-    if (p.out_vec4) {
-        constexpr int TP = 64 * MB;                   // pixels of the tile; sC [TP][64]
-        __syncthreads();                              // every wave has read its last operands out of the window
-        float *sC = win;
-        const float bv = col < p.N ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sC[(wm * 32 * MB + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * 64 + col] = acc[mb][r] + bv;
-        __syncthreads();
-        const float slope = p.act == 1 ? 0.1f : 0.0f;
-        float *orow = p.out + ((long long)(n * p.Ho + oy) * p.Wo + ox0) * p.Cs_out + p.c_off;
-#pragma unroll 4
-        for (int e = tid; e < TP * 16; e += 256) {
-            const int px = e >> 4, c4 = (e & 15) * 4;
-            if (ox0 + px >= p.Wo || c4 >= p.N) continue;
-            f32x4 v = *reinterpret_cast<const f32x4 *>(sC + px * 64 + c4);
-            if (p.act) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], slope * v[i]);
-            }
-            float *o = orow + (long long)px * p.Cs_out + c4;
-            if (c4 + 4 <= p.N) *reinterpret_cast<f32x4 *>(o) = v;
-            else for (int i = 0; c4 + i < p.N; ++i) o[i] = v[i];
-        }
-    } else if (col < p.N) {
-        const float bv = p.bias[col];
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int ox = ox0 + wm * 32 * MB + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (ox < p.Wo) {
-                    float v = acc[mb][r] + bv;
-                    if (p.act) v = fmaxf(v, (p.act == 1 ? 0.1f : 0.0f) * v);
-                    p.out[((long long)(n * p.Ho + oy) * p.Wo + ox) * p.Cs_out + p.c_off + col] = v;
-                }
-            }
-    }
-}
-
-bool rowwin_applicable(const RowWinParams &p)
-{
-    const int pix_step = p.s_in * p.Cs_in;
-    return (pix_step % 2 == 0) && ((p.Wi * p.Cs_in) % 4 == 0) && (((uintptr_t)p.in & 15) == 0) && p.N <= 64 &&
-           p.Npad == 64 && (p.MB == 1 || p.MB == 2) && p.WLEN <= (p.MB == 2 ? 7 : 4) * 1024 && (p.WLEN % 4) == 0 &&
-           p.in_bytes < 0x80000000u;
+    rowwin_epilogue(t, p, acc, oy, win);              // the window buffers are free now
 }
 
 hipError_t rowwin_set_attributes()
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_rowwin_kernel<7, 2>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 7 * 1024 * 4);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(conv_rowwin_kernel<4, 1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 1024 * 4);
+    return rowwin_set_lds_limits(conv_rowwin_kernel<7, 2>, 2 * 7 * 1024 * 4, conv_rowwin_kernel<4, 1>, 2 * 4 * 1024 * 4);
 }
 
 hipError_t launch_conv_rowwin(const RowWinParams &p, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    if (!rowwin_applicable(p)) return hipErrorInvalidValue;
-    const int tile = 64 * p.MB;
-    if (p.ox_base < 0 || p.ox_base >= p.Wo || (p.ox_base & 1) || p.ntile_x < 0) return hipErrorInvalidValue;
-    const int ntx = p.ntile_x > 0 ? p.ntile_x : (p.Wo - p.ox_base + tile - 1) / tile;       // x tiles of THIS launch
-    dim3 grid(p.Ho, ntx, p.B), block(256);       // (row, x tile, sample): see the XCD remap in the kernel
+    const int ntx = rowwin_xtiles(p);            // x tiles of THIS launch
+    if (!rowwin_geometry_ok(p) || ntx < 0) return hipErrorInvalidValue;
     RowWinParams q = p;
-    // the staged epilogue needs 16-byte friendly output rows and the [tile][64] staging area inside the two window buffers
-    q.out_vec4 = (((uintptr_t)p.out & 15) == 0 && (p.Cs_out & 3) == 0 && (p.c_off & 3) == 0 && 2 * p.WLEN >= tile * 64) ? 1 : 0;
     q.asm_loop = ((p.SEGP >> 5) == 6 && p.KH >= 1 && 4 * p.WLEN <= (p.MB == 2 ? VSTAB_ROWWIN_BUF_BYTES : VSTAB_ROWWIN1_BUF_BYTES)) ? 1 : 0;
 #ifdef VSTAB_NO_ASM_KLOOP
     q.asm_loop = 0;                              // A/B builds only (scripts/build_variant_lib.sh)
@@ -361,18 +269,8 @@ hipError_t launch_conv_rowwin(const RowWinParams &p, hipStream_t stream, hipEven
 #ifdef VSTAB_NO_ROWWIN_STREAM
     q.stream_rows = 0;                           // A/B builds only
 #endif
-    if (q.stream_rows > 0) grid.x = (unsigned)(p.Ho / q.stream_rows);
     const size_t lds2 = q.asm_loop ? (size_t)2 * (p.MB == 2 ? VSTAB_ROWWIN_BUF_BYTES : VSTAB_ROWWIN1_BUF_BYTES) : (size_t)2 * p.WLEN * 4;
-    const bool timed = ev_start || ev_stop;      // timestamps of the kernel's own dispatch packet, no marker packets (see conv_mfma.hip); a
-                                                 // launch that is one half of a pair carries only the start or only the stop event
-    if (p.MB == 2) {
-        if (timed) hipExtLaunchKernelGGL((conv_rowwin_kernel<7, 2>), grid, block, lds2, stream, ev_start, ev_stop, 0, q);
-        else conv_rowwin_kernel<7, 2><<<grid, block, lds2, stream>>>(q);
-    } else {
-        if (timed) hipExtLaunchKernelGGL((conv_rowwin_kernel<4, 1>), grid, block, lds2, stream, ev_start, ev_stop, 0, q);
-        else conv_rowwin_kernel<4, 1><<<grid, block, lds2, stream>>>(q);
-    }
-    return hipGetLastError();
+    return rowwin_launch(q, conv_rowwin_kernel<7, 2>, conv_rowwin_kernel<4, 1>, lds2, stream, ev_start, ev_stop);
 }
 
 }  // namespace vstab

@@ -198,40 +198,23 @@ static int conv1_rowwin(vstab_ctx *ctx, bool bf16x3, const float *feats, int B, 
     const Layer &e = NET[0];
     const float *dw = ctx->dev_weights;
     *launched = false;
-    RowWinParams r{};
-    r.in = feats; r.out = out; r.wpk = dw + ctx->enc0_rw; r.bias = dw + ctx->enc_b[0];
-    const long long in_bytes = (long long)B * H * W * Cin * 4;
-    r.in_bytes = (unsigned)std::min<long long>(in_bytes, 0xFFFFFFFFLL);
-    r.B = B; r.Hi = H; r.Wi = W; r.Cs_in = Cin; r.KH = e.k;
-    r.SEGP = rowwin_segp(-e.p, e.k, Cin);
-    r.s_in = e.s; r.off_y = -e.p;
-    r.e_off = -e.p * Cin - rowwin_lead(-e.p, Cin);
-    r.w_a = ((r.e_off % 4) + 4) % 4;
-    r.MB = rowwin_mb(B, Ho, Wo);
-    r.WLEN = round_up(r.s_in * Cin * (64 * r.MB - 1) + r.w_a + r.SEGP, 4);
-    r.Ho = Ho; r.Wo = Wo; r.Cs_out = cs_out; r.c_off = c_off; r.N = N; r.Npad = Npad; r.act = 1;
-    if (in_bytes >= 0x80000000LL || !rowwin_applicable(r)) return VSTAB_OK;
-    const bool b3 = bf16x3 && ctx->enc0_b3 != 0 && conv1_bf16x3_applicable(r);
-    if (b3) r.wpk = dw + ctx->enc0_b3;
+    RowWinDesc d = rowwin_desc(B, H, W, Cin, e.k, e.s, e.p, Ho, Wo, N, Npad, cs_out, c_off, 1);
+    if (!d.ok || ((uintptr_t)feats & 15) != 0) return VSTAB_OK;
+    const bool b3 = bf16x3 && ctx->enc0_b3 != 0 && conv1_bf16x3_geometry_ok(d.main);
+    RowWinParams &r = d.main, &t = d.tail;
+    r.in = t.in = feats; r.out = t.out = out; r.bias = t.bias = dw + ctx->enc_b[0];
+    r.wpk = t.wpk = dw + (b3 ? ctx->enc0_b3 : ctx->enc0_rw);
     auto launch1 = [&](const RowWinParams &q, hipEvent_t a, hipEvent_t b) {
         return b3 ? launch_conv1_bf16x3(q, stream, a, b) : launch_conv_rowwin(q, stream, a, b);
     };
     if (tickets) { r.clear_words = tickets; r.clear_n = SKINNY_MAX_TILES; }
     *launched = true;
-    const int rem = Wo % 128;
-    if (r.MB == 2 && Wo > 128 && rem >= 1 && rem <= 64) {
+    if (d.two) {
         // 128 k + (1..64) columns: k full tiles, then the rest as ONE 64-pixel tile (second launch; events span both)
-        RowWinParams t = r;
-        r.ntile_x = Wo / 128;
-        t.MB = 1; t.ox_base = r.ntile_x * 128; t.ntile_x = 1; t.clear_n = 0;
-        t.WLEN = round_up(t.s_in * Cin * 63 + t.w_a + t.SEGP, 4);
-        if (rowwin_applicable(t)) {
-            HIP_TRY(ctx, launch1(r, ev_a, nullptr));
-            HIP_TRY(ctx, launch1(t, nullptr, ev_b));
-            *kname = b3 ? "conv1_bf16x3_kernel<7, 2> + <4, 1> tail" : "conv_rowwin_kernel<7, 2> + <4, 1> tail";
-            return VSTAB_OK;
-        }
-        r.ntile_x = 0;
+        HIP_TRY(ctx, launch1(r, ev_a, nullptr));
+        HIP_TRY(ctx, launch1(t, nullptr, ev_b));
+        *kname = b3 ? "conv1_bf16x3_kernel<7, 2> + <4, 1> tail" : "conv_rowwin_kernel<7, 2> + <4, 1> tail";
+        return VSTAB_OK;
     }
     HIP_TRY(ctx, launch1(r, ev_a, ev_b));
     if (b3) *kname = r.MB == 2 ? "conv1_bf16x3_kernel<7, 2>" : "conv1_bf16x3_kernel<4, 1>";

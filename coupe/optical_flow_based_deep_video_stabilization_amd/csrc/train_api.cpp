@@ -499,7 +499,7 @@ extern "C" int vstab_conv_forward(const float *x, int B, int Hi, int Wi, int cs_
 // assembly K loop: 0.92 of the MFMA peak at B=8 512x512, where the generic implicit GEMM reaches 0.73) fed by an operand gathered on
 // the device every call -- the host packer's layout, recorded once per geometry as an index table by packing a tensor of indices.
 namespace {
-struct RowWinPlan { RowWinParams r; int32_t *tbl; size_t packed_floats; bool two; RowWinParams t; };
+struct RowWinPlan { RowWinDesc g; int32_t *tbl; size_t packed_floats; };
 
 bool rowwin_plan(int B, int H, int W, int Cin, int cs_w, int cout, int k, int stride, int pad, int cs_y, int cy_off, int act, RowWinPlan &out)
 {
@@ -515,25 +515,9 @@ bool rowwin_plan(int B, int H, int W, int Cin, int cs_w, int cout, int k, int st
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     if (Ho < 1 || Wo < 1 || (long long)B * H * W * Cin * 4 >= 0x80000000LL || (long long)B * Ho * Wo * cs_y * 4 >= 0x80000000LL) return false;
     RowWinPlan d{};
-    RowWinParams &r = d.r;
-    r.in_bytes = (unsigned)((long long)B * H * W * Cin * 4);
-    r.B = B; r.Hi = H; r.Wi = W; r.Cs_in = Cin; r.KH = k;
-    r.SEGP = rowwin_segp(-pad, k, Cin);
-    r.s_in = stride; r.off_y = -pad;
-    r.e_off = -pad * Cin - rowwin_lead(-pad, Cin);
-    r.w_a = ((r.e_off % 4) + 4) % 4;
-    r.MB = rowwin_mb(B, Ho, Wo);
-    r.WLEN = round_up(r.s_in * Cin * (64 * r.MB - 1) + r.w_a + r.SEGP, 4);
-    r.Ho = Ho; r.Wo = Wo; r.Cs_out = cs_y; r.c_off = cy_off; r.N = cout; r.Npad = 64; r.act = act;
-    r.in = reinterpret_cast<const float *>(16);       // (rowwin_applicable tests the alignment of the real pointer at launch time)
-    if (!rowwin_applicable(r)) return false;
-    const int rem = Wo % 128;
-    if (r.MB == 2 && Wo > 128 && rem >= 1 && rem <= 64) {      // 128 k + (1..64) columns: k full tiles, then ONE 64-pixel tile (flownet_forward.cpp's rule)
-        RowWinParams t = r;
-        t.MB = 1; t.ox_base = (Wo / 128) * 128; t.ntile_x = 1;
-        t.WLEN = round_up(t.s_in * Cin * 63 + t.w_a + t.SEGP, 4);
-        if (rowwin_applicable(t)) { r.ntile_x = Wo / 128; d.two = true; d.t = t; }
-    }
+    d.g = rowwin_desc(B, H, W, Cin, k, stride, pad, Ho, Wo, cout, 64, cs_y, cy_off, act);
+    if (!d.g.ok) return false;
+    const RowWinParams &r = d.g.main;
     // the packer's layout as a gather table: pack a filter whose value at (ky, kx, ci, n) is 1 + its index in the [k,k,cs_w,cout] tensor
     const int lead = rowwin_lead(-pad, Cin);
     d.packed_floats = (size_t)k * (r.SEGP / 32) * 64 * 32;
@@ -584,14 +568,10 @@ extern "C" int vstab_conv_rowwin_forward(const float *x, int B, int H, int W, in
     HIP_TRY(nullptr, launch_pack_apply(Wf, d.tbl, (long long)d.packed_floats, wpk, st));
     HIP_TRY(nullptr, hipMemsetAsync(b64, 0, 64 * sizeof(float), st));
     if (bias) HIP_TRY(nullptr, hipMemcpyAsync(b64, bias, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-    RowWinParams r = d.r;
-    r.in = x; r.out = y; r.wpk = wpk; r.bias = b64;
-    if (d.two) {
-        RowWinParams t = d.t;
-        t.in = x; t.out = y; t.wpk = wpk; t.bias = b64;
-        HIP_TRY(nullptr, launch_conv_rowwin(r, st));
-        HIP_TRY(nullptr, launch_conv_rowwin(t, st));
-    } else HIP_TRY(nullptr, launch_conv_rowwin(r, st));
+    RowWinParams &r = d.g.main, &t = d.g.tail;
+    r.in = t.in = x; r.out = t.out = y; r.wpk = t.wpk = wpk; r.bias = t.bias = b64;
+    HIP_TRY(nullptr, launch_conv_rowwin(r, st));
+    if (d.g.two) HIP_TRY(nullptr, launch_conv_rowwin(t, st));
     return VSTAB_OK;
 }
 

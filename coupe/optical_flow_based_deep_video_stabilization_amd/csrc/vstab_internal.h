@@ -202,9 +202,10 @@ struct RowWinParams {
     int Ho, Wo, Cs_out, c_off;
     int N, Npad, act;
     int MB;                 // 2: 128-pixel tiles; 1: 64-pixel tiles (small launches)
-    int out_vec4;           // set by launch_conv_rowwin: the tile leaves through LDS as 16-byte stores
-    int asm_loop;           // set by launch_conv_rowwin: the K loop runs as the assembly block of conv_kloop_gfx950.inc (128-pixel tiles, 6 K-tiles per filter row)
-    int stream_rows;        // set by launch_conv_rowwin: > 0 = a workgroup walks down this many consecutive output rows as one seamless stream of tiles (grid.x = Ho / stream_rows)
+    // the next three are set by the launcher (launch_conv_rowwin or launch_conv1_bf16x3; the latter always clears the last two)
+    int out_vec4;           // the tile leaves through LDS as 16-byte stores (rowwin_launch, rowwin_tile.h)
+    int asm_loop;           // the K loop runs as the assembly block of conv_kloop_gfx950.inc (6 K-tiles per filter row)
+    int stream_rows;        // > 0 = a workgroup walks down this many consecutive output rows as one seamless stream of tiles (grid.x = Ho / stream_rows)
     unsigned *clear_words;  // clear_n > 0: the launch's first workgroup zeroes these words (the forward's split-K tickets; the launches that
     int clear_n;            // use them come later in the stream)
     int ox_base, ntile_x;   // first output column and number of x tiles of this launch (0 tiles = up to the row end): a row whose length
@@ -214,7 +215,12 @@ struct RowWinParams {
 // tile height of the row-window kernel for a launch of Ho x Wo x B output pixels: 64-pixel tiles while 128-pixel ones would not
 // give every CU two workgroups
 inline int rowwin_mb(int B, int Ho, int Wo) { return (long long)B * Ho * ((Wo + 127) / 128) < 512 ? 1 : 2; }
-bool rowwin_applicable(const RowWinParams &p);
+// the geometries the row-window kernels take (descriptors come from rowwin_desc, conv_desc.h); the launchers also want p.in 16-byte aligned
+inline bool rowwin_geometry_ok(const RowWinParams &p)
+{
+    return ((p.s_in * p.Cs_in) % 2 == 0) && ((p.Wi * p.Cs_in) % 4 == 0) && p.N <= 64 && p.Npad == 64 && (p.MB == 1 || p.MB == 2) &&
+           p.WLEN <= (p.MB == 2 ? 7 : 4) * 1024 && (p.WLEN % 4) == 0 && p.in_bytes < 0x80000000u;
+}
 hipError_t rowwin_set_attributes();
 hipError_t launch_conv_rowwin(const RowWinParams &p, hipStream_t stream, hipEvent_t ev_start = nullptr,
                               hipEvent_t ev_stop = nullptr);
@@ -226,8 +232,9 @@ void pack_conv_rowwin(const float *W, const double *scale, int kh, int kw, int c
                       int lead, int segp, float *wpk);
 
 // The same layer on the bf16 MFMA with every operand split into three bf16 pieces, six piece-products per multiply, fp32
-// accumulation (conv1_bf16x3.hip).  Same RowWinParams (wpk = the planes of pack_conv1_bf16x3), same tiles, window and epilogue.
-bool conv1_bf16x3_applicable(const RowWinParams &p);
+// accumulation (conv1_bf16x3.hip).  Same RowWinParams (wpk = the planes of pack_conv1_bf16x3), same tiles, window and epilogue
+// (rowwin_tile.h).  Its geometries: the row-window kernel's with whole trips of two 16-wide K-groups per filter row.
+inline bool conv1_bf16x3_geometry_ok(const RowWinParams &p) { return rowwin_geometry_ok(p) && p.KH >= 1 && (p.SEGP % 32) == 0 && p.SEGP >= 32; }
 hipError_t conv1_bf16x3_set_attributes();
 hipError_t launch_conv1_bf16x3(const RowWinParams &p, hipStream_t stream, hipEvent_t ev_start = nullptr,
                                hipEvent_t ev_stop = nullptr);
