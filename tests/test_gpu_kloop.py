@@ -1,7 +1,9 @@
 """The assembly K loops (csrc/conv_kloop_gfx950.inc) through the C ABI's generic convolution: reductions of one, two, three ... K-tiles
 take the loop's tail-only / body0 / body1 exits for both tile shapes it serves (128x128: cout >= 128, 128x64: cout = 64), rows past
 the end of the GEMM, padded segment tails and out-of-image taps ride on the EXEC-narrowed validity test.  Reference: torch conv2d in
-fp64 on the CPU.  (The first layer's row-window loop is reached through the network only: tests/test_gpu_parity.py, test_gpu_network_property.py.)"""
+fp64 on the CPU.  Every case here is whole pixels at the symmetric-pad output size; channel slices, the four epilogues, the bias routes,
+the dword-gather variant and one more output row / column of the same entry point are in tests/test_gpu_train_conv_edges.py.  (The first
+layer's row-window loops: the stream form below, the network in tests/test_gpu_parity.py, its other paths in tests/test_gpu_rowwin_shapes.py.)"""
 import pytest
 import torch
 import torch.nn.functional as F
