@@ -5,7 +5,8 @@ of 8 TB/s.  Prints one JSON line.  AffineTransformer with the bilinear sampler i
 --backward adds the gradients of the affine bilinear transformer at the same shape (rows "backward"): d img (four global atomics
 per pixel-channel), d theta, both together, and torch's own grid_sample backward (NCHW, bilinear, zeros, align_corners=True) for scale -- an independent implementation of a comparable op,
 not a gate; and the gradients of ElasticTransformer (g = 4, bilinear) at the same shape (rows "elastic_g4_*": time and algorithmic
-bytes only -- the thin-plate spline is bound by logf, not by HBM, so a fraction of 8 TB/s would say nothing).
+bytes only -- the thin-plate spline is bound by logf, not by HBM, so a fraction of 8 TB/s would say nothing); and those of warp.py's
+homography warp under a near-identity homography (rows "homography_*": d img, d M, both).
 --volume adds the 3-D volume transformer (rows "volume"): AffineVolumeTransformer at B = 4, 256^3, C = 1 under an oblique rotation of
 about 10 degrees plus a small shift -- forward by theta, d vol, d theta, both gradients -- with torch's 5-D grid_sample (bilinear,
 zeros, align_corners=True) forward timed interleaved for scale.  The forward counts 8 algorithmic bytes per output voxel."""
@@ -86,6 +87,19 @@ def backward_rows(img, th6, out_size, iters, warmup):
 
     us = time_interleaved({"d_img": run_tps(True, False), "d_theta": run_tps(False, True), "both": run_tps(True, True)}, iters, warmup)
     rows.update({f"elastic_g4_{k}": {"us": round(v, 1), "alg_bytes": int(nbytes[k] * npix)} for k, v in us.items()})
+    # warp.py's homography warp (plain form): M = the canonical-to-pixel map of the frame times a near-identity homography; the
+    # same bytes per pixel as the affine rows
+    ref = torch.tensor([[(W - 1) / 2, 0.0, (W - 1) / 2], [0.0, (H - 1) / 2, (H - 1) / 2], [0.0, 0.0, 1.0]])
+    pM = torch.eye(3).repeat(B, 1, 1) + (torch.rand(B, 3, 3, generator=torch.Generator().manual_seed(6)) - 0.5) * 0.02
+    M = torch.matmul(ref, pM).cuda()
+
+    def run_h(need_img, need_M):
+        return lambda: training.homography_warp_backward(img, M, dout, out_size, need_img=need_img, need_M=need_M)
+
+    us = time_interleaved({"d_img": run_h(True, False), "d_M": run_h(False, True), "both": run_h(True, True)}, iters, warmup)
+    hb = {"d_img": 36.0, "d_M": 24.0, "both": 48.0}
+    rows.update({f"homography_{k}": {"us": round(v, 1), "alg_bytes": int(hb[k] * npix),
+                                     "frac_8TBs": round(hb[k] * npix / (v * 1e-6) / 1e9 / PEAK_GBS, 3)} for k, v in us.items()})
     return rows
 
 

@@ -77,6 +77,12 @@ EXPORTS = {
                                             [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "vstab_transform_image": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p]),
     "vstab_vec2mtrx": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_homography_warp_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "vstab_homography_warp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_transform_image_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_vec2mtrx_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_vgg16_load": (C.c_int, [C.c_void_p, C.POINTER(VstabTensor), C.c_int]),
     "vstab_vgg16_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "vstab_vgg16_shapes": (C.c_int, [C.c_int, C.c_int, c_int32_p]),

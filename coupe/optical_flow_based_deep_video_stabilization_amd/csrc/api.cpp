@@ -533,6 +533,57 @@ extern "C" int vstab_vec2mtrx(const float *p, int B, int dim, int warp_approx, f
     return VSTAB_OK;
 }
 
+// ---- backward of warp.py's samplers (sampler_ops.hip): conventions of vstab_st_transform_backward
+extern "C" size_t vstab_homography_warp_backward_workspace_bytes(int B, int Hi, int Wi, int C, int oh, int ow)
+{
+    if (!stx_shape_ok(B, Hi, Wi, C, oh, ow)) return 0;
+    return homography_warp_backward_ws_bytes(B, Hi, Wi, C, oh, ow);
+}
+
+// `ref` null: vstab_homography_warp_backward (mat = M), else vstab_transform_image_backward (mat = pM)
+static int homography_backward(const char *who, const float *img, int B, int Hi, int Wi, int C, const float *mat, const float *ref,
+                               const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_mat, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (!stx_shape_ok(B, Hi, Wi, C, oh, ow) || (long long)B * Hi * Wi * C > 0x7fffffffLL)
+        return fail(nullptr, VSTAB_E_SHAPE, "%s: bad shape (B <= 65535, B*Hi*Wi*C < 2^31)", who);
+    if (!d_img && !d_mat) return fail(nullptr, VSTAB_E_SHAPE, "%s: d_img and the matrix gradient are both NULL", who);
+    if (d_mat) {
+        const size_t need = homography_warp_backward_ws_bytes(B, Hi, Wi, C, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "%s: workspace needs %zu bytes", who, need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "%s: workspace must be 8-byte aligned", who);
+    }
+    HIP_TRY(nullptr, launch_homography_warp_backward(img, B, Hi, Wi, C, mat, ref, dout, oh, ow, d_img, accumulate ? 1 : 0, d_mat,
+                                                     (double *)workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_homography_warp_backward(const float *img, int B, int Hi, int Wi, int C, const float *M, const float *dout, int oh, int ow,
+                                              float *d_img, int accumulate, float *d_M, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!img || !M || !dout) return fail(nullptr, VSTAB_E_STATE, "homography_warp_backward: NULL buffer");
+    return homography_backward("homography_warp_backward", img, B, Hi, Wi, C, M, nullptr, dout, oh, ow, d_img, accumulate, d_M, workspace,
+                               workspace_bytes, stream);
+}
+
+extern "C" int vstab_transform_image_backward(const float *img, int B, int Hi, int Wi, int C, const float *ref, const float *pM, const float *dout,
+                                              int oh, int ow, float *d_img, int accumulate, float *d_pM, void *workspace, size_t workspace_bytes,
+                                              void *stream)
+{
+    if (!img || !ref || !pM || !dout) return fail(nullptr, VSTAB_E_STATE, "transform_image_backward: NULL buffer");
+    return homography_backward("transform_image_backward", img, B, Hi, Wi, C, pM, ref, dout, oh, ow, d_img, accumulate, d_pM, workspace,
+                               workspace_bytes, stream);
+}
+
+extern "C" int vstab_vec2mtrx_backward(const float *p, int B, int dim, int warp_approx, const float *d_out, float *d_p, void *stream)
+{
+    if (!p || !d_out || !d_p) return fail(nullptr, VSTAB_E_STATE, "vec2mtrx_backward: NULL buffer");
+    if (B < 1 || (dim != 8 && dim != 6) || warp_approx < 1 || warp_approx > 64)
+        return fail(nullptr, VSTAB_E_SHAPE, "vec2mtrx_backward: p must be [B,8] or [B,6], 1 <= warpApprox <= 64");
+    HIP_TRY(nullptr, launch_vec2mtrx_backward(p, B, dim, warp_approx, d_out, d_p, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
 extern "C" int vstab_scale_shift(const float *x, long long npix, int C, float scale, const float *mean, float *out, void *stream)
 {
     if (!x || !mean || !out) return fail(nullptr, VSTAB_E_STATE, "scale_shift: NULL buffer");

@@ -6,7 +6,8 @@
 // function (st_axis in st_axis.h, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta,
 // explicit-coordinate and thin-plate-spline sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel and, for the spline,
 // st3_tile_tps_bwd_kernel / st_pixel_tps_bwd_kernel, at the end of the file) that calls the same functions; its d img is summed by
-// float atomics and depends on their arrival order in its last bits, its d theta is reproducible.
+// float atomics and depends on their arrival order in its last bits, its d theta is reproducible.  The homography source has its own
+// backward arithmetic (homog_bwd_point / homog3_bwd_point, d M [B,9]) on the same two kernel skeletons, and vec2mtrx its own kernel.
 // -ffp-contract=off keeps the weight arithmetic the reference's op-by-op fp32 sequence.
 #include "vstab_internal.h"
 #include "hbm_profile.h"
@@ -88,14 +89,26 @@ __device__ __forceinline__ Taps st_taps(const Axis &X, const Axis &Y)
 
 __device__ __forceinline__ Taps st_taps(float xn, float yn, int H, int W) { return st_taps(st_axis(xn, W), st_axis(yn, H)); }
 
-__device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, int oy, double dsx, double dsy, int Hi, int Wi)
+// the homography at grid point (ox, oy): the grid values X, Y, the products before the division xh, yh, zs = zh + 1e-8f (which the
+// backward's chain rule needs) and the source pixel coordinates xw, yw
+struct HomogPt { float X, Y, xh, yh, zs, xw, yw; };
+
+__device__ __forceinline__ HomogPt homog_coords(const float *__restrict__ m, int ox, int oy, double dsx, double dsy)
 {
-    const float X = (float)(-1.0 + (double)ox * dsx);
-    const float Y = (float)(-1.0 + (double)oy * dsy);
-    const float xh = (m[0] * X + m[1] * Y) + m[2];
-    const float yh = (m[3] * X + m[4] * Y) + m[5];
-    const float zh = (m[6] * X + m[7] * Y) + m[8];
-    const float xw = xh / (zh + 1e-8f), yw = yh / (zh + 1e-8f);
+    HomogPt q;
+    q.X = (float)(-1.0 + (double)ox * dsx);
+    q.Y = (float)(-1.0 + (double)oy * dsy);
+    q.xh = (m[0] * q.X + m[1] * q.Y) + m[2];
+    q.yh = (m[3] * q.X + m[4] * q.Y) + m[5];
+    const float zh = (m[6] * q.X + m[7] * q.Y) + m[8];
+    q.zs = zh + 1e-8f;
+    q.xw = q.xh / q.zs; q.yw = q.yh / q.zs;
+    return q;
+}
+
+__device__ __forceinline__ Taps homog_taps(const HomogPt &q, int Hi, int Wi)
+{
+    const float xw = q.xw, yw = q.yw;
     const float xf = floorf(xw), xc = ceilf(xw), yf = floorf(yw), yc = ceilf(yw);
     // clamp before the int conversion (out-of-range float->int is undefined); anything outside is "outside"
     const float lim = 1.0e9f;
@@ -107,6 +120,11 @@ __device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, 
     t.xa = min(max(xfi, 0), Wi - 1); t.xb = min(max(xci, 0), Wi - 1);
     t.ya = min(max(yfi, 0), Hi - 1); t.yb = min(max(yci, 0), Hi - 1);
     return t;
+}
+
+__device__ __forceinline__ Taps homog_taps(const float *__restrict__ m, int ox, int oy, double dsx, double dsy, int Hi, int Wi)
+{
+    return homog_taps(homog_coords(m, ox, oy, dsx, dsy), Hi, Wi);
 }
 
 template <bool HOMOG>
@@ -754,18 +772,114 @@ __device__ __forceinline__ void st3_bwd_point(const rgb3 *b, float *di, const rg
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Backward of XS_HOMOG (warp.transformImage / transformCropImage / warpImage): what TensorFlow's autodiff gives for warp.py:46-86 and
+// 89-129.  The coordinates and taps are homog_coords / homog_taps, the forward's, so every floor, ceil and inside decision is shared.
+// floor, ceil and to_int32 have zero derivative and there is no clip: with xr = xw - floor(xw), yr likewise, per channel
+//   d out / d xw = (UR - UL) (1 - yr) + (BR - BL) yr,   d out / d yw = (BL - UL) (1 - xr) + (BR - UR) xr,   a tap outside reading 0.
+// Where xw is an exact integer floor == ceil, so UL == UR and the x slope is 0: the reference's behaviour, kept.
+//   d img   the gather's adjoint: (1-xr)(1-yr), xr(1-yr), (1-xr)yr, xr yr times dout added to the four taps by float atomics, nothing
+//           for a tap outside; with floor == ceil two taps of one address both add, as the reference's gather gradient does.
+//   d M     [B,9]: gx, gy = the channel-summed slopes times dout; d xh = gx / zs, d yh = gy / zs, d zh = -(gx xh + gy yh) / zs^2, the
+//           nine products with (X, Y, 1) in double from the forward's fp32 xh, yh, zs, X, Y; summed like d theta (part[workgroup][9],
+//           st_theta_final_kernel<9>).  Composed form (ref given): M = ref . pM by compose3 as in the forward, and the final kernel
+//           stores d pM = ref^T . d M.  A pixel none of whose taps is inside (a non-finite xw, yw among them) contributes nothing.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ void homog_slope(const Taps &t, float UL, float UR, float BL, float BR, float g, float &gx, float &gy)
+{
+    const float xr = t.w0, yr = t.w1;
+    gx = gx + ((UR - UL) * (1.0f - yr) + (BR - BL) * yr) * g;
+    gy = gy + ((BL - UL) * (1.0f - xr) + (BR - UR) * xr) * g;
+}
+
+__device__ __forceinline__ void homog_accum(double *acc, float gxf, float gyf, const HomogPt &q)
+{
+    if (gxf == 0.0f && gyf == 0.0f) return;
+    const double iz = 1.0 / (double)q.zs;
+    const double gz = -((double)gxf * (double)q.xh + (double)gyf * (double)q.yh) * iz * iz;
+    const double gx = (double)gxf * iz, gy = (double)gyf * iz;
+    acc[0] += gx * (double)q.X; acc[1] += gx * (double)q.Y; acc[2] += gx;
+    acc[3] += gy * (double)q.X; acc[4] += gy * (double)q.Y; acc[5] += gy;
+    acc[6] += gz * (double)q.X; acc[7] += gz * (double)q.Y; acc[8] += gz;
+}
+
+// one output pixel, any channel count; gx, gy = d out / d (xw, yw) summed over the channels times dout (0 without DCOORD)
+template <bool DIMG, bool DCOORD>
+__device__ __forceinline__ void homog_bwd_point(const float *__restrict__ b, float *di, const float *__restrict__ g, int W, int C, const Taps &t,
+                                                float &gx, float &gy)
+{
+    gx = gy = 0.0f;
+    const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+    if (!(v00 || v01 || v10 || v11)) return;
+    const long long i00 = ((long long)t.ya * W + t.xa) * C, i01 = ((long long)t.ya * W + t.xb) * C;
+    const long long i10 = ((long long)t.yb * W + t.xa) * C, i11 = ((long long)t.yb * W + t.xb) * C;
+    const float xr = t.w0, yr = t.w1;
+    const float w00 = (1.0f - xr) * (1.0f - yr), w01 = xr * (1.0f - yr), w10 = (1.0f - xr) * yr, w11 = xr * yr;
+    for (int c = 0; c < C; ++c) {
+        const float gc = g[c];
+        if (DCOORD) homog_slope(t, v00 ? b[i00 + c] : 0.f, v01 ? b[i01 + c] : 0.f, v10 ? b[i10 + c] : 0.f, v11 ? b[i11 + c] : 0.f, gc, gx, gy);
+        if (DIMG) {
+            if (v00) atomicAdd(di + i00 + c, w00 * gc);
+            if (v01) atomicAdd(di + i01 + c, w01 * gc);
+            if (v10) atomicAdd(di + i10 + c, w10 * gc);
+            if (v11) atomicAdd(di + i11 + c, w11 * gc);
+        }
+    }
+}
+
+// 3-channel frames (3 H W < 2^31: host)
+template <bool DIMG, bool DCOORD>
+__device__ __forceinline__ void homog3_bwd_point(const rgb3 *b, float *di, const rgb3 g, int W, const Taps &t, float &gx, float &gy)
+{
+    gx = gy = 0.0f;
+    const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
+    if (!(v00 || v01 || v10 || v11)) return;
+    if (DCOORD) {
+        const rgb3 z = {0.f, 0.f, 0.f};
+        const rgb3 UL = v00 ? b[t.ya * W + t.xa] : z, UR = v01 ? b[t.ya * W + t.xb] : z;
+        const rgb3 BL = v10 ? b[t.yb * W + t.xa] : z, BR = v11 ? b[t.yb * W + t.xb] : z;
+        homog_slope(t, UL.r, UR.r, BL.r, BR.r, g.r, gx, gy);
+        homog_slope(t, UL.g, UR.g, BL.g, BR.g, g.g, gx, gy);
+        homog_slope(t, UL.b, UR.b, BL.b, BR.b, g.b, gx, gy);
+    }
+    if (DIMG) {
+        const float xr = t.w0, yr = t.w1;
+        auto add = [&](int y, int x, bool valid, float w) {
+            if (!valid) return;
+            float *q = di + ((long long)y * W + x) * 3;
+            atomicAdd(q, w * g.r); atomicAdd(q + 1, w * g.g); atomicAdd(q + 2, w * g.b);
+        };
+        add(t.ya, t.xa, v00, (1.0f - xr) * (1.0f - yr)); add(t.ya, t.xb, v01, xr * (1.0f - yr));
+        add(t.yb, t.xa, v10, (1.0f - xr) * yr); add(t.yb, t.xb, v11, xr * yr);
+    }
+}
+
+// doubles per d theta / d M partial row: the theta sources' 8 (the affine one uses six of them), the homography's 9
+template <int SRC>
+constexpr int st_part_width() { return SRC == XS_HOMOG ? 9 : 8; }
+
 // any channel count, one thread per pixel (st_pixel_kernel's layout); d img the plain way
 template <int SRC, bool DIMG, bool DCOORD>
 __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restrict__ img, int H, int W, int C, StSrc S, StBwd G, int FH, int FW, unsigned bps)
 {
-    __shared__ double red[4][8];
+    constexpr int NP = st_part_width<SRC>();
+    __shared__ double red[4][NP];
     const int n = (int)(blockIdx.x / bps);
     float th[9];
     st_matrix_wg<SRC>(S, n, th, nullptr);
     const long long p = (long long)(blockIdx.x - (unsigned)n * bps) * 256 + threadIdx.x;
     const bool ok = p < (long long)FH * FW;
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (ok) {
+    double acc[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) acc[k] = 0.0;
+    if (ok && SRC == XS_HOMOG) {
+        const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+        const HomogPt q = homog_coords(th, fx, fy, S.dsx, S.dsy);
+        float gx, gy;
+        homog_bwd_point<DIMG, DCOORD>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
+                                      G.dout + ((long long)n * FH * FW + p) * C, W, C, homog_taps(q, H, W), gx, gy);
+        if (DCOORD) homog_accum(acc, gx, gy, q);
+    } else if (ok) {
         const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
         float xs, ys, xh = 0.f, yh = 0.f, zs = 1.f;
         const float xt = st_grid_t(fx, S.sx), yt = st_grid_t(fy, S.sy);
@@ -783,7 +897,7 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
             }
         }
     }
-    if (DCOORD && SRC == XS_THETA) st_theta_reduce(acc, red, G.part + (long long)blockIdx.x * 8);
+    if (DCOORD && (SRC == XS_THETA || SRC == XS_HOMOG)) st_theta_reduce<NP>(acc, red, G.part + (long long)blockIdx.x * NP);
 }
 
 // 3-channel frames on the tile skeleton (st3_tile_kernel's pixels: a wave instruction works on a 4 x 16 patch)
@@ -791,19 +905,28 @@ template <int SRC, bool DIMG, bool DCOORD>
 __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restrict__ img, int H, int W, StSrc S, StBwd G, int FH, int FW,
                                                            int tiles_x, int tiles_y)
 {
-    constexpr int PPT = StTile::PPT;
-    __shared__ double red[4][8];
+    constexpr int PPT = StTile::PPT, NP = st_part_width<SRC>();
+    __shared__ double red[4][NP];
     const StTile tile(tiles_x, tiles_y);
     const int n = tile.n;
     float th[9];
     st_matrix_wg<SRC>(S, n, th, nullptr);
     const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + (long long)n * H * W;     // 3 B H W < 2^31 (host)
     float *di = DIMG ? G.d_img + (long long)n * H * W * 3 : nullptr;
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double acc[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) acc[k] = 0.0;
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
         if (!(tile.y(j) < FH && tile.x(j) < FW)) continue;
         const int fy = tile.y(j), fx = tile.x(j);
+        if (SRC == XS_HOMOG) {
+            const HomogPt q = homog_coords(th, fx, fy, S.dsx, S.dsy);
+            float gx, gy;
+            homog3_bwd_point<DIMG, DCOORD>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[((long long)n * FH + fy) * FW + fx], W, homog_taps(q, H, W), gx, gy);
+            if (DCOORD) homog_accum(acc, gx, gy, q);
+            continue;
+        }
         float xs, ys, xh = 0.f, yh = 0.f, zs = 1.f;
         const float xt = st_grid_t(fx, S.sx), yt = st_grid_t(fy, S.sy);
         if (SRC == XS_THETA) st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
@@ -820,9 +943,9 @@ __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restri
             }
         }
     }
-    if (DCOORD && SRC == XS_THETA) {
+    if (DCOORD && (SRC == XS_THETA || SRC == XS_HOMOG)) {
         const int tidx = (tile.ty0 / StTile::TH) * tiles_x + tile.tx0 / StTile::TW;
-        st_theta_reduce(acc, red, G.part + ((long long)n * tiles_x * tiles_y + tidx) * 8);
+        st_theta_reduce<NP>(acc, red, G.part + ((long long)n * tiles_x * tiles_y + tidx) * NP);
     }
 }
 
@@ -852,7 +975,8 @@ static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, St
 {
     S.B = B;
     st_steps(S);
-    const bool dimg = G.d_img != nullptr, dcoord = SRC == XS_THETA ? G.part != nullptr : (G.d_x || G.d_y);
+    if (SRC == XS_HOMOG) { S.dsx = S.gw > 1 ? 2.0 / (double)(S.gw - 1) : 0.0; S.dsy = S.gh > 1 ? 2.0 / (double)(S.gh - 1) : 0.0; }      // launch_st's
+    const bool dimg = G.d_img != nullptr, dcoord = (SRC == XS_THETA || SRC == XS_HOMOG) ? G.part != nullptr : (G.d_x || G.d_y);
     int tx, ty;
     dim3 grid;
     long long wgs;
@@ -905,6 +1029,98 @@ hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int 
     S.x = x; S.y = y;
     StBwd G{dout, d_img, d_x, d_y, nullptr};
     return launch_st_bwd<XS_COORDS>(img, B, H, W, C, S, G, oh, ow, stream);
+}
+
+size_t homography_warp_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow)
+{
+    int tx, ty;
+    dim3 grid;
+    long long wgs;
+    st_bwd_plan(B, H, W, C, oh, ow, tx, ty, grid, wgs);
+    return (size_t)wgs * B * 9 * sizeof(double);
+}
+
+// ref == null: M [B,9] is the matrix and d_M its gradient; ref given: M holds pMtrx, the kernels compose ref . pMtrx as the forward
+// does, and d_M receives d pMtrx = ref^T . d (ref . pMtrx)
+hipError_t launch_homography_warp_backward(const float *img, int B, int Hi, int Wi, int C, const float *M, const float *ref, const float *dout,
+                                           int oh, int ow, float *d_img, int accumulate, float *d_M, double *part, hipStream_t stream)
+{
+    if (d_img && !accumulate) {
+        const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * Hi * Wi * C * sizeof(float), stream);
+        if (e != hipSuccess) return e;
+    }
+    StSrc S = st_plain(oh, ow);
+    S.theta = M; S.tdim = 9; S.ref = ref;
+    StBwd G{dout, d_img, nullptr, nullptr, d_M ? part : nullptr};
+    const hipError_t e = launch_st_bwd<XS_HOMOG>(img, B, Hi, Wi, C, S, G, oh, ow, stream);
+    if (e != hipSuccess || !d_M) return e;
+    int tx, ty;
+    dim3 grid;
+    long long wgs;
+    st_bwd_plan(B, Hi, Wi, C, oh, ow, tx, ty, grid, wgs);
+    st_theta_final_kernel<9><<<dim3((unsigned)B), dim3(256), 0, stream>>>(part, (int)wgs, 9, d_M, ref);
+    return hipGetLastError();
+}
+
+// Backward of vec2mtrx_kernel: d p [B,8|6] from d P [B,9].  The forward's recurrence N_i = N_{i-1} A, P += N_i / i! reversed:
+// G_i = dP / i! + G_{i+1} A^T, d A += N_{i-1}^T G_i, which is d A = sum_i 1/i! sum_{j<i} (A^j)^T dP (A^{i-1-j})^T; then d A back through
+// the generator layout (warp.py:28-33).  One thread per sample, in double from the fp32 p (the powers of A kept in a local array:
+// approx <= 64 on the host), rounded to fp32 once.
+constexpr int VEC2MTRX_MAX_APPROX = 64;
+
+__device__ __forceinline__ void mat3_mul(const double *a, const double *b, double *o)
+{
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) o[r * 3 + c] = (a[r * 3] * b[c] + a[r * 3 + 1] * b[3 + c]) + a[r * 3 + 2] * b[6 + c];
+}
+
+__global__ void vec2mtrx_bwd_kernel(const float *__restrict__ p, int B, int dim, int approx, const float *__restrict__ d_out, float *__restrict__ d_p)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= B) return;
+    const float *q = p + (long long)n * dim;
+    double A[9], At[9], dP[9];
+    if (dim == 8) {
+        A[0] = (double)q[2]; A[1] = (double)q[1]; A[2] = (double)q[0];
+        A[3] = (double)q[5]; A[4] = -(double)q[2] - (double)q[6]; A[5] = (double)q[4];
+        A[6] = (double)q[3]; A[7] = (double)q[7]; A[8] = (double)q[6];
+    } else {
+        for (int k = 0; k < 6; ++k) A[k] = (double)q[k];
+        A[6] = A[7] = A[8] = 0.0;
+    }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) At[r * 3 + c] = A[c * 3 + r];
+    for (int k = 0; k < 9; ++k) dP[k] = (double)d_out[(long long)n * 9 + k];
+    double Nt[VEC2MTRX_MAX_APPROX][9];                   // Nt[i] = (A^i)^T
+    double fact = 1.0;                                   // (approx - 1)!
+    for (int k = 0; k < 9; ++k) Nt[0][k] = (k % 4 == 0) ? 1.0 : 0.0;
+    for (int i = 1; i < approx; ++i) {
+        if (i < approx - 1) mat3_mul(At, Nt[i - 1], Nt[i]);          // (N A)^T = A^T N^T
+        fact *= (double)i;
+    }
+    double Gm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, dA[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = approx - 1; i >= 1; --i) {
+        double T[9];
+        mat3_mul(Gm, At, T);
+        for (int k = 0; k < 9; ++k) Gm[k] = dP[k] / fact + T[k];
+        mat3_mul(Nt[i - 1], Gm, T);
+        for (int k = 0; k < 9; ++k) dA[k] += T[k];
+        fact /= (double)i;
+    }
+    float *o = d_p + (long long)n * dim;
+    if (dim == 8) {
+        o[0] = (float)dA[2]; o[1] = (float)dA[1]; o[2] = (float)(dA[0] - dA[4]); o[3] = (float)dA[6];
+        o[4] = (float)dA[5]; o[5] = (float)dA[3]; o[6] = (float)(dA[8] - dA[4]); o[7] = (float)dA[7];
+    } else {
+        for (int k = 0; k < 6; ++k) o[k] = (float)dA[k];
+    }
+}
+
+hipError_t launch_vec2mtrx_backward(const float *p, int B, int dim, int approx, const float *d_out, float *d_p, hipStream_t stream)
+{
+    if (approx < 1 || approx > VEC2MTRX_MAX_APPROX) return hipErrorInvalidValue;
+    vec2mtrx_bwd_kernel<<<dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream>>>(p, B, dim, approx, d_out, d_p);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------

@@ -61,9 +61,12 @@ __device__ __forceinline__ void st_theta_reduce(double *acc, double (*red)[K], d
     if (threadIdx.x < K) part[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-// d theta[n, k] = sum of sample n's `wgs` partials [K]: thread t adds partials t, t + 256, ..., then st_theta_reduce's order
+// d theta[n, k] = sum of sample n's `wgs` partials [K]: thread t adds partials t, t + 256, ..., then st_theta_reduce's order.
+// `left` (K = 9 only; null otherwise): the totals are a 3 x 3 matrix d M of M = left . P, and what is stored is d P = left^T . d M,
+// the three products of an entry in double, (l0 d0 + l1 d1) + l2 d2, rounded to fp32 once.
 template <int K>
-__global__ __launch_bounds__(256) void st_theta_final_kernel(const double *__restrict__ part, int wgs, int tdim, float *__restrict__ d_theta)
+__global__ __launch_bounds__(256) void st_theta_final_kernel(const double *__restrict__ part, int wgs, int tdim, float *__restrict__ d_theta,
+                                                             const float *__restrict__ left = nullptr)
 {
     __shared__ double red[4][K], tot[K];
     const int n = blockIdx.x;
@@ -75,6 +78,14 @@ __global__ __launch_bounds__(256) void st_theta_final_kernel(const double *__res
         for (int k = 0; k < K; ++k) acc[k] += part[((long long)n * wgs + i) * K + k];
     st_theta_reduce<K>(acc, red, tot);
     __syncthreads();
+    if (K == 9 && left) {
+        if (threadIdx.x < 9) {
+            const int i = threadIdx.x / 3, j = threadIdx.x - 3 * i;
+            d_theta[(long long)n * 9 + threadIdx.x] =
+                (float)(((double)left[i] * tot[j] + (double)left[3 + i] * tot[3 + j]) + (double)left[6 + i] * tot[6 + j]);
+        }
+        return;
+    }
     if ((int)threadIdx.x < tdim) d_theta[(long long)n * tdim + threadIdx.x] = (float)tot[threadIdx.x];
 }
 

@@ -418,6 +418,12 @@ hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, i
                                         int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream);
 hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y, const float *dout, int oh,
                                      int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream);
+// backward of launch_homography_warp (d img, d M [B,9]; with `ref`: M holds pMtrx and d_M receives d pMtrx = ref^T . d (ref . pMtrx)) and
+// of launch_vec2mtrx (d p [B,dim] from d_out [B,9]); conventions as launch_st_transform_backward, `part`: homography_warp_backward_ws_bytes
+size_t homography_warp_backward_ws_bytes(int B, int Hi, int Wi, int C, int oh, int ow);
+hipError_t launch_homography_warp_backward(const float *img, int B, int Hi, int Wi, int C, const float *M, const float *ref, const float *dout,
+                                           int oh, int ow, float *d_img, int accumulate, float *d_M, double *part, hipStream_t stream);
+hipError_t launch_vec2mtrx_backward(const float *p, int B, int dim, int approx, const float *d_out, float *d_p, hipStream_t stream);
 // ElasticTransformer: the source coordinates the forward samples at, x_out, y_out [B*oh*ow]; and the backward of its bilinear
 // sampler, conventions as launch_st_transform_backward, `part`: st_elastic_backward_ws_bytes of scratch for the d theta partials
 hipError_t launch_st_elastic_coords(const float *theta, int B, int g, const float *linv_t, int oh, int ow, float *x_out, float *y_out,

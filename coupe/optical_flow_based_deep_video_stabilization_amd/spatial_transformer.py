@@ -10,7 +10,8 @@ Differentiable (torch.autograd, HIP backward kernels): `AffineTransformer.transf
 elastic one: the control-point offsets), and `bilinear_interp` with respect to the image, `x` and `y`; `AffineVolumeTransformer.transform` with respect to the volume and `theta`, `bilinear_interp3d` with respect to the
 volume, `x`, `y` and `z`.  The gradient of the image or volume is summed by float atomics (last bits may differ between runs); those of `theta`, `x`, `y`,
 `z` are bit-reproducible.  NOT differentiable -- the result has no `grad_fn`, whatever requires grad: `bicubic_interp` and
-`interp_method='bicubic'` (on `ElasticTransformer` too), the symmetric-pad transformers, `ElasticTransformer.transform_coords`."""
+`interp_method='bicubic'` (on `ElasticTransformer` too), the symmetric-pad transformers, `ElasticTransformer.transform_coords`.
+The homography samplers of the reference's `warp.py` (`warp.transformImage` and its kin) are differentiable too: see `warp.py`."""
 from __future__ import annotations
 
 import ctypes

@@ -2,7 +2,8 @@
 `lossterm` / `masked_MSE` (main:188-210, "main" = main_flownetS_pyramid_noprevloss_dataloader.py), the total-variation
 terms and `loss_main` (main:213-275) with their gradient with respect to every predicted flow; filter / input gradients
 of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and its backward; the resamplers' adjoints; the
-gradients of the bilinear spatial transformers (`st_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`).
+gradients of the bilinear spatial transformers (`st_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`)
+and of warp.py's homography warp and matrix exponential (`homography_warp_backward`, `vec2mtrx_backward`).
 `train_step.Trainer` strings them into the whole step (forward, loss, backward, Adam: main:184-185, 333-335).
 
 Everything runs in the HIP library (csrc/train_ops.hip); there is no CPU path."""
@@ -258,6 +259,56 @@ def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, nee
                                                  d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
                                                  runtime.stream_ptr()))
     return (d_img if need_img else None), d_theta
+
+
+def homography_warp_backward(img, M, dout, out_size, need_img: bool = True, need_M: bool = True, d_img=None, ref=None):
+    """Gradients of warp.warpImage (ref None: M [B,9] or [B,3,3] is the composed matrix) or of warp.transformImage / transformCropImage
+    (ref [9] or [3,3] the refMtrx: M is pMtrx and the kernels compose ref . pMtrx as the forward does) for the output gradient dout
+    [B,oh,ow,C]: (d img [B,Hi,Wi,C] or None, d M -- with ref: d pMtrx = ref^T . d (ref . pMtrx) -- [B,3,3] or None).  d_img, need_img
+    as in st_transform_backward; need_M False skips the matrix gradient's work.  d img is summed by float atomics (its last bits may
+    differ between runs); the matrix gradient is bit-reproducible.  ref gets no gradient."""
+    need_img = need_img or d_img is not None
+    img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
+    if not torch.is_tensor(M) or M.device != img.device or M.dtype != torch.float32 or M.numel() != 9 * B:
+        raise ValueError("M must be a float32 tensor [B,9] or [B,3,3] beside img")
+    M = M.contiguous()
+    if ref is not None:
+        if not torch.is_tensor(ref) or ref.device != img.device or ref.dtype != torch.float32 or ref.numel() != 9:
+            raise ValueError("ref must be a float32 tensor of 9 elements beside img")
+        ref = ref.contiguous()
+    L = _lib.lib()
+    d_M, ws, n = None, None, 0
+    if need_M:
+        d_M = torch.empty((B, 3, 3), dtype=torch.float32, device=img.device)
+        n = int(L.vstab_homography_warp_backward_workspace_bytes(B, H, W, C, oh, ow))
+        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
+    tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_M.data_ptr() if need_M else None,
+            ws.data_ptr() if need_M else None, n, runtime.stream_ptr())
+    with torch.cuda.device(img.device):
+        if ref is None:
+            _lib.check(L.vstab_homography_warp_backward(img.data_ptr(), B, H, W, C, M.data_ptr(), *tail))
+        else:
+            _lib.check(L.vstab_transform_image_backward(img.data_ptr(), B, H, W, C, ref.data_ptr(), M.data_ptr(), *tail))
+    return (d_img if need_img else None), d_M
+
+
+def vec2mtrx_backward(p, d_out, warp_type, warp_approx):
+    """Gradient of warp.vec2mtrx: p [B,8] (warp_type 'homography') or [B,6] ('affine'), d_out [B,3,3] the gradient of the matrix ->
+    d p of p's shape.  In double from the fp32 p, rounded once; bit-reproducible."""
+    dim = {"homography": 8, "affine": 6}.get(warp_type)
+    if dim is None:
+        raise ValueError("warp_type must be 'homography' or 'affine'")
+    if not torch.is_tensor(p) or not p.is_cuda or p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != dim:
+        raise ValueError(f"p must be a float32 CUDA tensor [B,{dim}]")
+    B = p.shape[0]
+    if not torch.is_tensor(d_out) or d_out.device != p.device or d_out.dtype != torch.float32 or d_out.numel() != 9 * B:
+        raise ValueError("d_out must be a float32 tensor [B,3,3] beside p")
+    p, d_out = p.contiguous(), d_out.contiguous()
+    d_p = torch.empty_like(p)
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().vstab_vec2mtrx_backward(p.data_ptr(), B, dim, int(warp_approx), d_out.data_ptr(), d_p.data_ptr(),
+                                                      runtime.stream_ptr()))
+    return d_p
 
 
 def st_elastic_transform_backward(img, theta, dout, out_size, g, linv_t, need_img: bool = True, need_theta: bool = True, d_img=None):

@@ -2,11 +2,19 @@
 reference: only `import warp` at config.py:3, and `config.py` never defines the `warpType`,
 `refMtrx`, `warpApprox`, `batch_size`, `height`, `width` fields these functions read).  `config` is
 any object carrying those attributes; images and parameters are float32 CUDA tensors.  The
-arithmetic runs in HIP kernels (csrc/sampler_ops.hip); `fit` is host numpy like the original."""
+arithmetic runs in HIP kernels (csrc/sampler_ops.hip); `fit` is host numpy like the original.
+
+Differentiable (torch.autograd, HIP backward kernels): `vec2mtrx` with respect to `p`; `warpImage` with respect to the image and `M`;
+`transformImage` and `transformCropImage` with respect to the image and `pMtrx` (`refMtrx` is configuration and gets no gradient);
+`compose` and `inverse` are torch arithmetic.  floor, ceil and the int casts have zero derivative, so where a source coordinate is an
+exact integer that axis' slope is 0, as in the reference.  The image gradient is summed by float atomics (last bits may differ between
+runs); those of `M`, `pMtrx` and `p` are bit-reproducible.  The autograd path is taken only when gradients are enabled and an input
+requires grad; otherwise the calls are the forward launches alone and the results carry no `grad_fn`."""
 from __future__ import annotations
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
 
@@ -41,11 +49,39 @@ def _f32_cuda(t, name):
     return t.to(torch.float32).contiguous()
 
 
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def _vec2mtrx_call(p, dim, approx):
+    B = p.shape[0]
+    out = torch.empty((B, 3, 3), dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().vstab_vec2mtrx(p.data_ptr(), B, dim, approx, out.data_ptr(), runtime.stream_ptr()))
+    return out
+
+
+class _Vec2MtrxFn(torch.autograd.Function):
+    """vec2mtrx with its HIP backward (training.vec2mtrx_backward)."""
+
+    @staticmethod
+    def forward(ctx, p, warp_type, dim, approx):
+        ctx.save_for_backward(p)
+        ctx.warp_type, ctx.approx = warp_type, approx
+        return _vec2mtrx_call(p, dim, approx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        from . import training
+        (p,) = ctx.saved_tensors
+        return training.vec2mtrx_backward(p, d_out, ctx.warp_type, ctx.approx), None, None, None
+
+
 def vec2mtrx(config, p):
     """p [B,8] (homography: sl(3) generator, warp.py:28-30) or [B,6] (affine, :31-34) -> [B,3,3]
-    Taylor matrix exponential with config.warpApprox terms (:37-42)."""
+    Taylor matrix exponential with config.warpApprox terms (:37-42).  Differentiable with respect to p."""
     p = _f32_cuda(p, "p")
-    B = p.shape[0]
     if config.warpType == "homography":
         dim = 8
     elif config.warpType == "affine":
@@ -54,42 +90,69 @@ def vec2mtrx(config, p):
         raise AssertionError("warpType must be 'homography' or 'affine'")
     if p.shape[1] != dim:
         raise ValueError(f"p must be [B,{dim}] for warpType={config.warpType}")
-    out = torch.empty((B, 3, 3), dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        _lib.check(_lib.lib().vstab_vec2mtrx(p.data_ptr(), B, dim, int(config.warpApprox), out.data_ptr(),
-                                             runtime.stream_ptr()))
+    if _wants_grad(p):
+        return _Vec2MtrxFn.apply(p, config.warpType, dim, int(config.warpApprox))
+    return _vec2mtrx_call(p, dim, int(config.warpApprox))
+
+
+def _warp_call(image, mat, ref, oh, ow):
+    """ref None: mat [B,9] is M = refMtrx . pMtrx; otherwise mat is pMtrx and refMtrx . pMtrx (warp.py:48-49, 91-92: a tf.matmul in the
+    reference) is composed inside the warp launch -- every product and sum rounded to fp32 -- not by a library GEMM in front of it."""
+    B, Hi, Wi, Cc = image.shape
+    out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=image.device)
+    with torch.cuda.device(image.device):
+        if ref is None:
+            _lib.check(_lib.lib().vstab_homography_warp(image.data_ptr(), B, Hi, Wi, Cc, mat.data_ptr(), out.data_ptr(),
+                                                        oh, ow, runtime.stream_ptr()))
+        else:
+            _lib.check(_lib.lib().vstab_transform_image(image.data_ptr(), B, Hi, Wi, Cc, ref.data_ptr(), mat.data_ptr(), out.data_ptr(),
+                                                        oh, ow, runtime.stream_ptr()))
     return out
+
+
+class _WarpFn(torch.autograd.Function):
+    """The homography warp with its HIP backward (training.homography_warp_backward): d image and d M, or with ref d pMtrx."""
+
+    @staticmethod
+    def forward(ctx, image, mat, ref, oh, ow):
+        ctx.save_for_backward(image, mat)
+        ctx.ref, ctx.out_size = ref, (oh, ow)
+        return _warp_call(image, mat, ref, oh, ow)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        image, mat = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_img, d_mat = training.homography_warp_backward(image, mat, dout, ctx.out_size, need_img=need[0], need_M=need[1], ref=ctx.ref)
+        return d_img, (d_mat.reshape(mat.shape) if d_mat is not None else None), None, None, None
+
+
+def _warp(image, mat, ref, oh, ow):
+    if _wants_grad(image, mat):
+        return _WarpFn.apply(image, mat, ref, oh, ow)
+    return _warp_call(image, mat, ref, oh, ow)
 
 
 def warpImage(image, M, oh, ow):
     """The warp of transformImage given the composed matrices M = refMtrx . pMtrx [B,3,3] (not a reference symbol: the reference
-    composes inside transformImage, as `transformImage` below does inside its launch)."""
+    composes inside transformImage, as `transformImage` below does inside its launch).  Differentiable with respect to image and M."""
     image = _f32_cuda(image, "image")
-    B, Hi, Wi, Cc = image.shape
-    M = _f32_cuda(M, "matrix").reshape(B, 9)
-    out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=image.device)
-    with torch.cuda.device(image.device):
-        _lib.check(_lib.lib().vstab_homography_warp(image.data_ptr(), B, Hi, Wi, Cc, M.data_ptr(), out.data_ptr(),
-                                                    oh, ow, runtime.stream_ptr()))
-    return out
+    M = _f32_cuda(M, "matrix").reshape(image.shape[0], 9)
+    return _warp(image, M, None, oh, ow)
 
 
 def _warp_ref(image, ref, pMtrx, oh, ow):
-    """refMtrx . pMtrx (warp.py:48-49, 91-92: a tf.matmul in the reference) is composed inside the warp launch -- every product and
-    sum rounded to fp32 -- not by a library GEMM in front of it."""
     image = _f32_cuda(image, "image")
-    B, Hi, Wi, Cc = image.shape
-    pM = _f32_cuda(pMtrx, "pMtrx").to(image.device).reshape(B, 9)
-    ref = _f32_cuda(ref, "refMtrx").to(image.device).reshape(9)
-    out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=image.device)
-    with torch.cuda.device(image.device):
-        _lib.check(_lib.lib().vstab_transform_image(image.data_ptr(), B, Hi, Wi, Cc, ref.data_ptr(), pM.data_ptr(), out.data_ptr(),
-                                                    oh, ow, runtime.stream_ptr()))
-    return out
+    pM = _f32_cuda(pMtrx, "pMtrx").to(image.device).reshape(image.shape[0], 9)
+    ref = _f32_cuda(ref, "refMtrx").to(image.device).reshape(9).detach()          # configuration: no gradient
+    return _warp(image, pM, ref, oh, ow)
 
 
 def transformImage(config, image, pMtrx):
-    """image [B,H,W,3] warped by refMtrx . pMtrx on the canonical [-1,1]^2 grid (warp.py:46-86)."""
+    """image [B,H,W,3] warped by refMtrx . pMtrx on the canonical [-1,1]^2 grid (warp.py:46-86).  Differentiable with respect to image
+    and pMtrx; refMtrx is configuration."""
     return _warp_ref(image, config.refMtrx, pMtrx, int(config.height), int(config.width))
 
 

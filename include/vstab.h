@@ -210,8 +210,8 @@ VSTAB_API int vstab_host_tps_linv(int g, float *linv_t, int cap);
 VSTAB_API int vstab_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                          int interp, float *out, int oh, int ow, void *stream);
 /* ---- backward of the BILINEAR sampler: vstab_st_transform (affine and projective) and vstab_st_bilinear_interp.  These two are the
- * differentiable samplers besides the thin-plate spline (further down); bicubic, the symmetric-pad transformers and the homography
- * warps have no backward.
+ * differentiable samplers besides the thin-plate spline and the homography warps (further down); bicubic and the symmetric-pad
+ * transformers have no backward.
  * What TensorFlow's autodiff gives for ST:902-964 / 438-452 / 578-608: floor and the casts have zero derivative, the clip passes the
  * gradient where -1 <= x <= W inclusive (0 outside and for NaN), taps on the zero border receive nothing; coordinates and taps are
  * the forward's fp32 values.  img, B, H, W, C, theta | x, y, oh, ow as in the forward (B <= 65535, B*H*W*C < 2^31);
@@ -300,6 +300,30 @@ VSTAB_API int vstab_transform_image(const float *img, int B, int Hi, int Wi, int
 /* warp.vec2mtrx (warp.py:25-43): p [B,8] (homography, sl(3) generator) or [B,6] (affine) -> [B,9]
  * Taylor matrix exponential with `warp_approx` terms. */
 VSTAB_API int vstab_vec2mtrx(const float *p, int B, int dim, int warp_approx, float *out, void *stream);
+/* ---- backward of the three above: what TensorFlow's autodiff gives for warp.py:46-86 / 89-129 and :25-43.  Conventions, limits and
+ * error codes of vstab_st_transform_backward (B <= 65535, B*Hi*Wi*C < 2^31; a NULL output skips that gradient's work, both NULL is
+ * VSTAB_E_SHAPE).  floor, ceil and the int casts have zero derivative and there is no clip; coordinates and taps are the forward's fp32
+ * values; a tap outside the image reads 0 and receives nothing.  Where a source coordinate is an exact integer floor == ceil, both
+ * taps are the same pixel and that axis' slope is 0 (the reference's behaviour).  dout [B,oh,ow,C].
+ *   d_img   [B,Hi,Wi,C] (nullable): zero-filled on `stream` when accumulate == 0, added into when accumulate == 1; float atomics, so its
+ *           last bits DEPEND ON ATOMIC ARRIVAL ORDER.
+ *   d_M     [B,9] (nullable): overwritten; d xh = gx / zs, d yh = gy / zs, d zh = -(gx xh + gy yh) / zs^2 with zs = zh + 1e-8f, times
+ *           (X, Y, 1), products and sums in double in a fixed order (two runs are bit-equal), rounded to fp32 once.
+ *   d_pM    [B,9] (nullable), vstab_transform_image_backward: M = ref . pM is composed as in the forward and d_pM = ref^T . d_M, in
+ *           double, rounded once.  ref is configuration: it gets no gradient.
+ *   workspace: vstab_homography_warp_backward_workspace_bytes() (both calls), 8-byte aligned; VSTAB_E_NOMEM when too small, not read
+ *           when the matrix gradient is NULL.  0 for a shape outside the contract.
+ * vstab_vec2mtrx_backward: d_out [B,9] the gradient of the matrix -> d_p [B,dim], the reverse of the Taylor recurrence
+ * (d A = sum_i 1/i! sum_{j<i} (A^j)^T d_out (A^(i-1-j))^T mapped back through the generator layout), in double from the fp32 p,
+ * rounded once; reproducible; needs no workspace. */
+VSTAB_API size_t vstab_homography_warp_backward_workspace_bytes(int B, int Hi, int Wi, int C, int oh, int ow);
+VSTAB_API int vstab_homography_warp_backward(const float *img, int B, int Hi, int Wi, int C, const float *M, const float *dout, int oh,
+                                             int ow, float *d_img, int accumulate, float *d_M, void *workspace, size_t workspace_bytes,
+                                             void *stream);
+VSTAB_API int vstab_transform_image_backward(const float *img, int B, int Hi, int Wi, int C, const float *ref, const float *pM,
+                                             const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_pM,
+                                             void *workspace, size_t workspace_bytes, void *stream);
+VSTAB_API int vstab_vec2mtrx_backward(const float *p, int B, int dim, int warp_approx, const float *d_out, float *d_p, void *stream);
 
 /* ---- VGG16 convolutional trunk (vgg16.py:25-64; BASELINE config 5) ------------------------------
  * 13 x (conv 3x3 SAME + bias + ReLU) and 5 x (max pool 2x2 stride 2 SAME).  Weights in the layout of
