@@ -446,6 +446,60 @@ extern "C" int vstab_st_elastic_transform_backward(const float *img, int B, int 
     return VSTAB_OK;
 }
 
+// ---- the symmetric-pad transformers: the matrices and coordinates the forward uses, and the backward of their bilinear sampler
+static bool sym_kind_ok(int kind) { return kind == VSTAB_SYM_AFFINE || kind == VSTAB_SYM_PROJECTIVE || kind == VSTAB_SYM_SIMILARITY; }
+
+// the forward's shape rule (vstab_st_symmetry_transform)
+static bool sym_shape_ok(int B, int H, int W, int C, int oh, int ow)
+{
+    return oh >= 1 && ow >= 1 && oh <= (1 << 20) && ow <= (1 << 20) && stx_shape_ok(B, H, W, C, oh + 200, ow + 200);
+}
+
+extern "C" int vstab_st_symmetry_matrix(const float *theta, int B, int kind, float *out, void *stream)
+{
+    if (!theta || !out) return fail(nullptr, VSTAB_E_STATE, "st_symmetry_matrix: NULL buffer");
+    if (B < 1 || B > 65535) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_matrix: bad shape (1 <= B <= 65535)");
+    if (!sym_kind_ok(kind)) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_matrix: unknown kind %d", kind);
+    HIP_TRY(nullptr, launch_st_symmetry_matrix(theta, B, kind, out, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_st_symmetry_coords(const float *theta, int B, int kind, int oh, int ow, float *x_out, float *y_out, void *stream)
+{
+    if (!theta || !x_out || !y_out) return fail(nullptr, VSTAB_E_STATE, "st_symmetry_coords: NULL buffer");
+    if (!sym_shape_ok(B, 1, 1, 1, oh, ow)) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_coords: bad shape (B <= 65535)");
+    if (!sym_kind_ok(kind)) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_coords: unknown kind %d", kind);
+    HIP_TRY(nullptr, launch_st_symmetry_coords(theta, B, kind, oh, ow, x_out, y_out, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" size_t vstab_st_symmetry_transform_backward_workspace_bytes(int B, int H, int W, int C, int oh, int ow)
+{
+    if (!sym_shape_ok(B, H, W, C, oh, ow) || H < 100 || W < 100) return 0;
+    return st_symmetry_backward_ws_bytes(B, H, W, C, oh, ow);
+}
+
+extern "C" int vstab_st_symmetry_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind, const float *dout,
+                                                    int oh, int ow, float *d_img, int accumulate, float *d_theta, void *workspace,
+                                                    size_t workspace_bytes, void *stream)
+{
+    if (!img || !theta || !dout) return fail(nullptr, VSTAB_E_STATE, "st_symmetry_transform_backward: NULL buffer");
+    if (!sym_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL)
+        return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: bad shape (B <= 65535)");
+    if (H < 100 || W < 100)
+        return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: the 100-pixel symmetric pad needs H, W >= 100 (got %dx%d)", H, W);
+    if (!sym_kind_ok(kind)) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: unknown kind %d", kind);
+    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: d_img and d_theta are both NULL");
+    if (d_theta) {
+        const size_t need = st_symmetry_backward_ws_bytes(B, H, W, C, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "st_symmetry_transform_backward: workspace needs %zu bytes", need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "st_symmetry_transform_backward: workspace must be 8-byte aligned");
+    }
+    HIP_TRY(nullptr, launch_st_symmetry_transform_backward(img, B, H, W, C, theta, kind, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
+                                                           (double *)workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
 // ---- the 3-D volume transformer (sampler3d_ops.hip).  The shape is judged before the pointers: a shape outside the contract is
 // VSTAB_E_SHAPE whatever else is wrong with the call.
 static bool st3d_shape_ok(int B, int D, int H, int W, int C, int od, int oh, int ow, int edge)

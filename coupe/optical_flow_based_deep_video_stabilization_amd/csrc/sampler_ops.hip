@@ -4,7 +4,7 @@
 // st3_tile_kernel for 3-channel frames (tile3.h's skeleton: 2-D tiles, 3-dword tap gathers, rows leaving as 16-byte stores),
 // st_pixel_kernel (one thread per pixel) for other channel counts.  Each piece of the reference's arithmetic is one device
 // function (st_axis in st_axis.h, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta,
-// explicit-coordinate and thin-plate-spline sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel and, for the spline,
+// explicit-coordinate, symmetric-pad and thin-plate-spline sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel and, for the spline,
 // st3_tile_tps_bwd_kernel / st_pixel_tps_bwd_kernel, at the end of the file) that calls the same functions; its d img is summed by
 // float atomics and depends on their arrival order in its last bits, its d theta is reproducible.  The homography source has its own
 // backward arithmetic (homog_bwd_point / homog3_bwd_point, d M [B,9]) on the same two kernel skeletons, and vec2mtrx its own kernel.
@@ -252,6 +252,20 @@ __device__ __forceinline__ void st_theta_coords(const float *th, int tdim, float
     }
 }
 
+// The symmetric-pad transformers at grid point (xt, yt): M . (x_t, y_t, 1) with the pre-mapped matrix, the projective kind divided by
+// z as is -- no safe_z (ST:710-711).  xh, yh, zs (1 unless projective) are the values before the division, for the backward's chain rule.
+__device__ __forceinline__ void st_sym_coords(const float *th, bool proj, float xt, float yt, float &xh, float &yh, float &zs, float &xs, float &ys)
+{
+    xh = (th[0] * xt + th[1] * yt) + th[2];
+    yh = (th[3] * xt + th[4] * yt) + th[5];
+    zs = 1.0f; xs = xh; ys = yh;
+    if (proj) {
+        zs = (th[6] * xt + th[7] * yt) + th[8];
+        xs = xh / zs;
+        ys = yh / zs;
+    }
+}
+
 // normalised source coordinates of grid point (gx, gy) of sample n
 template <int SRC>
 __device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const float *cf, int n, int gx, int gy, float &xs, float &ys)
@@ -280,13 +294,8 @@ __device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const
         st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
         return;
     }
-    xs = (th[0] * xt + th[1] * yt) + th[2];
-    ys = (th[3] * xt + th[4] * yt) + th[5];
-    if (SRC == XS_SYM && S.kind == 1) {           // ProjectiveSymmetryTransformer divides by z as is (ST:710-711)
-        const float zs = (th[6] * xt + th[7] * yt) + th[8];
-        xs = xs / zs;
-        ys = ys / zs;
-    }
+    float xh, yh, zs;
+    st_sym_coords(th, S.kind == 1, xt, yt, xh, yh, zs, xs, ys);
 }
 
 // bicubic_interp's taps and weights along one axis (ST:988-1050): clip to [-1,1] first (NaN -> -1), scale, x0 = floor, taps in
@@ -614,16 +623,25 @@ hipError_t launch_st_transform_interp(const float *img, int B, int H, int W, int
     return launch_st<XS_THETA, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, oh, ow, stream);
 }
 
-hipError_t launch_st_symmetry_transform(const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
-                                        float *out, int oh, int ow, hipStream_t stream)
+// the symmetric-pad source of out_size (oh, ow): the (oh+200) x (ow+200) sampling grid and the crop-or-pad to th x tw, the final extent
+static StSrc st_sym_src(const float *theta, int kind, int oh, int ow, int &th, int &tw)
 {
     StSrc S{};
     S.theta = theta; S.kind = kind;
+    S.tdim = kind == 1 ? 8 : 6;              // the backward's d M entries per sample (st_theta_accum)
     S.gh = oh + 200; S.gw = ow + 200;
     // resize_image_with_crop_or_pad(out, ow, oh) (ST:343, 488, 682): target height ow, width oh -- swapped
-    const int th = ow, tw = oh;
+    th = ow; tw = oh;
     S.cropy = max((S.gh - th) / 2, 0); S.pady = max((th - S.gh) / 2, 0); S.leny = min(S.gh, th);
     S.cropx = max((S.gw - tw) / 2, 0); S.padx = max((tw - S.gw) / 2, 0); S.lenx = min(S.gw, tw);
+    return S;
+}
+
+hipError_t launch_st_symmetry_transform(const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
+                                        float *out, int oh, int ow, hipStream_t stream)
+{
+    int th, tw;
+    const StSrc S = st_sym_src(theta, kind, oh, ow, th, tw);
     if (interp == XI_BILINEAR) return launch_st<XS_SYM, XI_BILINEAR>(-1, 0.0, img, B, H, W, C, S, out, th, tw, stream);
     return launch_st<XS_SYM, XI_BICUBIC>(-1, 0.0, img, B, H, W, C, S, out, th, tw, stream);
 }
@@ -673,6 +691,56 @@ hipError_t launch_st_elastic_coords(const float *theta, int B, int g, const floa
     return hipGetLastError();
 }
 
+// The symmetric-pad transformers' pre-mapped matrices themselves, [B,9] (SimilarityTransformer's interleave included), and their
+// normalised source coordinates per FINAL pixel, [B*FH*FW] each (0 where the crop-or-pad pads): st_matrix / st_matrix_wg, st_grid_pos
+// and st_coords<XS_SYM>, called as the sampling kernels call them, so these are the values the forward uses bit for bit.
+__global__ __launch_bounds__(64) void st_sym_matrix_kernel(StSrc S, float *__restrict__ out)
+{
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= S.B) return;
+    float th[9];
+    st_matrix<XS_SYM>(S, n, th);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out[(long long)n * 9 + k] = th[k];
+}
+
+__global__ __launch_bounds__(256) void st_sym_coords_kernel(StSrc S, float *__restrict__ x_out, float *__restrict__ y_out, int FH, int FW, unsigned bps)
+{
+    __shared__ float sm[8];
+    const int n = (int)(blockIdx.x / bps);
+    float th[9];
+    st_matrix_wg<XS_SYM>(S, n, th, sm);
+    const long long p = (long long)(blockIdx.x - (unsigned)n * bps) * 256 + threadIdx.x;
+    if (p >= (long long)FH * FW) return;
+    const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+    int gx, gy;
+    float xs = 0.f, ys = 0.f;
+    if (st_grid_pos<XS_SYM>(S, fx, fy, gx, gy)) st_coords<XS_SYM>(S, th, nullptr, n, gx, gy, xs, ys);
+    x_out[(long long)n * FH * FW + p] = xs;
+    y_out[(long long)n * FH * FW + p] = ys;
+}
+
+hipError_t launch_st_symmetry_matrix(const float *theta, int B, int kind, float *out, hipStream_t stream)
+{
+    int th, tw;
+    StSrc S = st_sym_src(theta, kind, 1, 1, th, tw);
+    S.B = B;
+    st_sym_matrix_kernel<<<dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream>>>(S, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_st_symmetry_coords(const float *theta, int B, int kind, int oh, int ow, float *x_out, float *y_out, hipStream_t stream)
+{
+    int th, tw;
+    StSrc S = st_sym_src(theta, kind, oh, ow, th, tw);
+    S.B = B;
+    st_steps(S);
+    const long long bps = ((long long)th * tw + 255) / 256;
+    if (bps * B >= (1ll << 31)) return hipErrorInvalidValue;
+    st_sym_coords_kernel<<<dim3((unsigned)(bps * B)), dim3(256), 0, stream>>>(S, x_out, y_out, th, tw, (unsigned)bps);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------
 // Backward of the BILINEAR sampler for the theta (affine / projective) and explicit-coordinate sources: what TensorFlow's autodiff
 // gives for ST:902-964 and ST:438-452 / 578-608.  The coordinates, taps and weights are the forward's (st_theta_coords, st_axis,
@@ -719,15 +787,17 @@ struct StBwd {
 // The bilinear backward of ONE output pixel sampled at (xs, ys), stated once for every source of coordinates.  b, di: the sample's
 // image and its gradient; g: the pixel's dout.  DIMG: w_k * dout added to the four taps (none to a tap on the zero border).  DCOORD:
 // gxn, gyn = d out / d (xs, ys) summed over the channels times dout, through the clip and the pixel scaling (0 otherwise).
-// Any channel count:
-template <bool DIMG, bool DCOORD>
+// XS_SYM: the axes are the padded extent's (st_extent) and a padded tap p is image pixel refl(p - 100) (st_src), for the values read
+// and for the adjoint alike: several padded taps fold onto one image pixel and all of them add.  Any channel count:
+template <bool DIMG, bool DCOORD, int SRC = XS_THETA>
 __device__ __forceinline__ void st_bwd_point(const float *__restrict__ b, float *di, const float *__restrict__ g, int H, int W, int C, float xs,
                                              float ys, float &gxn, float &gyn)
 {
-    const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
+    const Axis X = st_axis(xs, st_extent<SRC>(W)), Y = st_axis(ys, st_extent<SRC>(H));
     const Taps t = st_taps(X, Y);
-    const long long i00 = ((long long)t.ya * W + t.xa) * C, i01 = ((long long)t.ya * W + t.xb) * C;
-    const long long i10 = ((long long)t.yb * W + t.xa) * C, i11 = ((long long)t.yb * W + t.xb) * C;
+    const int ya = st_src<SRC>(t.ya, H), yb = st_src<SRC>(t.yb, H), xa = st_src<SRC>(t.xa, W), xb = st_src<SRC>(t.xb, W);
+    const long long i00 = ((long long)ya * W + xa) * C, i01 = ((long long)ya * W + xb) * C;
+    const long long i10 = ((long long)yb * W + xa) * C, i11 = ((long long)yb * W + xb) * C;
     const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
     float gx = 0.f, gy = 0.f;
     for (int c = 0; c < C; ++c) {
@@ -740,27 +810,28 @@ __device__ __forceinline__ void st_bwd_point(const float *__restrict__ b, float 
             if (v11) atomicAdd(di + i11 + c, t.w3 * gc);
         }
     }
-    gxn = DCOORD ? st_axis_chain(X, gx, W) : 0.0f;
-    gyn = DCOORD ? st_axis_chain(Y, gy, H) : 0.0f;
+    gxn = DCOORD ? st_axis_chain(X, gx, st_extent<SRC>(W)) : 0.0f;
+    gyn = DCOORD ? st_axis_chain(Y, gy, st_extent<SRC>(H)) : 0.0f;
 }
 
 // 3-channel frames (3 H W < 2^31: host):
-template <bool DIMG, bool DCOORD>
+template <bool DIMG, bool DCOORD, int SRC = XS_THETA>
 __device__ __forceinline__ void st3_bwd_point(const rgb3 *b, float *di, const rgb3 g, int H, int W, float xs, float ys, float &gxn, float &gyn)
 {
-    const Axis X = st_axis(xs, W), Y = st_axis(ys, H);
+    const Axis X = st_axis(xs, st_extent<SRC>(W)), Y = st_axis(ys, st_extent<SRC>(H));
     const Taps t = st_taps(X, Y);
+    const int ya = st_src<SRC>(t.ya, H), yb = st_src<SRC>(t.yb, H), xa = st_src<SRC>(t.xa, W), xb = st_src<SRC>(t.xb, W);
     const bool v00 = t.vxa && t.vya, v01 = t.vxb && t.vya, v10 = t.vxa && t.vyb, v11 = t.vxb && t.vyb;
     gxn = gyn = 0.0f;
     if (DCOORD) {
         const rgb3 z = {0.f, 0.f, 0.f};
-        const rgb3 I00 = v00 ? b[t.ya * W + t.xa] : z, I01 = v01 ? b[t.ya * W + t.xb] : z;
-        const rgb3 I10 = v10 ? b[t.yb * W + t.xa] : z, I11 = v11 ? b[t.yb * W + t.xb] : z;
+        const rgb3 I00 = v00 ? b[ya * W + xa] : z, I01 = v01 ? b[ya * W + xb] : z;
+        const rgb3 I10 = v10 ? b[yb * W + xa] : z, I11 = v11 ? b[yb * W + xb] : z;
         float gx = 0.f, gy = 0.f;
         st_slope(X, Y, I00.r, I01.r, I10.r, I11.r, g.r, gx, gy);
         st_slope(X, Y, I00.g, I01.g, I10.g, I11.g, g.g, gx, gy);
         st_slope(X, Y, I00.b, I01.b, I10.b, I11.b, g.b, gx, gy);
-        gxn = st_axis_chain(X, gx, W); gyn = st_axis_chain(Y, gy, H);
+        gxn = st_axis_chain(X, gx, st_extent<SRC>(W)); gyn = st_axis_chain(Y, gy, st_extent<SRC>(H));
     }
     if (DIMG) {
         auto add = [&](int y, int x, bool valid, float w) {
@@ -768,7 +839,7 @@ __device__ __forceinline__ void st3_bwd_point(const rgb3 *b, float *di, const rg
             float *q = di + ((long long)y * W + x) * 3;
             atomicAdd(q, w * g.r); atomicAdd(q + 1, w * g.g); atomicAdd(q + 2, w * g.b);
         };
-        add(t.ya, t.xa, v00, t.w0); add(t.ya, t.xb, v01, t.w1); add(t.yb, t.xa, v10, t.w2); add(t.yb, t.xb, v11, t.w3);
+        add(ya, xa, v00, t.w0); add(ya, xb, v01, t.w1); add(yb, xa, v10, t.w2); add(yb, xb, v11, t.w3);
     }
 }
 
@@ -854,7 +925,8 @@ __device__ __forceinline__ void homog3_bwd_point(const rgb3 *b, float *di, const
     }
 }
 
-// doubles per d theta / d M partial row: the theta sources' 8 (the affine one uses six of them), the homography's 9
+// doubles per d theta / d M partial row: the theta and symmetric-pad sources' 8 (the affine kinds use six of them; the symmetric-pad
+// projective M[8] is a constant), the homography's 9
 template <int SRC>
 constexpr int st_part_width() { return SRC == XS_HOMOG ? 9 : 8; }
 
@@ -864,9 +936,10 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
 {
     constexpr int NP = st_part_width<SRC>();
     __shared__ double red[4][NP];
+    __shared__ float sm[SRC == XS_SYM ? 8 : 1];          // XS_SYM: st_matrix_wg's six similarity entries
     const int n = (int)(blockIdx.x / bps);
     float th[9];
-    st_matrix_wg<SRC>(S, n, th, nullptr);
+    st_matrix_wg<SRC>(S, n, th, SRC == XS_SYM ? sm : nullptr);
     const long long p = (long long)(blockIdx.x - (unsigned)n * bps) * 256 + threadIdx.x;
     const bool ok = p < (long long)FH * FW;
     double acc[NP];
@@ -879,6 +952,17 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
         homog_bwd_point<DIMG, DCOORD>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
                                       G.dout + ((long long)n * FH * FW + p) * C, W, C, homog_taps(q, H, W), gx, gy);
         if (DCOORD) homog_accum(acc, gx, gy, q);
+    } else if (ok && SRC == XS_SYM) {
+        const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
+        int gx, gy;
+        if (st_grid_pos<SRC>(S, fx, fy, gx, gy)) {          // a pixel the crop-or-pad pads contributes nothing: its dout is not read
+            float xs, ys, xh, yh, zs, gxn, gyn;
+            const float xt = st_grid_t(gx, S.sx), yt = st_grid_t(gy, S.sy);
+            st_sym_coords(th, S.kind == 1, xt, yt, xh, yh, zs, xs, ys);
+            st_bwd_point<DIMG, DCOORD, SRC>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
+                                            G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
+            if (DCOORD) st_theta_accum(acc, S.tdim, gxn, gyn, xt, yt, xh, yh, zs);          // S.tdim: 8 projective, 6 otherwise (host)
+        }
     } else if (ok) {
         const int fy = (int)(p / FW), fx = (int)(p - (long long)fy * FW);
         float xs, ys, xh = 0.f, yh = 0.f, zs = 1.f;
@@ -897,7 +981,7 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
             }
         }
     }
-    if (DCOORD && (SRC == XS_THETA || SRC == XS_HOMOG)) st_theta_reduce<NP>(acc, red, G.part + (long long)blockIdx.x * NP);
+    if (DCOORD && (SRC == XS_THETA || SRC == XS_HOMOG || SRC == XS_SYM)) st_theta_reduce<NP>(acc, red, G.part + (long long)blockIdx.x * NP);
 }
 
 // 3-channel frames on the tile skeleton (st3_tile_kernel's pixels: a wave instruction works on a 4 x 16 patch)
@@ -907,10 +991,11 @@ __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restri
 {
     constexpr int PPT = StTile::PPT, NP = st_part_width<SRC>();
     __shared__ double red[4][NP];
+    __shared__ float sm[SRC == XS_SYM ? 8 : 1];          // XS_SYM: st_matrix_wg's six similarity entries
     const StTile tile(tiles_x, tiles_y);
     const int n = tile.n;
     float th[9];
-    st_matrix_wg<SRC>(S, n, th, nullptr);
+    st_matrix_wg<SRC>(S, n, th, SRC == XS_SYM ? sm : nullptr);
     const rgb3 *b = reinterpret_cast<const rgb3 *>(img) + (long long)n * H * W;     // 3 B H W < 2^31 (host)
     float *di = DIMG ? G.d_img + (long long)n * H * W * 3 : nullptr;
     double acc[NP];
@@ -925,6 +1010,16 @@ __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restri
             float gx, gy;
             homog3_bwd_point<DIMG, DCOORD>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[((long long)n * FH + fy) * FW + fx], W, homog_taps(q, H, W), gx, gy);
             if (DCOORD) homog_accum(acc, gx, gy, q);
+            continue;
+        }
+        if (SRC == XS_SYM) {
+            int gx, gy;
+            if (!st_grid_pos<SRC>(S, fx, fy, gx, gy)) continue;          // a pixel the crop-or-pad pads contributes nothing: its dout is not read
+            float xs, ys, xh, yh, zs, gxn, gyn;
+            const float xt = st_grid_t(gx, S.sx), yt = st_grid_t(gy, S.sy);
+            st_sym_coords(th, S.kind == 1, xt, yt, xh, yh, zs, xs, ys);
+            st3_bwd_point<DIMG, DCOORD, SRC>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[((long long)n * FH + fy) * FW + fx], H, W, xs, ys, gxn, gyn);
+            if (DCOORD) st_theta_accum(acc, S.tdim, gxn, gyn, xt, yt, xh, yh, zs);          // S.tdim: 8 projective, 6 otherwise (host)
             continue;
         }
         float xs, ys, xh = 0.f, yh = 0.f, zs = 1.f;
@@ -943,7 +1038,7 @@ __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restri
             }
         }
     }
-    if (DCOORD && (SRC == XS_THETA || SRC == XS_HOMOG)) {
+    if (DCOORD && (SRC == XS_THETA || SRC == XS_HOMOG || SRC == XS_SYM)) {
         const int tidx = (tile.ty0 / StTile::TH) * tiles_x + tile.tx0 / StTile::TW;
         st_theta_reduce<NP>(acc, red, G.part + ((long long)n * tiles_x * tiles_y + tidx) * NP);
     }
@@ -976,7 +1071,7 @@ static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, St
     S.B = B;
     st_steps(S);
     if (SRC == XS_HOMOG) { S.dsx = S.gw > 1 ? 2.0 / (double)(S.gw - 1) : 0.0; S.dsy = S.gh > 1 ? 2.0 / (double)(S.gh - 1) : 0.0; }      // launch_st's
-    const bool dimg = G.d_img != nullptr, dcoord = (SRC == XS_THETA || SRC == XS_HOMOG) ? G.part != nullptr : (G.d_x || G.d_y);
+    const bool dimg = G.d_img != nullptr, dcoord = (SRC == XS_THETA || SRC == XS_HOMOG || SRC == XS_SYM) ? G.part != nullptr : (G.d_x || G.d_y);
     int tx, ty;
     dim3 grid;
     long long wgs;
@@ -1029,6 +1124,100 @@ hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int 
     S.x = x; S.y = y;
     StBwd G{dout, d_img, d_x, d_y, nullptr};
     return launch_st_bwd<XS_COORDS>(img, B, H, W, C, S, G, oh, ow, stream);
+}
+
+// ---------------------------------------------------------------------------------
+// Backward of the symmetric-pad transformers (XS_SYM, BILINEAR sampler): what TensorFlow's autodiff gives for ST:311-371, 454-517 and
+// 611-716.  The two kernels above with SRC = XS_SYM: a final pixel goes through st_grid_pos (one the crop-or-pad pads contributes
+// nothing), its coordinates are st_sym_coords', its axes those of the padded extent, and a padded tap p adds into image pixel
+// refl(p - 100) -- the adjoint of gather . symmetric-pad.  The per-pixel products give d M, the gradient of the PRE-MAPPED matrix
+// (part[workgroup][8], the projective kind's chain through x_h / z with z as is: no safe_z, z == 0 propagates by IEEE rules);
+// st_sym_dm_kernel adds a sample's partials in st_theta_final_kernel's order into d M [B][8] doubles (behind the partials in the
+// workspace), and st_sym_theta_final_kernel takes d M through the pre-map, in double, rounded to fp32 once:
+//   affine      M = (theta c) 0 + I:  d theta[k] = (d M[k] 0) c[k] -- zero for a finite d M, a non-finite one propagates
+//   projective  M = [theta, 1] P + A: d theta[k] = d M[k] P[k], k < 8
+//   similarity  entry k of sample n is vector v = (6n+k) / B at batch index b = (6n+k) % B (st_matrix), so dE[v][b] = d M[n][k], and with
+//               the forward's fp32 a, s, cosf a, sinf a:  d a = s (-sin a) (dE0 + dE4) + s cos a (dE1 - dE3),
+//               d s = cos a (dE0 + dE4) + sin a (dE1 - dE3),  d theta[b] = (d a (float)(3.14/6), d s .1, dE2 .2, dE5 .2).
+//               For B > 1 that couples samples: the kernel works on the whole batch, a thread per batch index.
+// No atomics in either: d theta is bit-reproducible.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void st_sym_dm_kernel(const double *__restrict__ part, int wgs, double *__restrict__ dM)
+{
+    __shared__ double red[4][8];
+    const int n = blockIdx.x;
+    double acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.0;
+    for (int i = threadIdx.x; i < wgs; i += 256)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += part[((long long)n * wgs + i) * 8 + k];
+    st_theta_reduce<8>(acc, red, dM + (long long)n * 8);
+}
+
+__global__ __launch_bounds__(64) void st_sym_theta_final_kernel(const double *__restrict__ dM, const float *__restrict__ theta, int B, int kind,
+                                                                float *__restrict__ d_theta)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    if (kind == 0) {
+        const float c[6] = {0.1f, 0.0f, 0.2f, 0.1f, 0.0f, 0.2f};
+#pragma unroll
+        for (int k = 0; k < 6; ++k) d_theta[(long long)b * 6 + k] = (float)((dM[(long long)b * 8 + k] * 0.0) * (double)c[k]);
+    } else if (kind == 1) {
+        const float P[8] = {0.01f, 0.005f, 0.01f, 0.01f, 0.005f, 0.01f, 0.01f, 0.01f};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d_theta[(long long)b * 8 + k] = (float)(dM[(long long)b * 8 + k] * (double)P[k]);
+    } else {
+        double dE[6];
+#pragma unroll
+        for (int v = 0; v < 6; ++v) {                        // undo the interleave: (v, b) is entry k of sample n, 6n + k = v B + b
+            const long long f = (long long)v * B + b;
+            const long long n = f / 6;
+            dE[v] = dM[n * 8 + (f - 6 * n)];
+        }
+        const float *tp = theta + (long long)b * 4;
+        const float a = tp[0] * (float)(3.14 / 6) + 0.0f, s = tp[1] * 0.1f + 1.0f;          // st_matrix's
+        const double ca = (double)cosf(a), sa = (double)sinf(a), sd = (double)s;
+        const double d_a = sd * (-sa) * (dE[0] + dE[4]) + sd * ca * (dE[1] - dE[3]);
+        const double d_s = ca * (dE[0] + dE[4]) + sa * (dE[1] - dE[3]);
+        d_theta[(long long)b * 4 + 0] = (float)(d_a * (double)(float)(3.14 / 6));
+        d_theta[(long long)b * 4 + 1] = (float)(d_s * (double)0.1f);
+        d_theta[(long long)b * 4 + 2] = (float)(dE[2] * (double)0.2f);
+        d_theta[(long long)b * 4 + 3] = (float)(dE[5] * (double)0.2f);
+    }
+}
+
+// the partials [B * workgroups][8] and, behind them, d M [B][8]
+size_t st_symmetry_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow)
+{
+    int tx, ty;
+    dim3 grid;
+    long long wgs;
+    st_bwd_plan(B, H, W, C, ow, oh, tx, ty, grid, wgs);          // the final extent: height ow, width oh
+    return ((size_t)wgs * B * 8 + (size_t)B * 8) * sizeof(double);
+}
+
+hipError_t launch_st_symmetry_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind, const float *dout,
+                                                 int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream)
+{
+    if (d_img && !accumulate) {
+        const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
+        if (e != hipSuccess) return e;
+    }
+    int th, tw;
+    const StSrc S = st_sym_src(theta, kind, oh, ow, th, tw);
+    StBwd G{dout, d_img, nullptr, nullptr, d_theta ? part : nullptr};
+    const hipError_t e = launch_st_bwd<XS_SYM>(img, B, H, W, C, S, G, th, tw, stream);
+    if (e != hipSuccess || !d_theta) return e;
+    int tx, ty;
+    dim3 grid;
+    long long wgs;
+    st_bwd_plan(B, H, W, C, th, tw, tx, ty, grid, wgs);
+    double *dM = part + wgs * B * 8;
+    st_sym_dm_kernel<<<dim3((unsigned)B), dim3(256), 0, stream>>>(part, (int)wgs, dM);
+    st_sym_theta_final_kernel<<<dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream>>>(dM, theta, B, kind, d_theta);
+    return hipGetLastError();
 }
 
 size_t homography_warp_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow)

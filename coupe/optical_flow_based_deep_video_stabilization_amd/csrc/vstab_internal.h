@@ -432,6 +432,14 @@ size_t st_elastic_backward_ws_bytes(int B, int H, int W, int C, int g, int oh, i
 hipError_t launch_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part,
                                                 hipStream_t stream);
+// The symmetric-pad transformers: their pre-mapped matrices out [B,9], the source coordinates per final pixel x_out, y_out
+// [B*ow*oh] (0 where the crop-or-pad pads), and the backward of their bilinear sampler, conventions as launch_st_transform_backward
+// (dout [B,ow,oh,C]), `part`: st_symmetry_backward_ws_bytes of scratch for the d M partials and d M
+hipError_t launch_st_symmetry_matrix(const float *theta, int B, int kind, float *out, hipStream_t stream);
+hipError_t launch_st_symmetry_coords(const float *theta, int B, int kind, int oh, int ow, float *x_out, float *y_out, hipStream_t stream);
+size_t st_symmetry_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow);
+hipError_t launch_st_symmetry_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind, const float *dout,
+                                                 int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream);
 
 // The 3-D volume transformer (sampler3d_ops.hip): AffineVolumeTransformer / bilinear_interp3d / _meshgrid3d and their backward.
 // st3d_plan: bricks along each axis and per sample of a [B, od, oh, ow] output; false when the launch grid does not fit.  d_vol

@@ -6,11 +6,14 @@
 imported, main:4 and cell.py:2); the arithmetic runs in HIP kernels (csrc/sampler_ops.hip, csrc/sampler3d_ops.hip for the volume transformer).
 
 Differentiable (torch.autograd, HIP backward kernels): `AffineTransformer.transform`, `ProjectiveTransformer.transform`,
-`ElasticTransformer.transform` and `transformer()` with the bilinear sampler, with respect to the image and `theta` (for the
-elastic one: the control-point offsets), and `bilinear_interp` with respect to the image, `x` and `y`; `AffineVolumeTransformer.transform` with respect to the volume and `theta`, `bilinear_interp3d` with respect to the
+`ElasticTransformer.transform`, `SimilarityTransformer.transform`, `AffineSymmetryTransformer.transform`,
+`ProjectiveSymmetryTransformer.transform` and `transformer()` with the bilinear sampler, with respect to the image and `theta` (for the
+elastic one: the control-point offsets; for the symmetric-pad ones: through each class's pre-map, which makes `AffineSymmetryTransformer`'s
+theta gradient exactly zero and couples the samples of a `SimilarityTransformer` batch), and `bilinear_interp` with respect to the image, `x` and `y`; `AffineVolumeTransformer.transform` with respect to the volume and `theta`, `bilinear_interp3d` with respect to the
 volume, `x`, `y` and `z`.  The gradient of the image or volume is summed by float atomics (last bits may differ between runs); those of `theta`, `x`, `y`,
 `z` are bit-reproducible.  NOT differentiable -- the result has no `grad_fn`, whatever requires grad: `bicubic_interp` and
-`interp_method='bicubic'` (on `ElasticTransformer` too), the symmetric-pad transformers, `ElasticTransformer.transform_coords`.
+`interp_method='bicubic'` (on `ElasticTransformer` and the symmetric-pad transformers too), `ElasticTransformer.transform_coords`, and the
+symmetric-pad transformers' `matrix` and `transform_coords`.
 The homography samplers of the reference's `warp.py` (`warp.transformImage` and its kin) are differentiable too: see `warp.py`."""
 from __future__ import annotations
 
@@ -208,11 +211,40 @@ class ProjectiveTransformer(_ThetaTransformer):
         super().__init__(out_size, name, interp_method, **kwargs)
 
 
+def _symmetry_transform_call(inp, theta, kind, oh, ow, interp):
+    B, H, W, Cc = inp.shape
+    out = torch.empty((B, ow, oh, Cc), dtype=torch.float32, device=inp.device)
+    with torch.cuda.device(inp.device):
+        _lib.check(_lib.lib().vstab_st_symmetry_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), kind, interp,
+                                                          out.data_ptr(), oh, ow, runtime.stream_ptr()))
+    return out
+
+
+class _SymmetryTransformFn(torch.autograd.Function):
+    """The symmetric-pad transformers' transform (bilinear) with its HIP backward (training.st_symmetry_transform_backward); theta flat."""
+
+    @staticmethod
+    def forward(ctx, inp, theta, kind, oh, ow):
+        ctx.save_for_backward(inp, theta)
+        ctx.kind, ctx.out_size = kind, (oh, ow)
+        return _symmetry_transform_call(inp, theta, kind, oh, ow, 0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        inp, theta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_inp, d_theta = training.st_symmetry_transform_backward(inp, theta, dout, ctx.out_size, ctx.kind, need_img=need[0], need_theta=need[1])
+        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None
+
+
 class _SymmetryTransformer(object):
     """The symmetric-pad transformers (ST:311-371, 454-517, 611-716): the input padded by 100 px per side in SYMMETRIC mode
     (H, W >= 100, as tf.pad requires; never materialised), sampled on the linspace grid of (oh+200) x (ow+200) points, then
     tf.image.resize_image_with_crop_or_pad(out, out_size[1], out_size[0]) -- target height ow, width oh: the result is
-    [B, ow, oh, C].  For square outputs the swap does not show.  Not differentiable."""
+    [B, ow, oh, C].  For square outputs the swap does not show.  With the bilinear sampler `transform` is differentiable with
+    respect to the image and theta (through the pre-map of each class); with the bicubic one it is not (no `grad_fn`)."""
     param_dim = 0
     kind = -1
 
@@ -221,28 +253,56 @@ class _SymmetryTransformer(object):
         self.out_size = (int(out_size[0]), int(out_size[1]))
         self.interp_method = interp_method
 
+    def _theta(self, theta, B=None):
+        theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
+        if theta.numel() == 0 or theta.numel() % self.param_dim or (B is not None and theta.numel() != B * self.param_dim):
+            raise ValueError(f"theta must have shape [{'B' if B is None else B}, {self.param_dim}]")
+        return theta
+
     def transform(self, inp, theta):
         interp = _interp_code(self.interp_method)
         inp = _f32_cuda(inp, "inp")
         B, H, W, Cc = inp.shape
         if H < 100 or W < 100:
             raise ValueError(f"{type(self).__name__}: the 100-pixel symmetric pad needs H, W >= 100, got {H}x{W}")
-        theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
-        if theta.numel() != B * self.param_dim:
-            raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
+        theta = self._theta(theta, B)
         oh, ow = self.out_size
-        out = torch.empty((B, ow, oh, Cc), dtype=torch.float32, device=inp.device)
-        with torch.cuda.device(inp.device):
-            _lib.check(_lib.lib().vstab_st_symmetry_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), self.kind, interp,
-                                                              out.data_ptr(), oh, ow, runtime.stream_ptr()))
+        if interp == 0 and _wants_grad(inp, theta):          # bilinear only: the bicubic sampler has no backward
+            return _SymmetryTransformFn.apply(inp, theta, self.kind, oh, ow)
+        return _symmetry_transform_call(inp, theta, self.kind, oh, ow, interp)
+
+    def matrix(self, theta):
+        """theta [B, param_dim] -> [B,3,3]: the pre-mapped matrices `transform` multiplies the grid by (affine kinds: last row 0 0 1),
+        bit for bit -- the same device code computes them, SimilarityTransformer's interleave across samples included.  Forward
+        only: the result carries no graph."""
+        theta = self._theta(theta.detach())
+        B = theta.numel() // self.param_dim
+        out = torch.empty((B, 3, 3), dtype=torch.float32, device=theta.device)
+        with torch.cuda.device(theta.device):
+            _lib.check(_lib.lib().vstab_st_symmetry_matrix(theta.data_ptr(), B, self.kind, out.data_ptr(), runtime.stream_ptr()))
         return out
+
+    def transform_coords(self, theta):
+        """theta [B, param_dim] -> (x_s, y_s), each flat [B*ow*oh] in the output's layout: the normalised source coordinates, on the
+        (H+200) x (W+200) padded extent, that `transform` samples every final pixel at, bit for bit; 0 where the crop-or-pad pads.
+        Needs no image.  Forward only: the results carry no graph."""
+        theta = self._theta(theta.detach())
+        B = theta.numel() // self.param_dim
+        oh, ow = self.out_size
+        x_s = torch.empty(B * oh * ow, dtype=torch.float32, device=theta.device)
+        y_s = torch.empty_like(x_s)
+        with torch.cuda.device(theta.device):
+            _lib.check(_lib.lib().vstab_st_symmetry_coords(theta.data_ptr(), B, self.kind, oh, ow, x_s.data_ptr(), y_s.data_ptr(),
+                                                           runtime.stream_ptr()))
+        return x_s, y_s
 
 
 class SimilarityTransformer(_SymmetryTransformer):
     """theta [B,4] = (angle, scale, tx, ty) pre-mapped by * [3.14/6, .1, .2, .2] + [0, 1, 0, 0] (ST:356-357) into
     [s cos a, s sin a, tx; -s sin a, s cos a, ty].  The reference concatenates the six [B] vectors on axis 0 before the
     reshape to [B,2,3] (ST:358-360), so for B > 1 the matrices interleave across samples ("BatchSize Should be One",
-    ST:355); that order is kept.  Output [B, ow, oh, C]."""
+    ST:355); that order is kept.  Output [B, ow, oh, C].  With the bilinear sampler `transform` is differentiable with respect to
+    the image and theta; for B > 1 the interleave makes a sample's output depend on other samples' theta, and the gradient follows it."""
     param_dim = 4
     kind = 2
 
@@ -252,7 +312,9 @@ class SimilarityTransformer(_SymmetryTransformer):
 
 class AffineSymmetryTransformer(_SymmetryTransformer):
     """theta [B,6] pre-mapped by * [[.1,0,.2],[.1,0,.2]] * 0 + I (ST:503-505): the identity for any finite theta (NaN / inf
-    still propagate).  The [B, ow, oh, C] crop is relabelled [B, oh, ow, C] by a reshape, as the reference does (ST:492)."""
+    still propagate).  The [B, ow, oh, C] crop is relabelled [B, oh, ow, C] by a reshape, as the reference does (ST:492).  With the
+    bilinear sampler `transform` is differentiable: the image's gradient arrives through the reshape, theta's is exactly zero (the
+    pre-map multiplies it by 0) unless a non-finite gradient propagates."""
     param_dim = 6
     kind = 0
 
@@ -266,7 +328,8 @@ class AffineSymmetryTransformer(_SymmetryTransformer):
 
 class ProjectiveSymmetryTransformer(_SymmetryTransformer):
     """theta [B,8]: [theta, 1] * [[.01,.005,.01],[.01,.005,.01],[.01,.01,1]] + [[1,0,0],[0,1,0],[0,0,0]] (ST:692-699), divided
-    by z with no safe_z (ST:710-711).  Output [B, ow, oh, C]."""
+    by z with no safe_z (ST:710-711).  Output [B, ow, oh, C].  With the bilinear sampler `transform` is differentiable with respect to
+    the image and theta (z == 0 propagates by IEEE rules, as in the reference)."""
     param_dim = 8
     kind = 1
 

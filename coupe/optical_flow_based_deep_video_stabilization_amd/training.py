@@ -2,7 +2,7 @@
 `lossterm` / `masked_MSE` (main:188-210, "main" = main_flownetS_pyramid_noprevloss_dataloader.py), the total-variation
 terms and `loss_main` (main:213-275) with their gradient with respect to every predicted flow; filter / input gradients
 of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and its backward; the resamplers' adjoints; the
-gradients of the bilinear spatial transformers (`st_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`)
+gradients of the bilinear spatial transformers (`st_transform_backward`, `st_symmetry_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`)
 and of warp.py's homography warp and matrix exponential (`homography_warp_backward`, `vec2mtrx_backward`).
 `train_step.Trainer` strings them into the whole step (forward, loss, backward, Adam: main:184-185, 333-335).
 
@@ -258,6 +258,41 @@ def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, nee
                                                  d_img.data_ptr() if need_img else None, 1 if acc else 0,
                                                  d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
                                                  runtime.stream_ptr()))
+    return (d_img if need_img else None), d_theta
+
+
+_SYM_THETA_DIM = {0: 6, 1: 8, 2: 4}          # VSTAB_SYM_AFFINE, _PROJECTIVE, _SIMILARITY
+
+
+def st_symmetry_transform_backward(img, theta, dout, out_size, kind, need_img: bool = True, need_theta: bool = True, d_img=None):
+    """Gradients of SimilarityTransformer (kind 2) / AffineSymmetryTransformer (0) / ProjectiveSymmetryTransformer (1) .transform with
+    the bilinear sampler, for the output gradient dout in the forward's output layout [B,ow,oh,C] (out_size = (oh, ow)): (d img
+    [B,H,W,C] or None, d theta [B,4|6|8] or None).  H, W >= 100.  d_img, need_img, need_theta as in st_transform_backward; d img is
+    summed by float atomics (its last bits may differ between runs), d theta is bit-reproducible.  The affine kind's pre-map
+    multiplies theta by 0: its d theta is exactly zero for finite gradients.  The similarity kind's d theta couples the samples of a
+    batch for B > 1, as the reference's interleave does."""
+    kind = int(kind)
+    if kind not in _SYM_THETA_DIM:
+        raise ValueError("kind must be 0 (affine), 1 (projective) or 2 (similarity)")
+    need_img = need_img or d_img is not None
+    img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
+    if H < 100 or W < 100:
+        raise ValueError(f"the 100-pixel symmetric pad needs H, W >= 100, got {H}x{W}")
+    tdim = _SYM_THETA_DIM[kind]
+    theta = theta.contiguous()
+    if not theta.is_cuda or theta.dtype != torch.float32 or theta.numel() != tdim * B:
+        raise ValueError(f"theta must be a float32 CUDA tensor [B,{tdim}]")
+    L = _lib.lib()
+    d_theta, ws, n = None, None, 0
+    if need_theta:
+        d_theta = torch.empty((B, tdim), dtype=torch.float32, device=img.device)
+        n = int(L.vstab_st_symmetry_transform_backward_workspace_bytes(B, H, W, C, oh, ow))
+        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.check(L.vstab_st_symmetry_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), kind, dout.data_ptr(), oh, ow,
+                                                          d_img.data_ptr() if need_img else None, 1 if acc else 0,
+                                                          d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
+                                                          runtime.stream_ptr()))
     return (d_img if need_img else None), d_theta
 
 

@@ -210,8 +210,8 @@ VSTAB_API int vstab_host_tps_linv(int g, float *linv_t, int cap);
 VSTAB_API int vstab_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                          int interp, float *out, int oh, int ow, void *stream);
 /* ---- backward of the BILINEAR sampler: vstab_st_transform (affine and projective) and vstab_st_bilinear_interp.  These two are the
- * differentiable samplers besides the thin-plate spline and the homography warps (further down); bicubic and the symmetric-pad
- * transformers have no backward.
+ * differentiable samplers besides the thin-plate spline, the symmetric-pad transformers and the homography warps (further down);
+ * the bicubic sampler has no backward.
  * What TensorFlow's autodiff gives for ST:902-964 / 438-452 / 578-608: floor and the casts have zero derivative, the clip passes the
  * gradient where -1 <= x <= W inclusive (0 outside and for NaN), taps on the zero border receive nothing; coordinates and taps are
  * the forward's fp32 values.  img, B, H, W, C, theta | x, y, oh, ow as in the forward (B <= 65535, B*H*W*C < 2^31);
@@ -250,6 +250,32 @@ VSTAB_API size_t vstab_st_elastic_transform_backward_workspace_bytes(int B, int 
 VSTAB_API int vstab_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g,
                                                   const float *linv_t, const float *dout, int oh, int ow, float *d_img, int accumulate,
                                                   float *d_theta, void *workspace, size_t workspace_bytes, void *stream);
+/* ---- the symmetric-pad transformers (SimilarityTransformer, AffineSymmetryTransformer, ProjectiveSymmetryTransformer): what the
+ * forward computes on the way, and the backward of their BILINEAR sampler.  theta, kind, oh, ow as in vstab_st_symmetry_transform.
+ * vstab_st_symmetry_matrix: out [B,9], the pre-mapped row-major 3x3 matrices (affine kinds: last row 0 0 1), SimilarityTransformer's
+ *   interleave across samples included.  vstab_st_symmetry_coords: x_out, y_out [B*ow*oh], the normalised source coordinates of every
+ *   FINAL pixel (layout of the output, [B,ow,oh]) on the (H+200) x (W+200) padded extent; 0 where the crop-or-pad pads.  Both come from
+ *   the device code the forward calls, bit for bit, and need no image. */
+VSTAB_API int vstab_st_symmetry_matrix(const float *theta, int B, int kind, float *out, void *stream);
+VSTAB_API int vstab_st_symmetry_coords(const float *theta, int B, int kind, int oh, int ow, float *x_out, float *y_out, void *stream);
+/* vstab_st_symmetry_transform_backward: conventions, limits and error codes of vstab_st_transform_backward (d_img by float atomics, zero-
+ * filled on `stream` when accumulate == 0; a NULL output skips that gradient's work, both NULL is VSTAB_E_SHAPE; B*H*W*C < 2^31) and
+ * the forward's H, W >= 100.  What TensorFlow's autodiff gives for ST:311-371, 454-517, 611-716 with the bilinear sampler.
+ *   dout    [B,ow,oh,C], the gradient of the forward's output.  A pixel that the crop-or-pad pads contributes nothing: its dout is
+ *           not read into any sum.
+ *   d_img   [B,H,W,C] (nullable): the adjoint of gather . symmetric-pad -- a tap at padded index p adds into image pixel
+ *           refl(p - 100), several padded taps may fold onto one pixel; nothing for a tap on the zero border outside the padded extent.
+ *   d_theta [B,6|8|4] (nullable): overwritten; the gradient of the pre-mapped matrix is summed over the pixels in double in a fixed
+ *           order and taken through the pre-map in double, rounded to fp32 once -- two runs are bit-equal.  VSTAB_SYM_AFFINE: the
+ *           pre-map multiplies by 0, so d_theta is exactly zero for finite gradients (a non-finite one propagates).
+ *           VSTAB_SYM_PROJECTIVE divides by z as is (no safe_z): z == 0 propagates by IEEE rules.  VSTAB_SYM_SIMILARITY: through
+ *           cos / sin and the interleave, which couples the samples of a batch for B > 1.
+ *   workspace: vstab_st_symmetry_transform_backward_workspace_bytes(), 8-byte aligned; VSTAB_E_NOMEM when too small, not read when
+ *           d_theta is NULL.  0 for a shape outside the contract. */
+VSTAB_API size_t vstab_st_symmetry_transform_backward_workspace_bytes(int B, int H, int W, int C, int oh, int ow);
+VSTAB_API int vstab_st_symmetry_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind,
+                                                   const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
+                                                   void *workspace, size_t workspace_bytes, void *stream);
 /* ---- the 3-D volume transformer (spatial_transformer.py:227-308, 725-753, 794-899), forward and backward.  vol [B,D,H,W,C];
  * out_size = (od, oh, ow) = (depth, height, width) as the reference passes it.  One thread per output voxel, any C; a workgroup
  * owns a VSTAB_ST3D_BRICK_Z x _Y x _X brick of one sample's output.  64-bit element offsets: the limits are B <= 65535, every
