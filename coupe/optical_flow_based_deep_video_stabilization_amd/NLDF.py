@@ -56,10 +56,15 @@ class Model:
                 raise ValueError("NLDF.Model needs head_weights (or seed= for synthetic ones): the reference "
                                  "creates them with tf.get_variable and restores a checkpoint that is not available")
             head_weights = synthetic_head_weights(seed)
-        self.head_weights = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in head_weights.items()}
+        self.set_head_weights(head_weights)
+
+    def set_head_weights(self, head_weights: Dict[str, np.ndarray]):
+        """Replace the head's variables; the next build_model loads them into the trunk's context again."""
+        hw = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in head_weights.items()}
         for k, shp in HEAD_SHAPES.items():
-            if k not in self.head_weights or self.head_weights[k].shape != shp:
+            if k not in hw or hw[k].shape != shp:
                 raise ValueError(f"head weight {k}: expected shape {shp}")
+        self.head_weights = hw
         self._loaded_on = None
 
     def _load(self, ctx):
@@ -104,6 +109,7 @@ class Model:
         if nws == 0:
             raise ValueError(f"NLDF: unsupported batch {B}")
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        self._ws, self._ws_batch = ws, B                                  # kept for internals()
         pools = (C.c_void_p * 5)(vgg.pool1.data_ptr(), vgg.pool2.data_ptr(), vgg.pool3.data_ptr(), vgg.pool4.data_ptr(),
                                  vgg.pool5.data_ptr())
         with torch.cuda.device(dev):
@@ -111,3 +117,30 @@ class Model:
                                             self.Local_Fea.data_ptr(), self.Fea_Global.data_ptr(), ws.data_ptr(), nws,
                                             runtime.stream_ptr()), ctx._h)
         return self.Prob
+
+    def internals(self):
+        """Views (no copy, no launch) of the head's intermediate tensors in the workspace of the last build_model (tests):
+        G1 [B,7,7,128], G2 [B,3,3,128], cat1..cat5 = [Fea_Pk | Fea_Pk_LC | Fea_P(k+1)_Up] ([B,176,176,768] .. [B,11,11,256]),
+        Local_Score [B,176,176,2], Global_Score [B,1,1,2]."""
+        if getattr(self, "_ws", None) is None:
+            raise RuntimeError("internals() needs a build_model() call first")
+        views = workspace_views(self._ws, self._ws_batch)
+        del views["Local_Fea"]                # build_model has it written to self.Local_Fea: the workspace's copy is never touched
+        return views
+
+
+def workspace_views(ws: torch.Tensor, B: int) -> Dict[str, torch.Tensor]:
+    """Named views into a vstab_nldf_forward workspace `ws` (uint8) of batch B, by vstab_nldf_workspace_layout."""
+    ent = (_lib.VstabWsEntry * 16)()
+    n = _lib.lib().vstab_nldf_workspace_layout(B, ent, 16)
+    if n < 0:
+        _lib.check(n)
+    out = {}
+    for e in ent[:n]:
+        name = e.name.decode()
+        if e.h == 0:                          # the split-K partial sums
+            continue
+        nfl = e.n * e.h * e.w * e.c_stride
+        flat = ws[e.offset_bytes:e.offset_bytes + 4 * nfl].view(torch.float32)
+        out[name] = flat.view(e.n, e.h, e.w, e.c_stride)[..., :e.c]
+    return out

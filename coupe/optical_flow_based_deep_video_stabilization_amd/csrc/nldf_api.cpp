@@ -27,17 +27,23 @@ enum NBuf { N_G1, N_G2, N_G, N_CAT1, N_CAT2, N_CAT3, N_CAT4, N_CAT5, N_LF, N_LS,
 
 struct NldfPlan { size_t off[N_NBUF], bytes[N_NBUF], total; };
 
-size_t fl(int B, int hw, int c) { return (size_t)B * hw * hw * c; }
+// [B][hw][hw][c] per NBuf entry; hw == 0: a flat run of `c` floats whatever the batch (the split-K partial sums).  The one statement
+// of the workspace: nldf_plan sizes the buffers from it, vstab_nldf_workspace_layout reports it.
+struct NBufSpec { const char *name; int hw, c; };
+constexpr NBufSpec NBUFS[N_NBUF] = {
+    {"G1", 7, FEA},        {"G2", 3, FEA},         {"Fea_Global", 1, FEA}, {"cat1", 176, 768},       {"cat2", 88, 640},
+    {"cat3", 44, 512},     {"cat4", 22, 384},      {"cat5", 11, 256},      {"Local_Fea", 176, 640},  {"Local_Score", 176, 2},
+    {"Global_Score", 1, 2}, {"splitk", 0, 32 << 20}};
 
 bool nldf_plan(int B, NldfPlan &pl)
 {
     if (B < 1 || B > 64) return false;
-    size_t n[N_NBUF] = {fl(B, 7, FEA), fl(B, 3, FEA), fl(B, 1, FEA), fl(B, 176, 768), fl(B, 88, 640), fl(B, 44, 512),
-                        fl(B, 22, 384), fl(B, 11, 256), fl(B, 176, 640), fl(B, 176, 2), fl(B, 1, 2), (size_t)32 << 20};
     size_t off = 0;
     for (int i = 0; i < N_NBUF; ++i) {
-        if (n[i] * 4 >= 0x80000000ull) return false;
-        pl.off[i] = off; pl.bytes[i] = n[i] * 4;
+        const NBufSpec &s = NBUFS[i];
+        const size_t n = s.hw ? (size_t)B * s.hw * s.hw * s.c : (size_t)s.c;
+        if (n * 4 >= 0x80000000ull) return false;
+        pl.off[i] = off; pl.bytes[i] = n * 4;
         off += (pl.bytes[i] + 255) / 256 * 256;
     }
     pl.total = off;
@@ -71,6 +77,24 @@ extern "C" size_t vstab_nldf_workspace_bytes(int B)
     NldfPlan pl;
     if (!nldf_plan(B, pl)) { fail(nullptr, VSTAB_E_SHAPE, "nldf: unsupported batch %d", B); return 0; }
     return pl.total;
+}
+
+extern "C" int vstab_nldf_workspace_layout(int B, vstab_ws_entry *entries, int max_entries)
+{
+    NldfPlan pl;
+    if (!nldf_plan(B, pl)) return fail(nullptr, VSTAB_E_SHAPE, "nldf: unsupported batch %d", B);
+    if (!entries || max_entries < 0) return fail(nullptr, VSTAB_E_STATE, "nldf_workspace_layout: no entries");
+    int n = 0;
+    for (int i = 0; i < N_NBUF && n < max_entries; ++i, ++n) {
+        const NBufSpec &s = NBUFS[i];
+        vstab_ws_entry &e = entries[n];
+        std::memset(&e, 0, sizeof(e));
+        std::strncpy(e.name, s.name, sizeof(e.name) - 1);
+        e.offset_bytes = (int64_t)pl.off[i];
+        if (s.hw) { e.n = B; e.h = e.w = s.hw; e.c = e.c_stride = s.c; }
+        else { e.n = 1; e.h = 0; e.w = 0; e.c = e.c_stride = s.c; }             // h == 0: a flat run of c floats
+    }
+    return n;
 }
 
 extern "C" int vstab_nldf_load(vstab_ctx *ctx, const vstab_tensor *t, int count)

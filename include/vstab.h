@@ -379,6 +379,12 @@ VSTAB_API int vstab_maxpool2x2(const float *x, int B, int H, int W, int C, float
  * optional (NULL to skip). */
 VSTAB_API int vstab_nldf_load(vstab_ctx *ctx, const vstab_tensor *tensors, int count);
 VSTAB_API size_t vstab_nldf_workspace_bytes(int B);
+/* Host-only: names, offsets and shapes of the head's tensors inside that workspace, from the plan vstab_nldf_forward runs (tests):
+ * G1 [B,7,7,128], G2 [B,3,3,128], Fea_Global [B,1,1,128], cat1..cat5 = [Fea_Pk | Fea_Pk_LC | Fea_P(k+1)_Up] ([B,176,176,768],
+ * [B,88,88,640], [B,44,44,512], [B,22,22,384], [B,11,11,256]), Local_Fea (unused when the caller passes local_fea), Local_Score
+ * [B,176,176,2], Global_Score [B,1,1,2], splitk (h == 0: a flat run of c floats).  Returns the number of entries written
+ * (<= max_entries) or a negative error. */
+VSTAB_API int vstab_nldf_workspace_layout(int B, vstab_ws_entry *entries, int max_entries);
 VSTAB_API int vstab_nldf_forward(vstab_ctx *ctx, const float *const *pools5, int B, float *prob, float *score,
                                  float *local_fea, float *fea_global, void *workspace, size_t workspace_bytes,
                                  void *stream);

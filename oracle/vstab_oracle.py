@@ -502,41 +502,65 @@ def vgg_preprocess(x, dtype=torch.float32):
 
 
 # --------------------------------------------------------------------------- NLDF head (NLDF.py:24-101)
-def nldf_build_model(x, vgg_dict, hw, dtype=torch.float64):
+# The stage functions take and return NCHW tensors; W / b are the TF variables as stored ([k,k,Cin,Cout] for a convolution,
+# [k,k,Cout,Cin] for a transposed one).
+def nldf_conv(t, W_hwio, b, pad: int):
+    """Conv_2d (NLDF.py:103-114): stride 1, `pad` zeros on every side (0 = VALID, k // 2 = SAME), + bias; no activation."""
+    return F.conv2d(t, W_hwio.permute(3, 2, 0, 1), b, stride=1, padding=pad)
+
+
+def nldf_deconv(t, W_hwoi, b, out_hw: int):
+    """Deconv_2d (NLDF.py:116-129): 5x5 stride-2 SAME transposed convolution to out_hw = 2 * in, + bias; no activation.  Input
+    (iy, ix) adds filter tap (ky, kx) at output (2 iy + ky - 1, 2 ix + kx - 1); what falls outside out_hw x out_hw is cropped."""
+    y = F.conv_transpose2d(t, W_hwoi.permute(3, 2, 0, 1), b, stride=2, padding=1)     # weight as [Cin, Cout, kh, kw]
+    return y[:, :, :out_hw, :out_hw]
+
+
+def nldf_contrast(t):
+    """Contrast_Layer (NLDF.py:131-134): x - avg_pool3x3 of x padded by 1 with tf.pad 'SYMMETRIC' (the edge pixel repeated)."""
+    return t - F.avg_pool2d(F.pad(t, (1, 1, 1, 1), mode="replicate"), 3, 1)
+
+
+def nldf_score(ls, gs):
+    """NLDF.py:73-77: Score = Local_Score + Global_Score (broadcast over the image), Prob = softmax(Score)[..., 0].
+    NCHW in, NHWC out: (Score [B,H,W,2], Prob [B,H,W,1])."""
+    score = (ls + gs).permute(0, 2, 3, 1)
+    return score, torch.softmax(score, dim=3)[..., 0:1]
+
+
+NLDF_CAT_C = (768, 640, 512, 384, 256)          # cat_k = [Fea_Pk | Fea_Pk_LC | Fea_P(k+1)_Up] (NLDF.py:57-66)
+
+
+def nldf_build_model(x, vgg_dict, hw, dtype=torch.float64, return_internals=False):
     """Model.build_model (NLDF.py:24-101) on a [B,352,352,3] input in [0,1].  `hw` = head variables
-    {'<layer>/W', '<layer>/b'}.  Returns dict with Prob, Score, Local_Fea, Fea_Global."""
+    {'<layer>/W', '<layer>/b'}.  Returns dict with Prob, Score, Local_Fea, Fea_Global (NHWC); with return_internals also
+    G1, G2, cat1..cat5 (the concatenations the transposed convolutions and Local_Fea read), Local_Score, Global_Score."""
     v = vgg16_build(vgg_preprocess(x, dtype), vgg_dict, dtype)             # :29-31
     W = {k: _t(a, dtype) for k, a in hw.items()}
-
-    def conv(t, name, pad):                                               # Conv_2d (:103-114)
-        w = W[name + "/W"].permute(3, 2, 0, 1)
-        return F.conv2d(t, w, W[name + "/b"], stride=1, padding=pad)
-
-    def deconv(t, name, out_hw):                                          # Deconv_2d 5x5 s2 SAME (:116-129)
-        w = W[name + "/W"].permute(3, 2, 0, 1)                           # [Cin, Cout, kh, kw]
-        y = F.conv_transpose2d(t, w, W[name + "/b"], stride=2, padding=1)
-        return y[:, :, :out_hw, :out_hw]
-
-    def contrast(t):                                                      # Contrast_Layer (:131-134)
-        return t - F.avg_pool2d(F.pad(t, (1, 1, 1, 1), mode="replicate"), 3, 1)
-
+    conv = lambda t, name, pad: nldf_conv(t, W[name + "/W"], W[name + "/b"], pad)
+    deconv = lambda t, name, out_hw: nldf_deconv(t, W[name + "/W"], W[name + "/b"], out_hw)
     nchw = lambda t: t.permute(0, 3, 1, 2)
+    nhwc = lambda t: t.permute(0, 2, 3, 1)
     p1, p2, p3, p4, p5 = (nchw(v[f"pool{i}"]) for i in range(1, 6))
     g1 = torch.relu(conv(p5, "Fea_Global_1", 0))
     g2 = torch.relu(conv(g1, "Fea_Global_2", 0))
     fg = conv(g2, "Fea_Global", 0)
     fp = [torch.relu(conv(p, f"Fea_P{i}", 1)) for i, p in zip(range(1, 6), (p1, p2, p3, p4, p5))]
-    lc = [contrast(t) for t in fp]
-    up5 = torch.relu(deconv(torch.cat([fp[4], lc[4]], 1), "Fea_P5_Deconv", 22))
-    up4 = torch.relu(deconv(torch.cat([fp[3], lc[3], up5], 1), "Fea_P4_Deconv", 44))
-    up3 = torch.relu(deconv(torch.cat([fp[2], lc[2], up4], 1), "Fea_P3_Deconv", 88))
-    up2 = torch.relu(deconv(torch.cat([fp[1], lc[1], up3], 1), "Fea_P2_Deconv", 176))
-    lf = conv(torch.cat([fp[0], lc[0], up2], 1), "Local_Fea", 0)
+    lc = [nldf_contrast(t) for t in fp]
+    cat5 = torch.cat([fp[4], lc[4]], 1)
+    cat4 = torch.cat([fp[3], lc[3], torch.relu(deconv(cat5, "Fea_P5_Deconv", 22))], 1)
+    cat3 = torch.cat([fp[2], lc[2], torch.relu(deconv(cat4, "Fea_P4_Deconv", 44))], 1)
+    cat2 = torch.cat([fp[1], lc[1], torch.relu(deconv(cat3, "Fea_P3_Deconv", 88))], 1)
+    cat1 = torch.cat([fp[0], lc[0], torch.relu(deconv(cat2, "Fea_P2_Deconv", 176))], 1)
+    lf = conv(cat1, "Local_Fea", 0)
     ls = conv(lf, "Local_Score", 0)
     gs = conv(fg, "Global_Score", 0)
-    score = (ls + gs).permute(0, 2, 3, 1)
-    prob = torch.softmax(score, dim=3)[..., 0:1]
-    return {"Prob": prob, "Score": score, "Local_Fea": lf.permute(0, 2, 3, 1), "Fea_Global": fg.permute(0, 2, 3, 1)}
+    score, prob = nldf_score(ls, gs)
+    out = {"Prob": prob, "Score": score, "Local_Fea": nhwc(lf), "Fea_Global": nhwc(fg)}
+    if return_internals:
+        out.update({"G1": nhwc(g1), "G2": nhwc(g2), "cat1": nhwc(cat1), "cat2": nhwc(cat2), "cat3": nhwc(cat3), "cat4": nhwc(cat4),
+                    "cat5": nhwc(cat5), "Local_Score": nhwc(ls), "Global_Score": nhwc(gs)})
+    return out
 
 
 # --------------------------------------------------------------------------- clip driver (main:535-630)

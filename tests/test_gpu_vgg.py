@@ -50,6 +50,22 @@ def test_maxpool_same_on_odd_sizes():
     assert torch.equal(out.cpu(), ref)
 
 
+@pytest.mark.parametrize("shape", [(2, 5, 7, 64), (1, 1, 1, 4), (3, 11, 22, 128), (1, 6, 9, 512)])
+def test_maxpool_same_pads_with_minus_infinity(shape):
+    """TensorFlow's SAME pooling pads with -inf: the taps of a ragged window beyond the bottom / right edge take no part.  With an
+    all-negative input a kernel that padded with 0 would put a zero into every ragged window, so any difference is a failure."""
+    from coupe.optical_flow_based_deep_video_stabilization_amd import _lib, runtime
+    B, H, W, C = shape
+    x = torch.randn(shape, generator=torch.Generator().manual_seed(H * 100 + W)) - 10.0
+    assert float(x.max()) < 0
+    out = torch.full((B, (H + 1) // 2, (W + 1) // 2, C), float("nan"), device="cuda")
+    xg = x.cuda()
+    _lib.check(_lib.lib().vstab_maxpool2x2(xg.data_ptr(), B, H, W, C, out.data_ptr(), runtime.stream_ptr()))
+    ref = torch.nn.functional.max_pool2d(x.permute(0, 3, 1, 2), 2, 2, ceil_mode=True).permute(0, 2, 3, 1)
+    assert float(ref.max()) < 0
+    assert torch.equal(out.cpu(), ref)
+
+
 def test_vgg16_one_1080p_sample_is_finite_and_chunk_consistent():
     # config-5 resolution; conv1 activations of 2 samples are 1.06 GB each -> chunks of 3
     dd = vvgg.synthetic_data_dict(seed=4)

@@ -39,6 +39,27 @@ def test_vgg16_shapes_and_workspace():
     assert L.vstab_nldf_workspace_bytes(2) > L.vstab_nldf_workspace_bytes(1) > 0 and L.vstab_nldf_workspace_bytes(0) == 0
 
 
+def test_nldf_workspace_layout():
+    """vstab_nldf_workspace_layout states the plan vstab_nldf_workspace_bytes sizes: 256-byte aligned, in order, without overlap."""
+    want = [("G1", 7, 128), ("G2", 3, 128), ("Fea_Global", 1, 128), ("cat1", 176, 768), ("cat2", 88, 640), ("cat3", 44, 512),
+            ("cat4", 22, 384), ("cat5", 11, 256), ("Local_Fea", 176, 640), ("Local_Score", 176, 2), ("Global_Score", 1, 2)]
+    for B in (1, 2, 5):
+        ent = (_lib.VstabWsEntry * 16)()
+        n = L.vstab_nldf_workspace_layout(B, ent, 16)
+        assert n == len(want) + 1
+        end = 0
+        for e, (name, hw, c) in zip(ent, want):
+            assert (e.name.decode(), e.n, e.h, e.w, e.c, e.c_stride) == (name, B, hw, hw, c, c)
+            assert e.offset_bytes % 256 == 0 and e.offset_bytes >= end
+            end = e.offset_bytes + 4 * B * hw * hw * c
+        last = ent[n - 1]
+        assert last.name == b"splitk" and last.h == 0 and last.offset_bytes % 256 == 0 and last.offset_bytes >= end
+        assert last.offset_bytes + 4 * last.c <= L.vstab_nldf_workspace_bytes(B) < last.offset_bytes + 4 * last.c + 256
+    assert L.vstab_nldf_workspace_layout(2, ent, 3) == 3                       # truncated to max_entries
+    assert L.vstab_nldf_workspace_layout(0, ent, 16) == -1 and L.vstab_nldf_workspace_layout(65, ent, 16) == -1
+    assert L.vstab_nldf_workspace_layout(2, None, 16) < 0
+
+
 def test_chunks_are_equalised():
     # 32 samples at 720p: max chunk 21 -> two chunks of 16 (same plan, bit-identical results); the plan of a
     # 16-sample batch is what both chunks use

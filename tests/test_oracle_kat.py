@@ -383,3 +383,119 @@ def test_cv_warp_perspective_u8_hand_derived_and_exact_blend():
     interior = (ex >= 0) & (ex <= W - 1) & (ey >= 0) & (ey <= H - 1)
     g2 = vo.cv_warp_perspective_u8(smooth, M, H, W).astype(np.float64)
     assert np.abs(g2 - ref)[interior].max() <= 1.0
+
+
+# ---- NLDF head stages (NLDF.py:116-134 and TensorFlow's SAME rule): answers derived by hand
+def test_nldf_contrast_constant_ramp_and_corner_impulse():
+    # a constant image: the mean of nine equal values is that value (2.5 * 9 and / 9 are exact)
+    assert torch.equal(vo.nldf_contrast(torch.full((2, 3, 6, 7), 2.5, dtype=F64)), torch.zeros(2, 3, 6, 7, dtype=F64))
+    # horizontal ramp x[i] = d i: the 3-column mean is d i inside; at column 0 the repeated edge makes it d (0 + 0 + 1) / 3, at the
+    # last column d (W-2 + W-1 + W-1) / 3 = d (W-1) - d / 3: the layer gives -d/3, 0 ... 0, +d/3 on every row
+    for d, tol in ((3.0, 0.0), (0.7, 1e-15)):
+        H, W = 5, 8
+        ramp = (d * torch.arange(W, dtype=F64)).expand(1, 2, H, W).contiguous()
+        want = torch.zeros(1, 2, H, W, dtype=F64)
+        want[..., 0], want[..., W - 1] = -d / 3, d / 3
+        assert float((vo.nldf_contrast(ramp) - want).abs().max()) <= tol * W
+    # unit impulse in a corner: the symmetric pad repeats it into a 2x2 block, so the window of the corner pixel holds it 4 times,
+    # the two edge neighbours' windows twice, the diagonal neighbour's once; no other window reaches it
+    for cy, cx, sy, sx in ((0, 0, 1, 1), (5, 6, -1, -1), (0, 6, 1, -1)):
+        img = torch.zeros(1, 1, 6, 7, dtype=F64)
+        img[0, 0, cy, cx] = 1.0
+        want = torch.zeros(6, 7, dtype=F64)
+        want[cy, cx] = 1 - 4 / 9
+        want[cy + sy, cx], want[cy, cx + sx], want[cy + sy, cx + sx] = -2 / 9, -2 / 9, -1 / 9
+        assert float((vo.nldf_contrast(img)[0, 0] - want).abs().max()) <= 1e-16
+
+
+@pytest.mark.parametrize("n_in", [11, 22])
+def test_nldf_deconv_impulse_response(n_in):
+    # one input channel, one output channel, a unit impulse at (iy, ix): the output is the bias plus the 5x5 filter with its tap
+    # (ky, kx) at (2 iy + ky - 1, 2 ix + kx - 1), cropped to 2 n_in x 2 n_in (SAME, stride 2: NLDF.py:116-129).  Every value is a
+    # multiple of 1/8 below 2^10, so the sums are exact.
+    Wf = (torch.arange(25, dtype=F64).reshape(5, 5) + 1) / 8
+    b = torch.tensor([0.5], dtype=F64)
+    n_out = 2 * n_in
+    for iy, ix in ((0, 0), (n_in - 1, n_in - 1), (0, n_in - 1), (n_in - 1, 0), (n_in // 2, 3)):
+        x = torch.zeros(1, 1, n_in, n_in, dtype=F64)
+        x[0, 0, iy, ix] = 1.0
+        want = torch.full((n_out, n_out), 0.5, dtype=F64)
+        placed = 0
+        for ky in range(5):
+            for kx in range(5):
+                oy, ox = 2 * iy + ky - 1, 2 * ix + kx - 1
+                if 0 <= oy < n_out and 0 <= ox < n_out:
+                    want[oy, ox] += Wf[ky, kx]
+                    placed += 1
+        # the first row / column loses tap 0 (it lands on -1); the last loses taps 3 and 4 (2 (n_in - 1) + 3 - 1 = n_out and n_out + 1)
+        kept = lambda i: 4 if i == 0 else 3 if i == n_in - 1 else 5
+        assert placed == kept(iy) * kept(ix)
+        got = vo.nldf_deconv(x, Wf.reshape(5, 5, 1, 1), b, n_out)
+        assert got.shape == (1, 1, n_out, n_out) and torch.equal(got[0, 0], want), (iy, ix)
+
+
+def test_nldf_deconv_filter_layout_is_hw_out_in():
+    # tf.nn.conv2d_transpose takes [kh, kw, Cout, Cin] (NLDF.py:121-126): input channel ci reaches output channel co through W[:, :, co, ci]
+    Wf = torch.arange(5 * 5 * 3 * 2, dtype=F64).reshape(5, 5, 3, 2)
+    x = torch.zeros(1, 2, 4, 4, dtype=F64)
+    x[0, 1, 2, 1] = 1.0
+    got = vo.nldf_deconv(x, Wf, torch.zeros(3, dtype=F64), 8)
+    assert got.shape == (1, 3, 8, 8)
+    for co in range(3):
+        assert torch.equal(got[0, co, 3:8, 1:6], Wf[:, :, co, 1])           # taps 0..4 at rows 2*2-1 .. 2*2+3, columns 2*1-1 .. 2*1+3
+        assert float(got[0, co].abs().sum()) == float(Wf[:, :, co, 1].sum())
+
+
+def test_nldf_conv_and_score_known_answers():
+    # Conv_2d is a cross-correlation: a filter with a single 1 at (ky, kx) shifts the image by (ky - pad, kx - pad), zeros outside
+    x = torch.arange(16, dtype=F64).reshape(1, 1, 4, 4)
+    Wf = torch.zeros(3, 3, 1, 1, dtype=F64)
+    Wf[0, 2] = 1.0
+    got = vo.nldf_conv(x, Wf, torch.tensor([0.25], dtype=F64), 1)[0, 0]
+    want = torch.full((4, 4), 0.25, dtype=F64)
+    want[1:, :3] += x[0, 0, :3, 1:]
+    assert torch.equal(got, want)
+    assert vo.nldf_conv(x, Wf, torch.zeros(1, dtype=F64), 0).shape == (1, 1, 2, 2)          # VALID
+    # Score adds the sample's global pair to every pixel; Prob is the softmax's channel 0 = 1 / (1 + exp(s1 - s0))
+    ls = torch.tensor([[[[1.0, -2.0]], [[0.5, 3.0]]], [[[0.0, 0.0]], [[0.0, 0.0]]]], dtype=F64)       # [2,2,1,2] NCHW
+    gs = torch.tensor([[0.25, -0.25], [10.0, -20.0]], dtype=F64).reshape(2, 2, 1, 1)
+    score, prob = vo.nldf_score(ls, gs)
+    assert score.shape == (2, 1, 2, 2) and prob.shape == (2, 1, 2, 1)
+    assert score[0, 0].tolist() == [[1.25, 0.25], [-1.75, 2.75]] and score[1, 0].tolist() == [[10.0, -20.0], [10.0, -20.0]]
+    want_p = 1 / (1 + np.exp(np.array([[0.25 - 1.25, 2.75 + 1.75], [-30.0, -30.0]])))
+    assert np.abs(prob[..., 0].numpy()[:, 0] - want_p).max() <= 1e-15
+
+
+def test_nldf_build_model_is_the_composition_of_its_stages():
+    """The stage functions, composed here as NLDF.py:36-77 composes them, give nldf_build_model's tensors bit for bit in fp64 (one
+    sample at the head's only geometry; the trunk is evaluated once and shared), and return_internals adds tensors, changes none."""
+    from coupe.optical_flow_based_deep_video_stabilization_amd import NLDF as vnldf, vgg16 as vvgg
+    dd, hw = vvgg.synthetic_data_dict(seed=5), vnldf.synthetic_head_weights(seed=6, gain=1.5)
+    x = torch.rand(1, 352, 352, 3, generator=torch.Generator().manual_seed(1))
+    full = vo.nldf_build_model(x, dd, hw, F64, return_internals=True)
+    assert set(full) == {"Prob", "Score", "Local_Fea", "Fea_Global", "G1", "G2", "cat1", "cat2", "cat3", "cat4", "cat5", "Local_Score",
+                         "Global_Score"}
+    v = vo.vgg16_build(vo.vgg_preprocess(x, F64), dd, F64)
+    P = {k: torch.as_tensor(a, dtype=F64) for k, a in hw.items()}
+    nchw, nhwc = (lambda t: t.permute(0, 3, 1, 2)), (lambda t: t.permute(0, 2, 3, 1))
+    conv = lambda t, n, pad: vo.nldf_conv(t, P[n + "/W"], P[n + "/b"], pad)
+    g1 = torch.relu(conv(nchw(v["pool5"]), "Fea_Global_1", 0))
+    g2 = torch.relu(conv(g1, "Fea_Global_2", 0))
+    fg = conv(g2, "Fea_Global", 0)
+    assert g1.shape == (1, 128, 7, 7) and g2.shape == (1, 128, 3, 3) and fg.shape == (1, 128, 1, 1)
+    up, cats = None, {}
+    for k in (5, 4, 3, 2, 1):
+        fp = torch.relu(conv(nchw(v[f"pool{k}"]), f"Fea_P{k}", 1))
+        parts = [fp, vo.nldf_contrast(fp)] + ([] if up is None else [up])
+        cats[k] = torch.cat(parts, 1)
+        assert cats[k].shape == (1, vo.NLDF_CAT_C[k - 1], 352 >> k, 352 >> k)
+        if k > 1:
+            up = torch.relu(vo.nldf_deconv(cats[k], P[f"Fea_P{k}_Deconv/W"], P[f"Fea_P{k}_Deconv/b"], 352 >> (k - 1)))
+    lf = conv(cats[1], "Local_Fea", 0)
+    ls, gs = conv(lf, "Local_Score", 0), conv(fg, "Global_Score", 0)
+    score, prob = vo.nldf_score(ls, gs)
+    mine = {"Prob": prob, "Score": score, "Local_Fea": nhwc(lf), "Fea_Global": nhwc(fg), "G1": nhwc(g1), "G2": nhwc(g2),
+            "Local_Score": nhwc(ls), "Global_Score": nhwc(gs), **{f"cat{k}": nhwc(c) for k, c in cats.items()}}
+    for name, t in full.items():
+        assert t.dtype == F64 and torch.equal(t, mine[name]), name
+    assert full["Prob"].shape == (1, 176, 176, 1) and full["Score"].shape == (1, 176, 176, 2)
