@@ -79,6 +79,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the three extra steps with an event pair around every conv-family call")
     ap.add_argument("--phases", action="store_true", help="also time forward / loss+backward / Adam separately (adds syncs)")
+    ap.add_argument("--objective", choices=("noprev", "prev", "prev_hightv"), default="noprev",
+                    help="loss_main of which reference script: noprev = main_flownetS_pyramid_noprevloss_dataloader.py (default), prev = "
+                         "main_flownetS_pyramid.py, prev_hightv = main_flownetS_pyramid_highTV_noBBloss.py (24-channel stable tensor)")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel replicas to start when not already under a launcher")
     args = ap.parse_args()
     import importlib.util
@@ -102,14 +105,17 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29541")
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-    from coupe.optical_flow_based_deep_video_stabilization_amd import netspec, train_step, weights as wts
+    from coupe.optical_flow_based_deep_video_stabilization_amd import netspec, train_step, training, weights as wts
 
     B, H, W = args.batch, args.height, args.width
     w = wts.synthetic_weights(seed=1, cin=27, random_bn=False, flow_gain=0.2)
-    tr = train_step.Trainer(w, B, H, W)
+    # noprev keeps the Trainer's default code path (objective None), so its row stays comparable with earlier runs
+    tr = train_step.Trainer(w, B, H, W, objective=None if args.objective == "noprev" else training.OBJECTIVES[args.objective])
     g = torch.Generator().manual_seed(rank)                # every replica trains on its own shard
     feats = torch.rand(B, H, W, 27, generator=g).cuda()
     gt, un = torch.rand(B, H, W, 3, generator=g).cuda(), torch.rand(B, H, W, 3, generator=g).cuda()
+    if args.objective != "noprev":                         # the scripts' 24-channel stab_image placeholder; channels 0:3 as above
+        gt = torch.cat([gt, torch.rand(B, H, W, 21, generator=g).cuda()], dim=3)
     for _ in range(args.warmup):
         loss = tr.step(feats, gt, un, lr=1e-4)
     torch.cuda.synchronize()
@@ -130,15 +136,23 @@ def main():
         dt = float(tmax[0])
     phases = None
     if args.phases:
-        tf = tb = ta = 0.0
+        tf = tb = ta = tl = 0.0
         for _ in range(args.steps):
             torch.cuda.synchronize(); a = time.perf_counter()
             tr.forward(feats); torch.cuda.synchronize(); b = time.perf_counter()
             tr.loss_and_backward(gt, un); torch.cuda.synchronize(); c = time.perf_counter()
             tr.adam(1e-4); torch.cuda.synchronize(); d = time.perf_counter()
             tf += b - a; tb += c - b; ta += d - c
+        # the loss phase alone (value + flow gradients into dpf, as loss_and_backward issues it), in a loop of its own after the three phases
+        for _ in range(args.steps):
+            torch.cuda.synchronize(); a = time.perf_counter()
+            if tr.objective is None:
+                training.loss_main_fused(tr.pf, gt, un, tr.dpf)
+            else:
+                training.loss_main_multi(tr.pf, gt, un, tr.objective, tr.dpf)
+            torch.cuda.synchronize(); tl += time.perf_counter() - a
         phases = {"forward_ms": round(tf / args.steps * 1e3, 3), "loss_backward_ms": round(tb / args.steps * 1e3, 3),
-                  "adam_ms": round(ta / args.steps * 1e3, 3)}
+                  "adam_ms": round(ta / args.steps * 1e3, 3), "loss_ms": round(tl / args.steps * 1e3, 3)}
     # ---- roofline of the step's MFMA-bound calls: three more steps with an event pair (on the launch stream) around every conv-family
     # library call; a call's time includes its helper launches (operand packing, split-K combine, pixel tables), so the fractions are
     # lower bounds on the MFMA kernels' own.  flops = 2*MAC of the layer each call computes (forward, input gradient and filter gradient
@@ -182,7 +196,7 @@ def main():
             dist.destroy_process_group()
         return
     print(json.dumps({
-        "metric": f"training samples/sec @{H}x{W}", "value": round(B * world / dt, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
+        "metric": f"training samples/sec @{H}x{W} objective={args.objective}", "objective": args.objective, "value": round(B * world / dt, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
         "scaling": "weak", "vs_baseline": None,
         "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "dtype": "f32",
         "data": "synthetic (uniform [0,1) frames, seeded He-normal weights)", "final_loss": float(loss),

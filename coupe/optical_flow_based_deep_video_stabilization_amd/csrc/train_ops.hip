@@ -213,6 +213,254 @@ hipError_t launch_loss_main(const LossLevel *lv, int n, const float *gtstab, con
 }
 
 // ---------------------------------------------------------------------------------
+// The objective of the reference's other two training scripts (main_flownetS_pyramid.py:200-250 and the highTV file): at every
+// level the warped unstable frame is compared with T targets -- the ground-truth stable frame and five earlier stabilised frames,
+// 3-channel slices of one [B,h,w,Ct] tensor -- each with its own weight c_t:
+//   L = sum_t c_t * mean_b(num_{t,b} / den_b) + scale_tv * TV
+// The warp P, the mask M, sum safe(M) and TV do not depend on the target, so a pixel does its flow read, corners(), four-tap
+// gather, M and TV contribution ONCE and then reads T targets.  The gradient shares 2 M^2 / (B den_b) and the slope; per channel
+// the residual is e = sum_t c_t * (P - g_t), accumulated in float32 in target order with the first term taken as is.  Everything
+// else is loss_sums_kernel / loss_grad_kernel operation for operation: with T = 1 and c = 1 the results are bit-equal to theirs.
+// Per-sample sums: double[T + 2] = num_0..num_{T-1}, den, tv.
+// ---------------------------------------------------------------------------------
+struct LossTargets { int Ct; int c_off[LOSS_MAX_TARGETS]; float c[LOSS_MAX_TARGETS]; };
+
+template <int T>
+__global__ __launch_bounds__(256) void loss_sums_multi_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G,
+                                                              LossTargets tg, const float *__restrict__ U, int h, int w,
+                                                              double *__restrict__ sums)
+{
+    const int n = blockIdx.y;
+    double num[T], den = 0.0, tv = 0.0;
+#pragma unroll
+    for (int t = 0; t < T; ++t) num[t] = 0.0;
+    const float *fb = pf + (long long)n * h * w * cs_pf;
+    auto flow = [&](int i) { return *reinterpret_cast<const f32x2 *>(fb + (long long)i * cs_pf); };
+    for (int it = 0; it < LOSS_PPT; ++it) {
+        const int idx = (blockIdx.x * LOSS_PPT + it) * 256 + threadIdx.x;
+        if (idx >= h * w) break;
+        const int yy = idx / w, xx = idx - yy * w;
+        const f32x2 f = flow(idx);
+        const Corners c = corners(xx, yy, f, h, w);
+        const float wa = (c.x1f - c.x) * (c.y1f - c.y), wb = (c.x1f - c.x) * (c.y - c.y0f);
+        const float wc = (c.x - c.x0f) * (c.y1f - c.y), wd = (c.x - c.x0f) * (c.y - c.y0f);
+        const float M = ((wa + wb) + wc) + wd;
+        const float *ub = U + (long long)n * h * w * 3;
+        const float *Ia = ub + (c.y0 * w + c.x0) * 3, *Ib = ub + (c.y1 * w + c.x0) * 3;
+        const float *Ic = ub + (c.y0 * w + c.x1) * 3, *Id = ub + (c.y1 * w + c.x1) * 3;
+        const float *g = G + ((long long)n * h * w + idx) * tg.Ct;
+        float PM[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) PM[ch] = (((wa * Ia[ch] + wb * Ib[ch]) + wc * Ic[ch]) + wd * Id[ch]) * M;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const float *gt = g + tg.c_off[t];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const float d = PM[ch] - gt[ch] * M;
+                num[t] += (double)(d * d);
+            }
+        }
+        den += 3.0 * (double)(M == 0.f ? M + 1e-8f : M);
+        if (yy + 1 < h) { const f32x2 q = flow(idx + w); tv += (double)fabsf(q.x - f.x) + (double)fabsf(q.y - f.y); }
+        if (xx + 1 < w) { const f32x2 q = flow(idx + 1); tv += (double)fabsf(q.x - f.x) + (double)fabsf(q.y - f.y); }
+    }
+    __shared__ double red[T + 2][4];
+    const int wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const double s = wave_sum(num[t]);
+        if (lead) red[t][wave] = s;
+    }
+    den = wave_sum(den); tv = wave_sum(tv);
+    if (lead) { red[T][wave] = den; red[T + 1][wave] = tv; }
+    __syncthreads();
+    if ((int)threadIdx.x < T + 2) {
+        const double s = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+        atomicAdd(&sums[(T + 2) * n + threadIdx.x], s);
+    }
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void loss_grad_multi_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G,
+                                                              LossTargets tg, const float *__restrict__ U, int B, int h, int w,
+                                                              const double *__restrict__ sums, float scale_tv, float *__restrict__ grad,
+                                                              int cs_g)
+{
+    const int n = blockIdx.y;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= h * w) return;
+    const int yy = idx / w, xx = idx - yy * w;
+    const float *fb = pf + (long long)n * h * w * cs_pf;
+    auto flow = [&](int i) { return *reinterpret_cast<const f32x2 *>(fb + (long long)i * cs_pf); };
+    const f32x2 f = flow(idx);
+    const Corners c = corners(xx, yy, f, h, w);
+    const float wa = (c.x1f - c.x) * (c.y1f - c.y), wb = (c.x1f - c.x) * (c.y - c.y0f);
+    const float wc = (c.x - c.x0f) * (c.y1f - c.y), wd = (c.x - c.x0f) * (c.y - c.y0f);
+    const float M = ((wa + wb) + wc) + wd;
+    const float *ub = U + (long long)n * h * w * 3;
+    const float *Ia = ub + (c.y0 * w + c.x0) * 3, *Ib = ub + (c.y1 * w + c.x0) * 3;
+    const float *Ic = ub + (c.y0 * w + c.x1) * 3, *Id = ub + (c.y1 * w + c.x1) * 3;
+    const float *g = G + ((long long)n * h * w + idx) * tg.Ct;
+    const float k = 2.f * M * M / ((float)B * (float)sums[(T + 2) * n + T]);
+    float gx = 0.f, gy = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float a = Ia[ch], b = Ib[ch], cc = Ic[ch], d = Id[ch];
+        const float P = ((wa * a + wb * b) + wc * cc) + wd * d;
+        float e = tg.c[0] * (P - g[tg.c_off[0] + ch]);
+#pragma unroll
+        for (int t = 1; t < T; ++t) e += tg.c[t] * (P - g[tg.c_off[t] + ch]);
+        gx += e * ((c.y1f - c.y) * (cc - a) + (c.y - c.y0f) * (d - b));
+        gy += e * ((c.x1f - c.x) * (b - a) + (c.x - c.x0f) * (d - cc));
+    }
+    gx *= k; gy *= k;
+    auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); };
+    float tx = 0.f, ty = 0.f;
+    if (yy + 1 < h) { const f32x2 q = flow(idx + w); tx -= sgn(q.x - f.x); ty -= sgn(q.y - f.y); }
+    if (xx + 1 < w) { const f32x2 q = flow(idx + 1); tx -= sgn(q.x - f.x); ty -= sgn(q.y - f.y); }
+    if (yy > 0) { const f32x2 q = flow(idx - w); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
+    if (xx > 0) { const f32x2 q = flow(idx - 1); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
+    f32x2 o;
+    o.x = gx + scale_tv * tx;
+    o.y = gy + scale_tv * ty;
+    *reinterpret_cast<f32x2 *>(grad + ((long long)n * h * w + idx) * cs_g) = o;
+}
+
+// out[0] = sum over levels of [ sum_t c_t * mean_b(num_t/den) + tv_weight * sum_b TV ]; out[1 + t] = sum over levels of
+// mean_b(num_t/den), target t's unweighted share
+struct LossTotalMultiArgs { float tvw[8]; float c[LOSS_MAX_TARGETS]; int n, T; };
+__global__ void loss_total_multi_kernel(const double *__restrict__ sums, int B, LossTotalMultiArgs a, double *__restrict__ out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int S = a.T + 2;
+    double total = 0.0, per[LOSS_MAX_TARGETS];
+    for (int t = 0; t < a.T; ++t) per[t] = 0.0;
+    for (int l = 0; l < a.n; ++l) {
+        const double *s = sums + (long long)l * S * B;
+        double tv = 0.0, lvl = 0.0;
+        for (int b = 0; b < B; ++b) tv += s[S * b + a.T + 1];
+        for (int t = 0; t < a.T; ++t) {
+            double mse = 0.0;
+            for (int b = 0; b < B; ++b) mse += s[S * b + t] / s[S * b + a.T];
+            mse = mse / (double)B;
+            per[t] += mse;
+            lvl = t == 0 ? (double)a.c[0] * mse : lvl + (double)a.c[t] * mse;
+        }
+        total += lvl + (double)a.tvw[l] * tv;
+    }
+    out[0] = total;
+    for (int t = 0; t < a.T; ++t) out[1 + t] = per[t];
+}
+
+template <int T>
+static hipError_t loss_level_multi_kernels(const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B, int h,
+                                           int w, double *sums, float scale_tv, float *grad, int cs_g, hipStream_t stream)
+{
+    const int npix = h * w;
+    loss_sums_multi_kernel<T><<<dim3((unsigned)((npix + 256 * LOSS_PPT - 1) / (256 * LOSS_PPT)), (unsigned)B), dim3(256), 0, stream>>>(
+        pf, cs_pf, G, tg, U, h, w, sums);
+    if (grad)
+        loss_grad_multi_kernel<T><<<dim3((unsigned)((npix + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U, B, h, w, sums,
+                                                                                                          scale_tv, grad, cs_g);
+    return hipGetLastError();
+}
+
+static hipError_t loss_level_multi_dispatch(int T, const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B,
+                                            int h, int w, double *sums, float scale_tv, float *grad, int cs_g, hipStream_t stream)
+{
+    switch (T) {
+#define VSTAB_LOSS_T(N) case N: return loss_level_multi_kernels<N>(pf, cs_pf, G, tg, U, B, h, w, sums, scale_tv, grad, cs_g, stream)
+        VSTAB_LOSS_T(1); VSTAB_LOSS_T(2); VSTAB_LOSS_T(3); VSTAB_LOSS_T(4); VSTAB_LOSS_T(5); VSTAB_LOSS_T(6); VSTAB_LOSS_T(7); VSTAB_LOSS_T(8);
+#undef VSTAB_LOSS_T
+    }
+    return hipErrorInvalidValue;
+}
+
+static LossTargets loss_targets(int Ct, int T, const int *c_off, const float *weights)
+{
+    LossTargets tg = {};
+    tg.Ct = Ct;
+    for (int t = 0; t < T; ++t) { tg.c_off[t] = c_off[t]; tg.c[t] = weights[t]; }
+    return tg;
+}
+
+hipError_t launch_loss_level_multi(const float *pf, const float *G, int Ct, int T, const int *c_off, const float *weights, const float *U,
+                                   int B, int h, int w, double *sums, float scale_tv, float *grad, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * (size_t)(T + 2) * B, stream);
+    if (e != hipSuccess) return e;
+    return loss_level_multi_dispatch(T, pf, 2, G, loss_targets(Ct, T, c_off, weights), U, B, h, w, sums, scale_tv, grad, 2, stream);
+}
+
+// workspace: the sums of every level, then the resized targets [B,h,w,Ct] and the resized unstable frame [B,h,w,3] of the largest level
+static void loss_main_multi_layout(int B, const LossLevel *lv, int n, int Ct, int T, size_t &sbytes, size_t &gbytes, size_t &ubytes)
+{
+    size_t pix = 0;
+    for (int l = 0; l < n; ++l) pix = std::max(pix, (size_t)B * lv[l].h * lv[l].w);
+    sbytes = ((size_t)n * (T + 2) * B * sizeof(double) + 255) & ~(size_t)255;
+    gbytes = (pix * Ct * sizeof(float) + 255) & ~(size_t)255;
+    ubytes = (pix * 3 * sizeof(float) + 255) & ~(size_t)255;
+}
+
+size_t loss_main_multi_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int T)
+{
+    size_t s, g, u;
+    loss_main_multi_layout(B, lv, n, Ct, T, s, g, u);
+    return 256 + s + g + u;
+}
+
+// All levels of the multi-target objective in one call: per level ONE resize of the whole target tensor (all Ct channels) and one of
+// the unstable frame, the pair above with the gradient written straight into the caller's (strided) flow-gradient buffer; then the
+// scalars.  No allocation.
+// ONE target of weight 1 has nothing to share: its levels resize the target's three channels alone (read in place from the Ct-channel
+// tensor) and run loss_sums_kernel / loss_grad_kernel themselves -- the same launches, hence the same fp64 atomics, as launch_loss_main
+// on that slice, so the value is launch_loss_main's bit for bit at every size (with T + 2 = 3 the sums have its layout).  A level the
+// slice resize does not take (same size inside wider pixels, or too large for the tile kernel) goes the general way.
+hipError_t launch_loss_main_multi(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                                  const float *unstab, int B, int H, int W, double *loss_out, void *workspace, hipStream_t stream)
+{
+    size_t sbytes, gbytes, ubytes;
+    loss_main_multi_layout(B, lv, n, Ct, T, sbytes, gbytes, ubytes);
+    char *p = static_cast<char *>(workspace);
+    double *sums = reinterpret_cast<double *>(p);
+    float *G = reinterpret_cast<float *>(p + sbytes), *U = reinterpret_cast<float *>(p + sbytes + gbytes);
+    const int S = T + 2;
+    hipError_t e = hipMemsetAsync(sums, 0, (size_t)n * S * B * sizeof(double), stream);
+    if (e != hipSuccess) return e;
+    const LossTargets tg = loss_targets(Ct, T, c_off, weights);
+    LossTotalMultiArgs a = {};
+    a.n = n;
+    a.T = T;
+    for (int t = 0; t < T; ++t) a.c[t] = weights[t];
+    const bool single = T == 1 && weights[0] == 1.0f;
+    for (int l = 0; l < n; ++l) {
+        a.tvw[l] = lv[l].tv_weight;
+        bool sliced = false;
+        if (single && Ct == 3) {
+            if ((e = launch_resize_bilinear(targets, B, H, W, 3, G, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
+            sliced = true;
+        } else if (single && (lv[l].h != H || lv[l].w != W)) {
+            e = launch_resize_bilinear_slice3(targets, B, H, W, Ct, c_off[0], G, lv[l].h, lv[l].w, stream);
+            if (e != hipSuccess && e != hipErrorNotSupported) return e;
+            sliced = e == hipSuccess;
+        }
+        if (!sliced && (e = launch_resize_bilinear(targets, B, H, W, Ct, G, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
+        if ((e = launch_resize_bilinear(unstab, B, H, W, 3, U, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
+        if (sliced) {
+            if ((e = loss_level_kernels(lv[l].pf, lv[l].cs_pf, G, U, B, lv[l].h, lv[l].w, sums + (size_t)l * S * B, 1.0f, lv[l].tv_weight, lv[l].grad,
+                                        lv[l].cs_grad, stream)) != hipSuccess)
+                return e;
+        } else if ((e = loss_level_multi_dispatch(T, lv[l].pf, lv[l].cs_pf, G, tg, U, B, lv[l].h, lv[l].w, sums + (size_t)l * S * B, lv[l].tv_weight,
+                                           lv[l].grad, lv[l].cs_grad, stream)) != hipSuccess)
+            return e;
+    }
+    loss_total_multi_kernel<<<1, 64, 0, stream>>>(sums, B, a, loss_out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
 // BatchNormLayer(act = lrelu 0.1, is_train = True, gamma_init = None) (model.py:809 etc.; TensorLayer 1.x):
 //   mean, var = tf.nn.moments(z, [0,1,2])  (population variance);  y = lrelu((z - mean) * rsqrt(var + eps) + beta);
 //   moving = moving * decay + batch * (1 - decay)   (assign_moving_average, zero_debias = False)

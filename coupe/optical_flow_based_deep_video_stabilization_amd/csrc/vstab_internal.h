@@ -525,6 +525,14 @@ struct LossLevel { const float *pf; float *grad; int h, w, cs_pf, cs_grad; float
 size_t loss_main_workspace_bytes(int B, const LossLevel *lv, int n);
 hipError_t launch_loss_main(const LossLevel *lv, int n, const float *gtstab, const float *unstab, int B, int H, int W, double *loss_out,
                             void *workspace, hipStream_t stream);
+// the same objective against T weighted 3-channel targets inside one [B,h,w,Ct] tensor (the previous-frame terms of
+// main_flownetS_pyramid.py:200-250): sums = double[(T+2)*B] = num_0..num_{T-1}, den, tv per sample; c_off / weights are host arrays
+constexpr int LOSS_MAX_TARGETS = 8;
+hipError_t launch_loss_level_multi(const float *pf, const float *G, int Ct, int T, const int *c_off, const float *weights, const float *U,
+                                   int B, int h, int w, double *sums, float scale_tv, float *grad, hipStream_t stream);
+size_t loss_main_multi_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int T);
+hipError_t launch_loss_main_multi(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                                  const float *unstab, int B, int H, int W, double *loss_out, void *workspace, hipStream_t stream);
 hipError_t launch_flow_medfilt(const float *flow, int B, int h, int w, int kh, int kw, int kc, float *out, hipStream_t stream);
 
 // dense-flow homography fit + cv2.warpPerspective on 8-bit frames (homography_ops.hip)

@@ -58,10 +58,15 @@ def _pad_to(t: torch.Tensor, shape) -> torch.Tensor:
 
 class Trainer:
     """Holds the (padded, device-resident) parameters, BatchNorm moving statistics and Adam state; `step()` = one
-    `sess.run(optim_main)` of the reference."""
+    `sess.run(optim_main)` of the reference.  objective None: the objective of main_flownetS_pyramid_noprevloss_dataloader.py
+    (`loss_main_fused`); a `training.Objective` (OBJECTIVE_PREV = main_flownetS_pyramid.py, OBJECTIVE_PREV_HIGHTV =
+    main_flownetS_pyramid_highTV_noBBloss.py): that script's loss_main through `loss_main_multi` -- the third argument of
+    `loss_and_backward`, `step` and the batches of `train_epoch` is then the multi-channel stable tensor `stab_image` [B,H,W,Ct]
+    (24 channels in the scripts) instead of gtstab."""
 
-    def __init__(self, weights: Dict[str, np.ndarray], batch: int, height: int, width: int, device=None):
+    def __init__(self, weights: Dict[str, np.ndarray], batch: int, height: int, width: int, device=None, objective=None):
         runtime._require_gpu()
+        self.objective = objective
         self.dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.B, self.H, self.W = int(batch), int(height), int(width)
         self.sizes = list(netspec.sizes_for(self.H, self.W).enc)              # spatial size after every encoder stage
@@ -415,10 +420,14 @@ class Trainer:
 
     # ------------------------------------------------------------------ loss + backward
     def loss_and_backward(self, gtstab: torch.Tensor, unstab: torch.Tensor) -> torch.Tensor:
-        """loss_main (main:213-217, 269-275) and d loss_main / d every trainable tensor (into self.g)."""
-        from .training import loss_main_fused
+        """loss_main (main:213-217, 269-275; with an objective: main_flownetS_pyramid.py:200-250) and d loss_main / d every trainable
+        tensor (into self.g)."""
+        from .training import loss_main_fused, loss_main_multi
         self._zero_grads()
-        total = loss_main_fused(self.pf, gtstab, unstab, self.dpf)        # all five levels, gradients straight into dpf[..., :2]
+        if self.objective is None:
+            total = loss_main_fused(self.pf, gtstab, unstab, self.dpf)    # all five levels, gradients straight into dpf[..., :2]
+        else:                                                             # gtstab is the multi-channel stable tensor [B,H,W,Ct]
+            total, _per = loss_main_multi(self.pf, gtstab, unstab, self.objective, self.dpf)
         self._backward()
         return total
 

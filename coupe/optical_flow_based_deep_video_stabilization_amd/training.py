@@ -5,10 +5,14 @@ of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and it
 gradients of the bilinear spatial transformers (`st_transform_backward`, `st_symmetry_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`)
 and of warp.py's homography warp and matrix exponential (`homography_warp_backward`, `vec2mtrx_backward`).
 `train_step.Trainer` strings them into the whole step (forward, loss, backward, Adam: main:184-185, 333-335).
+The objective of the reference's other two training scripts -- the same terms plus five weighted comparisons with earlier stabilised
+frames -- is `Objective` / `lossterm_multi` / `loss_main_multi` (main_flownetS_pyramid.py:200-250).
 
 Everything runs in the HIP library (csrc/train_ops.hip); there is no CPU path."""
 from __future__ import annotations
 
+import math
+from dataclasses import dataclass
 from typing import Dict, Tuple
 
 import torch
@@ -88,6 +92,131 @@ def loss_main_fused(flows: Dict[str, torch.Tensor], gtstab_image, unstab_image, 
         _lib.check(L.vstab_loss_main(C.addressof(desc), len(LOSS_LEVELS), stab.data_ptr(), unstab.data_ptr(), B, H, W, out.data_ptr(),
                                      ws.data_ptr(), n, runtime.stream_ptr()))
     return out
+
+
+# ----------------------------------------------------------------------------- the objective with the previous-frame terms
+# main_flownetS_pyramid.py:214-242 writes the weights of the five previous-frame terms as np.exp(-1/3), np.exp(-2/3), np.exp(-3/3),
+# np.exp(-6/3), np.exp(-14/3).  The script is Python 2 (print statements at :358-360) without `from __future__ import division`, so
+# -1/3 is FLOOR division: -1, -1, -1, -2, -5.  Those are the weights its checkpoints were trained with, and the presets' weights.
+PREV_WEIGHTS_PY2_FLOOR_DIVISION = (math.exp(-1.0), math.exp(-1.0), math.exp(-1.0), math.exp(-2.0), math.exp(-5.0))
+# What the expressions would give under true division (Python 3 semantics): offered by name for whoever wants the weights as they
+# read on the page; no preset uses them.
+PREV_WEIGHTS_TRUE_DIVISION = (math.exp(-1.0 / 3.0), math.exp(-2.0 / 3.0), math.exp(-1.0), math.exp(-2.0), math.exp(-14.0 / 3.0))
+
+
+@dataclass(frozen=True)
+class Objective:
+    """loss_main of one of the reference's training scripts: at every pyramid level (LOSS_LEVELS order)
+    sum_t target_weights[t] * lossterm(flow, stab[..., target_channels[t] : +3], unstab) + tv_weights[level] * total_variation(flow).
+    The weights are stated in double and rounded to float32 where the library's ABI carries float (as `tv_weight` always was).
+
+    Presets: OBJECTIVE_NOPREV = main_flownetS_pyramid_noprevloss_dataloader.py, OBJECTIVE_PREV = main_flownetS_pyramid.py,
+    OBJECTIVE_PREV_HIGHTV = main_flownetS_pyramid_highTV_noBBloss.py.  The two prev presets weigh the five earlier frames with
+    PREV_WEIGHTS_PY2_FLOOR_DIVISION = exp(-1), exp(-1), exp(-1), exp(-2), exp(-5): the scripts write np.exp(-1/3) ... np.exp(-14/3)
+    and run under Python 2, where -1/3 floors to -1 and -14/3 to -5, so these are the values their checkpoints were trained with.
+    PREV_WEIGHTS_TRUE_DIVISION = exp(-1/3), exp(-2/3), exp(-1), exp(-2), exp(-14/3) is what the same text means under true
+    division; pass it to `with_target_weights` to get that variant.  Level 4's TV weight is 0 in both prev presets: the scripts
+    compute var4 but leave it out of the sum."""
+    target_channels: Tuple[int, ...]
+    target_weights: Tuple[float, ...]
+    tv_weights: Tuple[float, ...]
+
+    def __post_init__(self):
+        if not 1 <= len(self.target_channels) <= 8 or len(self.target_weights) != len(self.target_channels):
+            raise ValueError("an Objective has 1..8 targets, one weight each")
+        if len(self.tv_weights) != len(LOSS_LEVELS):
+            raise ValueError(f"an Objective has {len(LOSS_LEVELS)} TV weights (levels 6, 5, 4, 3, 2)")
+
+    def with_target_weights(self, prev_weights):
+        """The same objective with other weights on the targets after the first (e.g. PREV_WEIGHTS_TRUE_DIVISION)."""
+        return Objective(self.target_channels, (self.target_weights[0],) + tuple(float(v) for v in prev_weights), self.tv_weights)
+
+
+# main_flownetS_pyramid_noprevloss_dataloader.py: the ground-truth frame only (what loss_main / loss_main_fused compute)
+OBJECTIVE_NOPREV = Objective((0,), (1.0,), TV_WEIGHTS)
+_PREV_CHANNELS = (0, 3, 6, 9, 12, 15)                           # stab_image[..., 0:3] and the five earlier frames :203-241
+# main_flownetS_pyramid.py: TV / 2e7 on every level (:244-248), var4 computed (:246) but left out of the sum (:250) -> weight 0
+OBJECTIVE_PREV = Objective(_PREV_CHANNELS, (1.0,) + PREV_WEIGHTS_PY2_FLOOR_DIVISION, (1 / 2e7, 1 / 2e7, 0.0, 1 / 2e7, 1 / 2e7))
+# main_flownetS_pyramid_highTV_noBBloss.py: TV / 1e6 on levels 6, 5, (4), / 2e6 on levels 3, 2; var4 left out there too
+OBJECTIVE_PREV_HIGHTV = Objective(_PREV_CHANNELS, (1.0,) + PREV_WEIGHTS_PY2_FLOOR_DIVISION, (1 / 1e6, 1 / 1e6, 0.0, 1 / 2e6, 1 / 2e6))
+OBJECTIVES = {"noprev": OBJECTIVE_NOPREV, "prev": OBJECTIVE_PREV, "prev_hightv": OBJECTIVE_PREV_HIGHTV}
+
+
+def _targets(c_off, weights, Ct):
+    import ctypes as C
+    c_off, weights = [int(v) for v in c_off], [float(v) for v in weights]
+    T = len(c_off)
+    if not 1 <= T <= 8 or len(weights) != T:
+        raise ValueError("1..8 targets, one weight each")
+    if any(o < 0 or o + 3 > Ct for o in c_off):
+        raise ValueError(f"every target needs its 3 channels inside the {Ct} channels of the target tensor")
+    return T, (C.c_int32 * T)(*c_off), (C.c_float * T)(*weights), weights
+
+
+def _f32c(t, name):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[3] < 3:
+        raise ValueError(f"{name} must be a float32 CUDA tensor [B,H,W,Ct], Ct >= 3")
+    return t.contiguous()
+
+
+def lossterm_multi(predict_flow, targets, unstab_image, c_off, weights, tv_weight: float = 0.0, need_grad: bool = True):
+    """One level of main_flownetS_pyramid.py:203-250: sum_t weights[t] * lossterm(predict_flow, targets[..., c_off[t]:c_off[t]+3],
+    unstab_image) + tv_weight * TV in one kernel pair (`vstab_loss_level_multi`): the warp, the mask and the denominator are shared.
+    targets [B,H,W,Ct] is resized once, all channels.  Returns (loss [0-dim float64 CUDA tensor], d loss / d predict_flow [B,h,w,2]
+    or None, per-target lossterms [T] float64, unweighted)."""
+    pf = _f32(predict_flow, "predict_flow", 2)
+    B, h, w, _ = pf.shape
+    tg, unstab = _f32c(targets, "targets"), _f32(unstab_image, "unstab_image", 3)
+    Ct = tg.shape[3]
+    if tg.shape[0] != B or unstab.shape[:3] != tg.shape[:3]:
+        raise ValueError("targets / unstab_image must be [B,H,W,.] with the flow's batch size")
+    T, offs, wts, wlist = _targets(c_off, weights, Ct)
+    gt = resize_images(tg, (h, w))
+    un = resize_images(unstab, (h, w))
+    sums = torch.empty((T + 2) * B, dtype=torch.float64, device=pf.device)
+    grad = torch.empty_like(pf) if need_grad else None
+    with torch.cuda.device(pf.device):
+        _lib.check(_lib.lib().vstab_loss_level_multi(pf.data_ptr(), gt.data_ptr(), Ct, T, offs, wts, un.data_ptr(), B, h, w, sums.data_ptr(),
+                                                     float(tv_weight), grad.data_ptr() if need_grad else None, runtime.stream_ptr()))
+    s = sums.view(B, T + 2)
+    per = (s[:, :T] / s[:, T:T + 1]).mean(dim=0)
+    tvw32 = float(torch.tensor(float(tv_weight), dtype=torch.float32))            # as the kernel and vstab_loss_main_multi carry it
+    loss = (per * torch.tensor(list(wts), dtype=torch.float64, device=pf.device)).sum() + tvw32 * s[:, T + 1].sum()
+    return loss, grad, per
+
+
+def loss_main_multi(flows: Dict[str, torch.Tensor], stab_image, unstab_image, objective: Objective, grads: Dict[str, torch.Tensor] = None):
+    """loss_main of `objective` and (optionally) its flow gradients through ONE library call (`vstab_loss_main_multi`).  stab_image:
+    [B,H,W,Ct] (24 channels in the scripts; any Ct that holds the objective's targets); flows / grads as in loss_main_fused.
+    Returns (loss, per-target lossterms summed over the levels [T], unweighted), float64 CUDA tensors."""
+    import ctypes as C
+    stab, unstab = _f32c(stab_image, "stab_image"), _f32(unstab_image, "unstab_image", 3)
+    B, H, W, Ct = stab.shape
+    if unstab.shape[:3] != stab.shape[:3]:
+        raise ValueError("stab_image / unstab_image must have the same batch and frame size")
+    T, offs, wts, _w = _targets(objective.target_channels, objective.target_weights, Ct)
+    desc = (_lib.LossLevelDesc * len(LOSS_LEVELS))()
+    for d, name, tvw in zip(desc, LOSS_LEVELS, objective.tv_weights):
+        pf = flows[name]
+        if not pf.is_cuda or pf.dtype != torch.float32 or pf.dim() != 4 or pf.shape[0] != B or not pf.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor [B,h,w,C]")
+        d.pf, d.h, d.w, d.cs_pf, d.tv_weight = pf.data_ptr(), pf.shape[1], pf.shape[2], pf.shape[3], tvw
+        if grads is not None:
+            g = grads[name]
+            if g.shape[:3] != pf.shape[:3] or g.dtype != torch.float32 or not g.is_contiguous() or g.device != pf.device:
+                raise ValueError(f"grads[{name}] must be a contiguous float32 tensor [B,h,w,C'] beside the flow")
+            d.grad, d.cs_grad = g.data_ptr(), g.shape[3]
+    L = _lib.lib()
+    n = L.vstab_loss_main_multi_workspace_bytes(C.addressof(desc), len(LOSS_LEVELS), B, Ct, T)
+    if n == 0:
+        raise ValueError("loss_main_multi: the library rejects the level descriptors (1..8 levels, even channel counts >= 2, 8-byte aligned "
+                         "flow / gradient buffers, level sizes below 2^31 / 3 pixels)")
+    ws = torch.empty(n, dtype=torch.uint8, device=stab.device)
+    out = torch.empty(1 + T, dtype=torch.float64, device=stab.device)
+    with torch.cuda.device(stab.device):
+        _lib.check(L.vstab_loss_main_multi(C.addressof(desc), len(LOSS_LEVELS), stab.data_ptr(), Ct, T, offs, wts, unstab.data_ptr(), B, H, W,
+                                           out.data_ptr(), ws.data_ptr(), n, runtime.stream_ptr()))
+    return out[0], out[1:]
 
 
 # ----------------------------------------------------------------------------- backward building blocks

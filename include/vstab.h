@@ -455,6 +455,29 @@ VSTAB_API size_t vstab_loss_main_workspace_bytes(const vstab_loss_level_desc *le
 VSTAB_API int vstab_loss_main(const vstab_loss_level_desc *levels, int n_levels, const float *gtstab, const float *unstab, int B, int H,
                               int W, double *loss_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the full objective of main_flownetS_pyramid.py / main_flownetS_pyramid_highTV_noBBloss.py (:200-250) ----------------
+ * One level against T weighted targets, 1 <= T <= 8: the warped unstable frame is compared with the ground-truth stable frame AND
+ * with earlier stabilised frames, 3-channel slices c_off[t]..c_off[t]+2 of one tensor `targets` [B,h,w,Ct] (already resized, like
+ * unstab [B,h,w,3]); c_off / weights are HOST arrays of T entries.  The warp, the mask, sum safe(M) and TV are shared:
+ *   loss = sum_t weights[t] * mean_b(num_t / den) + scale_tv * sum_b TV
+ * sums: device double[(T+2)*B], overwritten with {num_0 .. num_{T-1}, den, TV} per sample.  grad_pf (may be NULL): [B,h,w,2]
+ * d loss / d pf, overwritten.  With T = 1, weights[0] = 1 both outputs are bit-equal to vstab_loss_level(scale_mse = 1).
+ * VSTAB_E_STATE for a NULL buffer or array; VSTAB_E_SHAPE for T outside 1..8, c_off[t] < 0 or c_off[t] + 3 > Ct, bad sizes;
+ * VSTAB_E_ALIGN when pf / grad_pf / sums are not 8-byte aligned. */
+VSTAB_API int vstab_loss_level_multi(const float *pf, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                                     const float *unstab, int B, int h, int w, double *sums, float scale_tv, float *grad_pf, void *stream);
+/* All levels of that objective in one call, the levels described as for vstab_loss_main: per level ONE resize of the full-size
+ * target tensor [B,H,W,Ct] (all Ct channels) and one of unstab [B,H,W,3], then the level above with its gradient written into
+ * channels 0..1 of the level's grad buffer.  loss_out: device double[1 + T] = the objective (sum over levels of
+ * sum_t weights[t] * mean_b(masked_MSE_t) + tv_weight * TV), then per target the unweighted sum over levels of mean_b(masked_MSE_t).
+ * One target of weight 1 is vstab_loss_main on that slice, launch for launch (only the target's three channels are resized): value
+ * and gradients are its bits.  The call allocates nothing; workspace as sized by vstab_loss_main_multi_workspace_bytes (0 for arguments the call would reject),
+ * VSTAB_E_NOMEM when too small.  Errors as above; odd channel strides in a descriptor are VSTAB_E_SHAPE. */
+VSTAB_API size_t vstab_loss_main_multi_workspace_bytes(const vstab_loss_level_desc *levels, int n_levels, int B, int Ct, int T);
+VSTAB_API int vstab_loss_main_multi(const vstab_loss_level_desc *levels, int n_levels, const float *targets, int Ct, int T, const int *c_off,
+                                    const float *weights, const float *unstab, int B, int H, int W, double *loss_out, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
 /* Weight and bias gradient of PadLayer(pad) -> Conv2d(k, stride, VALID) (model.py:807-844; what tf.gradients yields for
  * the filter of tf.nn.conv2d): dW[ky,kx,ci,co] = sum_{n,oy,ox} x[n, s*oy+ky-pad, s*ox+kx-pad, ci] * gout[n,oy,ox,co] in the
  * reference's HWIO layout, db[co] = sum gout (db may be NULL).  x: [B,Hi,Wi,cs_x] using channels cx_off..cx_off+cin;
