@@ -535,6 +535,19 @@ hipError_t launch_loss_main_multi(const LossLevel *lv, int n, const float *targe
                                   const float *unstab, int B, int H, int W, double *loss_out, void *workspace, hipStream_t stream);
 hipError_t launch_flow_medfilt(const float *flow, int B, int h, int w, int kh, int kw, int kc, float *out, hipStream_t stream);
 
+// SSIM structure term, its gradient and the 2x2 SAME average pool (ssim_ops.hip; utils.py:74-166).  win: the 1-D vector whose outer
+// product with itself is the window (ssim_api.cpp); size 1..SSIM_MAX_SIZE.  partial: ssim_tiles_per_sample(oh, ow) * B floats (needed
+// with means); fields: 5 * B*oh*ow floats.
+constexpr int SSIM_MAX_SIZE = 11;
+struct SsimWindow { float w[SSIM_MAX_SIZE]; };
+size_t ssim_tiles_per_sample(int oh, int ow);
+hipError_t launch_ssim_forward(const float *img1, const float *img2, int B, int H, int W, int size, const SsimWindow &win, float *map,
+                               float *means, float *partial, hipStream_t stream);
+hipError_t launch_ssim_backward(const float *img1, const float *img2, int B, int H, int W, int size, const SsimWindow &win, const float *dmap,
+                                const float *dmeans, float *d_img1, float *d_img2, float *fields, hipStream_t stream);
+hipError_t launch_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, hipStream_t stream);
+hipError_t launch_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, hipStream_t stream);
+
 // dense-flow homography fit + cv2.warpPerspective on 8-bit frames (homography_ops.hip)
 int homography_moment_blocks(int H, int W);
 size_t homography_workspace_bytes(int B, int H, int W, int K);

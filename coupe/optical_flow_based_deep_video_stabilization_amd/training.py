@@ -3,7 +3,7 @@
 terms and `loss_main` (main:213-275) with their gradient with respect to every predicted flow; filter / input gradients
 of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and its backward; the resamplers' adjoints; the
 gradients of the bilinear spatial transformers (`st_transform_backward`, `st_symmetry_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`)
-and of warp.py's homography warp and matrix exponential (`homography_warp_backward`, `vec2mtrx_backward`).
+and of warp.py's homography warp and matrix exponential (`homography_warp_backward`, `vec2mtrx_backward`), and of utils.py's SSIM (`ssim_backward`).
 `train_step.Trainer` strings them into the whole step (forward, loss, backward, Adam: main:184-185, 333-335).
 The objective of the reference's other two training scripts -- the same terms plus five weighted comparisons with earlier stabilised
 frames -- is `Objective` / `lossterm_multi` / `loss_main_multi` (main_flownetS_pyramid.py:200-250).
@@ -653,3 +653,36 @@ def conv3x3_winograd_wgrad(x, gout, cx_off: int = 0, cin: int = None, cg_off: in
         _lib.check(L.vstab_conv3x3_winograd_wgrad(x.data_ptr(), B, H, W, cs_x, cx_off, cin, gout.data_ptr(), cs_g, cg_off, cout,
                                                   dW.data_ptr(), ws.data_ptr(), n, runtime.stream_ptr()))
     return dW
+
+
+def ssim_backward(img1, img2, dout, size: int = 9, sigma: float = 0.5, need_img1: bool = True, need_img2: bool = True):
+    """Gradients of utils.tf_ssim's value s (utils.py:111; l**0 and c**0 are constants) with respect to both images [B,H,W,1]: (d img1
+    or None, d img2 or None).  dout is the gradient of the map, [B,H-size+1,W-size+1,1], or -- one dimension, [B] -- that of the
+    per-sample means, broadcast over the sample's map inside the kernel.  need_img1 / need_img2 False skips that image.  Gathered
+    through the flipped window without atomics: bit-reproducible, and what utils' autograd functions call."""
+    for t, name in ((img1, "img1"), (img2, "img2")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[3] != 1:
+            raise ValueError(f"{name} must be a float32 CUDA tensor [B,H,W,1]")
+    if img1.shape != img2.shape or img1.device != img2.device:
+        raise ValueError("img1 and img2 must have the same shape and device")
+    if not need_img1 and not need_img2:
+        return None, None
+    a, b, size = img1.contiguous(), img2.contiguous(), int(size)
+    B, H, W, _ = a.shape
+    L = _lib.lib()
+    n = int(L.vstab_ssim_backward_workspace_bytes(B, H, W, size))
+    if n == 0:
+        raise ValueError(f"ssim_backward: need B >= 1, 1 <= size <= 11 and images of at least size x size, got {B}x{H}x{W}, size {size}")
+    per_sample = torch.is_tensor(dout) and dout.dim() == 1
+    want = B if per_sample else B * (H - size + 1) * (W - size + 1)
+    if not torch.is_tensor(dout) or dout.device != a.device or dout.dtype != torch.float32 or dout.numel() != want:
+        raise ValueError(f"dout must be a float32 tensor of {want} elements beside the images")
+    dout = dout.contiguous()
+    d1 = torch.empty_like(a) if need_img1 else None
+    d2 = torch.empty_like(a) if need_img2 else None
+    ws = torch.empty(n, dtype=torch.uint8, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(L.vstab_ssim_backward(a.data_ptr(), b.data_ptr(), B, H, W, size, float(sigma), None if per_sample else dout.data_ptr(),
+                                         dout.data_ptr() if per_sample else None, d1.data_ptr() if need_img1 else None,
+                                         d2.data_ptr() if need_img2 else None, ws.data_ptr(), n, runtime.stream_ptr()))
+    return d1, d2

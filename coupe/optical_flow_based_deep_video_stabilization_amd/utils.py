@@ -1,0 +1,205 @@
+"""Drop-ins for the image-similarity measures of the reference's `utils.py`: `_tf_fspecial_gauss` (:74-89), `tf_ssim` (:91-124) and
+`tf_ms_ssim` (:126-166), as metrics and as differentiable loss terms.  Images are float32 CUDA tensors [B,H,W,1]; the arithmetic runs
+in HIP kernels (csrc/ssim_ops.hip, C ABI in include/vstab.h) and there is no CPU path.
+
+What the reference computes is not the textbook SSIM: the luminance and contrast terms enter as `l**0` and `c**0` (:113), so the value
+is the squared structure term  s = (s12^2 + C3) / (s1 s2 + C3),  C3 = 0.03^2 / 2  (:111) over VALID windows of
+`_tf_fspecial_gauss(size, sigma)`, whose default sigma of 0.5 leaves all but about 1e-3 of the weight in the central 3x3.  One
+channel only: the reference's conv2d with a [k,k,1,1] window takes nothing else.  The kernels apply the window in its separable
+form (it is an outer product), so results differ from a 2-D correlation in the last bits.
+
+Two things are kept or changed on purpose:
+  * `tf_ms_ssim` keeps the reference's reduction as written (:162): `reduce_prod` has no axis, so the [batch_size] result holds the
+    SAME number in every entry, the product of all level x batch_size per-sample means (times `ml[level-1]`, which is 1).
+  * Gradients (torch.autograd, with respect to both images) treat `l**0` and `c**0` as the constant 1.  TensorFlow's gradient of
+    pow(c, 0) is 0 * c^-1, which is NaN wherever a window is flat (sqrt(0)) or fp32 cancellation leaves a variance slightly
+    negative; here the gradient is that of s alone and is finite there.
+The autograd path is taken only when gradients are enabled and an image requires grad.  Values and gradients are summed without
+atomics in a fixed order: two runs give the same bits."""
+from __future__ import annotations
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib, runtime
+
+_MAX_SIZE = 11
+
+
+def _tf_fspecial_gauss(size, sigma):
+    """The normalised Gaussian window [size,size,1,1] (float32, host) of utils.py:74-89: offsets -size//2+1 .. size//2 with floor
+    division, so size 9 covers -4..4 and size 8 covers -3..4."""
+    size = int(size)
+    if size < 1:
+        raise ValueError("size must be >= 1")
+    c = torch.arange(-size // 2 + 1, size // 2 + 1, dtype=torch.float32)
+    xx, yy = c.reshape(size, 1), c.reshape(1, size)
+    g = torch.exp(-((xx ** 2 + yy ** 2) / (2.0 * float(sigma) ** 2)))
+    return (g / g.sum()).reshape(size, size, 1, 1)
+
+
+def _image(t, name):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
+        raise ValueError(f"{name} must be a float32 CUDA tensor [B,H,W,1]")
+    if t.shape[3] != 1:
+        raise ValueError(f"{name} has {t.shape[3]} channels: the reference's [k,k,1,1] window takes one channel only")
+    return t.contiguous()
+
+
+def _pair(img1, img2, size, sigma):
+    a, b = _image(img1, "img1"), _image(img2, "img2")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("img1 and img2 must have the same shape and device")
+    size = int(size)
+    if not 1 <= size <= _MAX_SIZE:
+        raise ValueError(f"size must be 1..{_MAX_SIZE}")
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+    if a.shape[0] < 1 or a.shape[1] < size or a.shape[2] < size:
+        raise ValueError(f"images of {a.shape[1]}x{a.shape[2]} are smaller than the {size}x{size} window")
+    return a, b, size, float(sigma)
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def _ssim_call(a, b, size, sigma, want_map, want_means):
+    B, H, W, _ = a.shape
+    L = _lib.lib()
+    smap = torch.empty((B, H - size + 1, W - size + 1, 1), dtype=torch.float32, device=a.device) if want_map else None
+    means, ws, n = None, None, 0
+    if want_means:
+        means = torch.empty((B,), dtype=torch.float32, device=a.device)
+        n = int(L.vstab_ssim_forward_workspace_bytes(B, H, W, size))
+        ws = torch.empty(max(n, 4), dtype=torch.uint8, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(L.vstab_ssim_forward(a.data_ptr(), b.data_ptr(), B, H, W, size, sigma, smap.data_ptr() if want_map else None,
+                                        means.data_ptr() if want_means else None, ws.data_ptr() if want_means else None, n,
+                                        runtime.stream_ptr()))
+    return smap, means
+
+
+class _SsimMapFn(torch.autograd.Function):
+    """s map [B,oh,ow,1] with its HIP backward (training.ssim_backward)."""
+
+    @staticmethod
+    def forward(ctx, a, b, size, sigma):
+        ctx.save_for_backward(a, b)
+        ctx.size, ctx.sigma = size, sigma
+        return _ssim_call(a, b, size, sigma, True, False)[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        a, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d1, d2 = training.ssim_backward(a, b, dout, ctx.size, ctx.sigma, need_img1=need[0], need_img2=need[1])
+        return d1, d2, None, None
+
+
+class _SsimMeansFn(torch.autograd.Function):
+    """per-sample means [B] of the s map (no map is stored) with the same backward; the upstream scalar of a sample is broadcast
+    inside the kernel."""
+
+    @staticmethod
+    def forward(ctx, a, b, size, sigma):
+        ctx.save_for_backward(a, b)
+        ctx.size, ctx.sigma = size, sigma
+        return _ssim_call(a, b, size, sigma, False, True)[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dmeans):
+        from . import training
+        a, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d1, d2 = training.ssim_backward(a, b, dmeans.reshape(-1), ctx.size, ctx.sigma, need_img1=need[0], need_img2=need[1])
+        return d1, d2, None, None
+
+
+def _ssim_map(a, b, size, sigma):
+    if _wants_grad(a, b):
+        return _SsimMapFn.apply(a, b, size, sigma)
+    return _ssim_call(a, b, size, sigma, True, False)[0]
+
+
+def _ssim_means(a, b, size, sigma):
+    if _wants_grad(a, b):
+        return _SsimMeansFn.apply(a, b, size, sigma)
+    return _ssim_call(a, b, size, sigma, False, True)[1]
+
+
+def _avg_pool_call(x):
+    B, H, W, C = x.shape
+    out = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().vstab_avgpool2x2_same(x.data_ptr(), B, H, W, C, out.data_ptr(), runtime.stream_ptr()))
+    return out
+
+
+class _AvgPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.in_shape = tuple(x.shape)
+        return _avg_pool_call(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        B, H, W, C = ctx.in_shape
+        dout = dout.contiguous()
+        dx = torch.empty(ctx.in_shape, dtype=torch.float32, device=dout.device)
+        with torch.cuda.device(dout.device):
+            _lib.check(_lib.lib().vstab_avgpool2x2_same_backward(dout.data_ptr(), B, H, W, C, dx.data_ptr(), runtime.stream_ptr()))
+        return dx
+
+
+def avg_pool_2x2_same(x):
+    """tf.nn.avg_pool(x, [1,2,2,1], [1,2,2,1], padding='SAME') on a float32 CUDA tensor [B,H,W,C] (utils.py:146-147): the output is
+    [B,ceil(H/2),ceil(W/2),C] and a window that hangs over the edge averages the pixels that exist.  Differentiable."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        raise ValueError("x must be a float32 CUDA tensor [B,H,W,C]")
+    x = x.contiguous()
+    return _AvgPoolFn.apply(x) if _wants_grad(x) else _avg_pool_call(x)
+
+
+def tf_ssim(img1, img2, mean_metric=True, cs_map=False, size=9, sigma=0.5):
+    """utils.py:91-124 on float32 CUDA images [B,H,W,1]: s = (s12^2 + C3) / (s1 s2 + C3) over VALID size x size Gaussian windows, a
+    map [B,H-size+1,W-size+1,1].  cs_map=True returns the pair (l**0, c**0 * s) = (ones, s) (:113); mean_metric takes the mean over
+    all elements (of each member of the pair).  The mean forms store no map.  Differentiable with respect to both images, with
+    l**0 and c**0 as constants (module docstring).  size 1..11."""
+    a, b, size, sigma = _pair(img1, img2, size, sigma)
+    if mean_metric:
+        value = _ssim_means(a, b, size, sigma).mean()
+        return (torch.ones_like(value), value) if cs_map else value
+    smap = _ssim_map(a, b, size, sigma)
+    return (torch.ones_like(smap), smap) if cs_map else smap
+
+
+def tf_ms_ssim(img1, img2, batch_size, mean_metric=True, level=5):
+    """utils.py:126-166: per level the per-sample mean of tf_ssim's cs map (size 9, sigma 0.5), then both images halved by the 2x2
+    SAME average pool; all level weights are 1.  The reduction is the reference's as written (:162): `reduce_prod` has no axis, so
+    the result is a [batch_size] vector whose EVERY entry is the product of all level x batch_size per-sample means (times
+    ml[level-1] = 1) -- the samples are not scored separately.  mean_metric takes the mean of that vector, i.e. the same number.
+    batch_size must be the images' B; every level's image must hold a 9x9 window (5 levels: H, W >= 129).  Differentiable; the
+    gradients of all levels accumulate into the full-size images through the pool's adjoint."""
+    a, b, size, sigma = _pair(img1, img2, 9, 0.5)
+    level = int(level)
+    if level < 1:
+        raise ValueError("level must be >= 1")
+    if int(batch_size) != a.shape[0]:
+        raise ValueError(f"batch_size {batch_size} is not the images' batch {a.shape[0]}")
+    h, w = a.shape[1], a.shape[2]
+    for lv in range(level):
+        if h < size or w < size:
+            raise ValueError(f"level {lv} would be {h}x{w}, smaller than the {size}x{size} window")
+        h, w = (h + 1) // 2, (w + 1) // 2
+    mcs = []
+    for lv in range(level):
+        mcs.append(_ssim_means(a, b, size, sigma))
+        if lv + 1 < level:                       # the reference also pools after the last level; nothing reads that result
+            a, b = avg_pool_2x2_same(a), avg_pool_2x2_same(b)
+    value = torch.prod(torch.stack(mcs, dim=0)).expand(int(batch_size))
+    return value.mean() if mean_metric else value

@@ -478,6 +478,35 @@ VSTAB_API int vstab_loss_main_multi(const vstab_loss_level_desc *levels, int n_l
                                     const float *weights, const float *unstab, int B, int H, int W, double *loss_out, void *workspace,
                                     size_t workspace_bytes, void *stream);
 
+/* ---- image similarity: tf_ssim / tf_ms_ssim of the reference's utils.py (:74-166) --------------------------------------------
+ * img1, img2: [B,H,W] (one channel).  With the size x size window of _tf_fspecial_gauss(size, sigma) (:74-89; offsets
+ * -size//2+1 .. size//2 with floor division, so an even size is not symmetric; applied in its separable form) and five VALID
+ * correlations,
+ *   mu1 = w*x, mu2 = w*y, s1 = w*x^2 - mu1^2, s2 = w*y^2 - mu2^2, s12 = w*xy - mu1 mu2,
+ *   s = (s12^2 + C3) / (s1 s2 + C3),  C3 = 0.03^2 / 2        (:111; the factors l**0 and c**0 of :113 are the constant 1)
+ * on oh x ow = (H-size+1) x (W-size+1) positions.  map (may be NULL): [B,oh,ow] receives s; means (may be NULL): [B] receives the
+ * per-sample mean of s, summed without atomics in a fixed order (two calls give the same bits); at least one of the two.
+ * workspace: vstab_ssim_forward_workspace_bytes() bytes, 4-byte aligned, needed only with means (VSTAB_E_NOMEM when too small).
+ * VSTAB_E_STATE for a NULL image, both outputs NULL, or means without a workspace (checked first); VSTAB_E_SHAPE unless B >= 1
+ * (<= 65535), 1 <= size <= 11, H, W >= size, sigma > 0 and B*H*W < 2^31; the workspace query returns 0 for such arguments. */
+VSTAB_API size_t vstab_ssim_forward_workspace_bytes(int B, int H, int W, int size);
+VSTAB_API int vstab_ssim_forward(const float *img1, const float *img2, int B, int H, int W, int size, float sigma, float *map, float *means,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+/* Gradient of the above with respect to both images for the upstream gradient dmap [B,oh,ow] of the map and / or dmeans [B] of the
+ * per-sample means (either may be NULL, not both; both given add up): d_img1, d_img2 [B,H,W], overwritten; a NULL output skips
+ * that image (both NULL is VSTAB_E_SHAPE).  l**0 and c**0 carry no gradient (TensorFlow's 0 * c^-1 is NaN on a flat window):
+ *   ds/ds12 = 2 s12 / D, ds/ds1 = -N s2 / D^2, ds/ds2 = -N s1 / D^2 with N, D the numerator and denominator of s,
+ * taken back through the adjoint of the VALID correlation (the flipped window) by gathering -- no atomics, bit-reproducible.
+ * workspace: vstab_ssim_backward_workspace_bytes() bytes (five [B,oh,ow] planes), 4-byte aligned; other errors as the forward's. */
+VSTAB_API size_t vstab_ssim_backward_workspace_bytes(int B, int H, int W, int size);
+VSTAB_API int vstab_ssim_backward(const float *img1, const float *img2, int B, int H, int W, int size, float sigma, const float *dmap,
+                                  const float *dmeans, float *d_img1, float *d_img2, void *workspace, size_t workspace_bytes, void *stream);
+/* tf.nn.avg_pool(x, [1,2,2,1], [1,2,2,1], 'SAME') (utils.py:146-147): x [B,H,W,C] -> out [B,ceil(H/2),ceil(W/2),C]; a window that
+ * hangs over the edge averages the pixels that exist.  The backward takes dout of the pooled size and writes dx [B,H,W,C] (H, W: the
+ * INPUT size).  VSTAB_E_STATE for a NULL buffer; VSTAB_E_SHAPE for a dimension < 1 or B*H*W*C >= 2^31. */
+VSTAB_API int vstab_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, void *stream);
+VSTAB_API int vstab_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, void *stream);
+
 /* Weight and bias gradient of PadLayer(pad) -> Conv2d(k, stride, VALID) (model.py:807-844; what tf.gradients yields for
  * the filter of tf.nn.conv2d): dW[ky,kx,ci,co] = sum_{n,oy,ox} x[n, s*oy+ky-pad, s*ox+kx-pad, ci] * gout[n,oy,ox,co] in the
  * reference's HWIO layout, db[co] = sum gout (db may be NULL).  x: [B,Hi,Wi,cs_x] using channels cx_off..cx_off+cin;
