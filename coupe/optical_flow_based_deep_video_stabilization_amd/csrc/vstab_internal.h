@@ -548,6 +548,22 @@ hipError_t launch_ssim_backward(const float *img1, const float *img2, int B, int
 hipError_t launch_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, hipStream_t stream);
 hipError_t launch_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, hipStream_t stream);
 
+// What follows the convolution in a ConvLSTMCell / ConvGRUCell step (cell_ops.hip; cell.py:5-136).  y: the convolution's output
+// [B, HW, ys]; states [B, HW*F] contiguous or slices of a wider NHWC buffer (pointer to the first channel of pixel 0 + pixel stride);
+// act 0 tanh, 1 relu, 2 identity.  A workgroup reduces CELL_CHUNK elements of one sample; workspace sizes are 0 without normalize.
+constexpr int CELL_CHUNK = 2048;
+int cell_chunks(int N);
+size_t convlstm_workspace_bytes(int B, int HW, int F, bool normalize);
+size_t convgru_workspace_bytes(int B, int HW, int F, bool normalize);
+hipError_t launch_convlstm_gates(const float *y, int ys, const float *c, const float *wci, const float *wcf, const float *wco, const float *gamma,
+                                 const float *beta, int B, int HW, int F, float forget_bias, int act, bool normalize, bool peephole, float *c_out,
+                                 float *h_out, float *h_cat, int cs_cat, void *workspace, hipStream_t stream);
+hipError_t launch_convgru_gates(const float *y, int ys, const float *h, int hs, const float *gamma, const float *beta, int B, int HW, int F,
+                                bool normalize, float *rh, int rhs, float *u, void *workspace, hipStream_t stream);
+hipError_t launch_convgru_update(const float *y2, int ys, const float *h, int hs, const float *u, const float *gamma, const float *beta, int B,
+                                 int HW, int F, int act, bool normalize, float *h_out, float *h_new, int hns, void *workspace,
+                                 hipStream_t stream);
+
 // dense-flow homography fit + cv2.warpPerspective on 8-bit frames (homography_ops.hip)
 int homography_moment_blocks(int H, int W);
 size_t homography_workspace_bytes(int B, int H, int W, int K);

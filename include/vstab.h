@@ -507,6 +507,37 @@ VSTAB_API int vstab_ssim_backward(const float *img1, const float *img2, int B, i
 VSTAB_API int vstab_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, void *stream);
 VSTAB_API int vstab_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, void *stream);
 
+/* The recurrent cells of cell.py (ConvLSTMCell :5-76, ConvGRUCell :78-136), forward only: what follows each cell's SAME convolution
+ * over concat([x, h]) -- that convolution is vstab_conv_forward on the caller's concat buffer.  y: the convolution's output
+ * [B,H,W,ys] (ys >= the gate channels; rows may be padded); states [B,H,W,F] contiguous, or slices of a wider NHWC buffer given as
+ * the address of the slice's first channel in pixel 0 plus the buffer's channel stride.  act: 0 tanh, 1 relu, 2 identity.
+ * Layer norm = tf.contrib.layers.layer_norm's defaults: per sample, mean and biased variance over all H*W*F numbers of a gate,
+ * (v - mean) * rsqrt(var + 1e-12) * gamma[ch] + beta[ch].  Statistics are per-workgroup moments about the workgroup's own mean,
+ * combined in double in a fixed order: no atomics, two runs give the same bits.
+ * VSTAB_E_STATE for a NULL buffer that the flags require; VSTAB_E_SHAPE for a dimension < 1, a stride below its channels, B > 65535,
+ * act outside 0..2 or a tensor of 2^31 elements or more; with normalize: VSTAB_E_ALIGN unless the workspace is 16-byte aligned,
+ * VSTAB_E_NOMEM when it is smaller than the *_workspace_bytes() value (0 without normalize: workspace may then be NULL).
+ *
+ * LSTM: j, i, f, o = y[..., 0:F], [F:2F], [2F:3F], [3F:4F];  peephole: i += w_ci c, f += w_cf c (w_*: [H,W,F]);  normalize: j, i, f =
+ * LN;  c' = c sigmoid(f + forget_bias) + sigmoid(i) act(j);  peephole: o += w_co c';  normalize: o, c' = LN;  h' = sigmoid(o) act(c').
+ * gamma, beta: [5][F] in the order j, i, f, o, c.  c_out (may be c), h_out: [B,H,W,F]; h_cat (may be NULL): h' also goes to this slice.
+ * Launches: 5 with normalize (moments, statistics, gates + moments, statistics, output), 1 without. */
+VSTAB_API size_t vstab_convlstm_gates_workspace_bytes(int B, int H, int W, int F, int normalize);
+VSTAB_API int vstab_convlstm_gates(const float *y, int ys, const float *c, const float *w_ci, const float *w_cf, const float *w_co,
+                                   const float *gamma, const float *beta, int B, int H, int W, int F, float forget_bias, int act, int normalize,
+                                   int peephole, float *c_out, float *h_out, float *h_cat, int cs_cat, void *workspace, size_t workspace_bytes,
+                                   void *stream);
+/* GRU, first half: r, u = sigmoid(LN or identity of y[..., 0:F], [F:2F]) (without normalize the convolution has added gates/bias);
+ * rh slice <- r * h, u [B,H,W,F] <- u.  h, hs: the old state as a slice; gamma, beta: [2][F] (r, u).
+ * Second half: h' = u h + (1 - u) act(LN or identity of y2[..., 0:F]); h_out [B,H,W,F]; h_new (may be NULL, may be h): h' as a slice.
+ * gamma, beta: [F].  One workspace of vstab_convgru_workspace_bytes() serves both calls. */
+VSTAB_API size_t vstab_convgru_workspace_bytes(int B, int H, int W, int F, int normalize);
+VSTAB_API int vstab_convgru_gates(const float *y, int ys, const float *h, int hs, const float *gamma, const float *beta, int B, int H, int W,
+                                  int F, int normalize, float *rh, int rhs, float *u, void *workspace, size_t workspace_bytes, void *stream);
+VSTAB_API int vstab_convgru_update(const float *y2, int ys, const float *h, int hs, const float *u, const float *gamma, const float *beta, int B,
+                                   int H, int W, int F, int act, int normalize, float *h_out, float *h_new, int hns, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
 /* Weight and bias gradient of PadLayer(pad) -> Conv2d(k, stride, VALID) (model.py:807-844; what tf.gradients yields for
  * the filter of tf.nn.conv2d): dW[ky,kx,ci,co] = sum_{n,oy,ox} x[n, s*oy+ky-pad, s*ox+kx-pad, ci] * gout[n,oy,ox,co] in the
  * reference's HWIO layout, db[co] = sum gout (db may be NULL).  x: [B,Hi,Wi,cs_x] using channels cx_off..cx_off+cin;
