@@ -1,5 +1,5 @@
 // C ABI of libvstab_hip.so (include/vstab.h): context, errors, roctx ranges and the thin wrappers around single launches (glue, warps,
-// samplers, clip-driver pieces, post-filters, losses).  The FlowNetS pyramid lives in flownet_plan.cpp / flownet_forward.cpp, the
+// samplers, clip-driver pieces, post-filters).  The FlowNetS pyramid lives in flownet_plan.cpp / flownet_forward.cpp, the
 // VGG16 trunk in vgg_api.cpp, the NLDF head in nldf_api.cpp, the training blocks in train_api.cpp.
 #include <cmath>
 #include <cstdlib>
@@ -732,115 +732,6 @@ extern "C" int vstab_axpby(const float *x, float a, const float *y, float b, flo
 {
     if (!x || !y || !out || n < 1) return fail(nullptr, VSTAB_E_STATE, "axpby: bad argument");
     HIP_TRY(nullptr, launch_axpby(x, a, y, b, out, n, (hipStream_t)stream));
-    return VSTAB_OK;
-}
-
-extern "C" int vstab_loss_level(const float *pf, const float *gt, const float *unstab, int B, int h, int w, double *sums,
-                                float scale_mse, float scale_tv, float *grad_pf, void *stream)
-{
-    if (!pf || !gt || !unstab || !sums) return fail(nullptr, VSTAB_E_STATE, "loss_level: NULL buffer");
-    if (B < 1 || h < 1 || w < 1 || (long long)h * w > (1LL << 30)) return fail(nullptr, VSTAB_E_SHAPE, "loss_level: bad shape");
-    if ((reinterpret_cast<uintptr_t>(pf) & 7) || (grad_pf && (reinterpret_cast<uintptr_t>(grad_pf) & 7)) ||
-        (reinterpret_cast<uintptr_t>(sums) & 7))
-        return fail(nullptr, VSTAB_E_ALIGN, "loss_level: flow / gradient / sums must be 8-byte aligned");
-    HIP_TRY(nullptr, launch_loss_level(pf, gt, unstab, B, h, w, sums, scale_mse, scale_tv, grad_pf, (hipStream_t)stream));
-    return VSTAB_OK;
-}
-
-static int loss_main_check(const vstab_loss_level_desc *lv, int n, int B)
-{
-    if (!lv || n < 1 || n > 8 || B < 1) return VSTAB_E_SHAPE;
-    for (int l = 0; l < n; ++l) {
-        if (!lv[l].pf || lv[l].h < 1 || lv[l].w < 1 || lv[l].cs_pf < 2 || (lv[l].cs_pf & 1)) return VSTAB_E_SHAPE;
-        if (lv[l].grad && (lv[l].cs_grad < 2 || (lv[l].cs_grad & 1))) return VSTAB_E_SHAPE;
-        if (((uintptr_t)lv[l].pf | (uintptr_t)lv[l].grad) & 7) return VSTAB_E_ALIGN;
-    }
-    return VSTAB_OK;
-}
-
-extern "C" size_t vstab_loss_main_workspace_bytes(const vstab_loss_level_desc *levels, int n_levels, int B)
-{
-    if (loss_main_check(levels, n_levels, B) != VSTAB_OK) return 0;
-    static_assert(sizeof(vstab_loss_level_desc) == sizeof(LossLevel), "descriptor layout");
-    return loss_main_workspace_bytes(B, reinterpret_cast<const LossLevel *>(levels), n_levels);
-}
-
-extern "C" int vstab_loss_main(const vstab_loss_level_desc *levels, int n_levels, const float *gtstab, const float *unstab, int B, int H,
-                               int W, double *loss_out, void *workspace, size_t workspace_bytes, void *stream)
-{
-    const int c = loss_main_check(levels, n_levels, B);
-    if (c != VSTAB_OK) return fail(nullptr, c, "loss_main: bad level descriptor (1..8 levels, even channel strides >= 2, 8-byte aligned buffers)");
-    if (!gtstab || !unstab || !loss_out || !workspace) return fail(nullptr, VSTAB_E_STATE, "loss_main: NULL buffer");
-    if (H < 1 || W < 1) return fail(nullptr, VSTAB_E_SHAPE, "loss_main: bad image shape");
-    if (((uintptr_t)loss_out | (uintptr_t)workspace) & 7) return fail(nullptr, VSTAB_E_ALIGN, "loss_main: loss_out / workspace must be 8-byte aligned");
-    const LossLevel *lv = reinterpret_cast<const LossLevel *>(levels);
-    if (workspace_bytes < loss_main_workspace_bytes(B, lv, n_levels)) return fail(nullptr, VSTAB_E_NOMEM, "loss_main: workspace too small");
-    void *ws = (void *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    HIP_TRY(nullptr, launch_loss_main(lv, n_levels, gtstab, unstab, B, H, W, loss_out, ws, (hipStream_t)stream));
-    return VSTAB_OK;
-}
-
-// targets of the multi-target objective: 1..LOSS_MAX_TARGETS slices of 3 channels inside Ct
-static int loss_targets_check(int Ct, int T, const int *c_off, const float *weights)
-{
-    if (!c_off || !weights) return VSTAB_E_STATE;
-    if (T < 1 || T > LOSS_MAX_TARGETS || Ct < 3) return VSTAB_E_SHAPE;
-    for (int t = 0; t < T; ++t)
-        if (c_off[t] < 0 || c_off[t] > Ct - 3) return VSTAB_E_SHAPE;
-    return VSTAB_OK;
-}
-
-extern "C" int vstab_loss_level_multi(const float *pf, const float *targets, int Ct, int T, const int *c_off, const float *weights,
-                                      const float *unstab, int B, int h, int w, double *sums, float scale_tv, float *grad_pf, void *stream)
-{
-    if (!pf || !targets || !unstab || !sums) return fail(nullptr, VSTAB_E_STATE, "loss_level_multi: NULL buffer");
-    const int c = loss_targets_check(Ct, T, c_off, weights);
-    if (c == VSTAB_E_STATE) return fail(nullptr, c, "loss_level_multi: NULL c_off / weights");
-    if (c != VSTAB_OK) return fail(nullptr, c, "loss_level_multi: 1..%d targets of 3 channels inside Ct, c_off[t] + 3 <= Ct", LOSS_MAX_TARGETS);
-    if (B < 1 || h < 1 || w < 1 || (long long)h * w * 3 >= (1LL << 31) || B > 65535) return fail(nullptr, VSTAB_E_SHAPE, "loss_level_multi: bad shape");
-    if ((reinterpret_cast<uintptr_t>(pf) & 7) || (grad_pf && (reinterpret_cast<uintptr_t>(grad_pf) & 7)) ||
-        (reinterpret_cast<uintptr_t>(sums) & 7))
-        return fail(nullptr, VSTAB_E_ALIGN, "loss_level_multi: flow / gradient / sums must be 8-byte aligned");
-    HIP_TRY(nullptr, launch_loss_level_multi(pf, targets, Ct, T, c_off, weights, unstab, B, h, w, sums, scale_tv, grad_pf, (hipStream_t)stream));
-    return VSTAB_OK;
-}
-
-static int loss_main_multi_check(const vstab_loss_level_desc *lv, int n, int B, int Ct, int T)
-{
-    const int c = loss_main_check(lv, n, B);
-    if (c != VSTAB_OK) return c;
-    if (T < 1 || T > LOSS_MAX_TARGETS || Ct < 3 || B > 65535) return VSTAB_E_SHAPE;
-    for (int l = 0; l < n; ++l)
-        if ((long long)lv[l].h * lv[l].w * 3 >= (1LL << 31)) return VSTAB_E_SHAPE;
-    return VSTAB_OK;
-}
-
-extern "C" size_t vstab_loss_main_multi_workspace_bytes(const vstab_loss_level_desc *levels, int n_levels, int B, int Ct, int T)
-{
-    if (loss_main_multi_check(levels, n_levels, B, Ct, T) != VSTAB_OK) return 0;
-    return loss_main_multi_workspace_bytes(B, reinterpret_cast<const LossLevel *>(levels), n_levels, Ct, T);
-}
-
-extern "C" int vstab_loss_main_multi(const vstab_loss_level_desc *levels, int n_levels, const float *targets, int Ct, int T, const int *c_off,
-                                     const float *weights, const float *unstab, int B, int H, int W, double *loss_out, void *workspace,
-                                     size_t workspace_bytes, void *stream)
-{
-    int c = loss_main_multi_check(levels, n_levels, B, Ct, T);
-    if (c != VSTAB_OK)
-        return fail(nullptr, c, "loss_main_multi: bad level descriptor or target count (1..8 levels, even channel strides >= 2, 8-byte aligned "
-                                "buffers, 1..%d targets, Ct >= 3)", LOSS_MAX_TARGETS);
-    if (!targets || !unstab || !loss_out || !workspace) return fail(nullptr, VSTAB_E_STATE, "loss_main_multi: NULL buffer");
-    c = loss_targets_check(Ct, T, c_off, weights);
-    if (c == VSTAB_E_STATE) return fail(nullptr, c, "loss_main_multi: NULL c_off / weights");
-    if (c != VSTAB_OK) return fail(nullptr, c, "loss_main_multi: every target needs 0 <= c_off[t] and c_off[t] + 3 <= Ct");
-    if (H < 1 || W < 1) return fail(nullptr, VSTAB_E_SHAPE, "loss_main_multi: bad image shape");
-    if (((uintptr_t)loss_out | (uintptr_t)workspace) & 7)
-        return fail(nullptr, VSTAB_E_ALIGN, "loss_main_multi: loss_out / workspace must be 8-byte aligned");
-    const LossLevel *lv = reinterpret_cast<const LossLevel *>(levels);
-    if (workspace_bytes < loss_main_multi_workspace_bytes(B, lv, n_levels, Ct, T))
-        return fail(nullptr, VSTAB_E_NOMEM, "loss_main_multi: workspace too small");
-    void *ws = (void *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    HIP_TRY(nullptr, launch_loss_main_multi(lv, n_levels, targets, Ct, T, c_off, weights, unstab, B, H, W, loss_out, ws, (hipStream_t)stream));
     return VSTAB_OK;
 }
 

@@ -12,7 +12,18 @@
 // the flow enters through the four bilinear weights only.  M = (x1-x0)(y1-y0) of the CLIPPED corners does not
 // depend on the fractional position, so its derivative vanishes (TF's four terms cancel) and
 //   dL/dfx = 2 M^2 / (B den_b) * sum_c (P_c - G_c) * [ (y1-y)(Ic-Ia) + (y-y0)(Id-Ib) ]_c        (same for fy)
-// Two HBM-bound passes: (1) per-sample sums num_b, den_b and the TV sum (double atomics), (2) gradient.
+//
+// The reference's other two training scripts (main_flownetS_pyramid.py:200-250 and the highTV file) compare the warped unstable
+// frame at every level with T targets -- the ground-truth stable frame and five earlier stabilised frames, 3-channel slices of one
+// [B,h,w,Ct] tensor -- each with its own weight c_t:
+//   L = sum_t c_t * mean_b(num_{t,b} / den_b) + scale_tv * TV
+// That is the ONE implementation here.  The warp P, the mask M, sum safe(M) and TV do not depend on the target, so a pixel does its
+// flow read, corners(), four-tap gather, M and TV contribution once and then reads T targets.  The gradient shares
+// 2 M^2 / (B den_b) and the slope; per channel the residual is e = sum_t c_t * (P - g_t), accumulated in float32 in target order
+// with the first term taken as is.  The one-target entry points (vstab_loss_level, vstab_loss_main) are its T = 1 instance with
+// Ct = 3, c_off = {0}, c = {1}: 1.0f * x is exact, so nothing is rounded that the one-target formulas above would not round.
+// Per-sample sums: double[T + 2] = num_0..num_{T-1}, den, tv (T = 1: num, den, tv).
+// Two HBM-bound passes: (1) the per-sample sums (double atomics), (2) gradient.
 // Hand-written for gfx950 (64-lane wavefront reductions).
 #include <hip/hip_runtime.h>
 
@@ -43,6 +54,42 @@ __device__ __forceinline__ Corners corners(int xx, int yy, f32x2 f, int H, int W
     return c;
 }
 
+// pixel i of one sample's [h,w,cs_pf] pixels, whose first two channels are the flow (cs_pf even, 8-byte aligned)
+__device__ __forceinline__ f32x2 flow_at(const float *fb, int cs_pf, int i)
+{
+    return *reinterpret_cast<const f32x2 *>(fb + (long long)i * cs_pf);
+}
+
+// What both passes need of a pixel before they look at a target: the corners its flow f points at, the four bilinear weights, the
+// mask M = tf_warp(ones) (add_n of the four weights) and the four taps in the sample's resized unstable frame ub [h,w,3].
+// h * w * 3 < 2^31 (checked by the entry points), so the tap offsets fit an int.
+struct LossPixel {
+    Corners c;
+    float wa, wb, wc, wd, M;
+    const float *Ia, *Ib, *Ic, *Id;
+};
+__device__ __forceinline__ LossPixel loss_pixel(int xx, int yy, f32x2 f, const float *ub, int h, int w)
+{
+    LossPixel p;
+    const Corners c = corners(xx, yy, f, h, w);
+    p.c = c;
+    p.wa = (c.x1f - c.x) * (c.y1f - c.y); p.wb = (c.x1f - c.x) * (c.y - c.y0f);
+    p.wc = (c.x - c.x0f) * (c.y1f - c.y); p.wd = (c.x - c.x0f) * (c.y - c.y0f);
+    p.M = ((p.wa + p.wb) + p.wc) + p.wd;
+    p.Ia = ub + (c.y0 * w + c.x0) * 3; p.Ib = ub + (c.y1 * w + c.x0) * 3;
+    p.Ic = ub + (c.y0 * w + c.x1) * 3; p.Id = ub + (c.y1 * w + c.x1) * 3;
+    return p;
+}
+
+// total_variation's two forward differences at pixel idx = (yy, xx): fn(q - f) for the neighbour below, then for the one to the
+// right, where they exist
+template <class Fn>
+__device__ __forceinline__ void tv_forward(const float *fb, int cs_pf, int idx, int xx, int yy, int h, int w, f32x2 f, Fn fn)
+{
+    if (yy + 1 < h) { const f32x2 q = flow_at(fb, cs_pf, idx + w); fn(q.x - f.x, q.y - f.y); }
+    if (xx + 1 < w) { const f32x2 q = flow_at(fb, cs_pf, idx + 1); fn(q.x - f.x, q.y - f.y); }
+}
+
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
@@ -51,207 +98,43 @@ __device__ __forceinline__ double wave_sum(double v)
 }
 }  // namespace
 
-// pass 1: sums[3*b + 0] += sum (P*M - G*M)^2, sums[3*b + 1] += sum safe(M) (3 channels), sums[3*b + 2] += TV.
-// pf: [B,h,w,cs_pf] pixels whose first two channels are the flow (cs_pf even).  A workgroup covers LOSS_PPT * 256 pixels, so
-// a full-resolution level issues ~64 atomics per sample and sum instead of ~1000 (they serialise on one address).
-constexpr int LOSS_PPT = 16;
-__global__ __launch_bounds__(256) void loss_sums_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G,
-                                                        const float *__restrict__ U, int h, int w, double *__restrict__ sums)
-{
-    const int n = blockIdx.y;
-    double num = 0.0, den = 0.0, tv = 0.0;
-    const float *fb = pf + (long long)n * h * w * cs_pf;
-    auto flow = [&](int i) { return *reinterpret_cast<const f32x2 *>(fb + (long long)i * cs_pf); };
-    for (int it = 0; it < LOSS_PPT; ++it) {
-        const int idx = (blockIdx.x * LOSS_PPT + it) * 256 + threadIdx.x;
-        if (idx >= h * w) break;
-        const int yy = idx / w, xx = idx - yy * w;
-        const f32x2 f = flow(idx);
-        const Corners c = corners(xx, yy, f, h, w);
-        const float wa = (c.x1f - c.x) * (c.y1f - c.y), wb = (c.x1f - c.x) * (c.y - c.y0f);
-        const float wc = (c.x - c.x0f) * (c.y1f - c.y), wd = (c.x - c.x0f) * (c.y - c.y0f);
-        const float M = ((wa + wb) + wc) + wd;                       // tf_warp(ones): add_n of the four weights
-        const float *ub = U + (long long)n * h * w * 3;
-        const float *Ia = ub + (c.y0 * w + c.x0) * 3, *Ib = ub + (c.y1 * w + c.x0) * 3;
-        const float *Ic = ub + (c.y0 * w + c.x1) * 3, *Id = ub + (c.y1 * w + c.x1) * 3;
-        const float *g = G + ((long long)n * h * w + idx) * 3;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const float P = ((wa * Ia[ch] + wb * Ib[ch]) + wc * Ic[ch]) + wd * Id[ch];
-            const float d = P * M - g[ch] * M;
-            num += (double)(d * d);
-        }
-        den += 3.0 * (double)(M == 0.f ? M + 1e-8f : M);
-        if (yy + 1 < h) { const f32x2 q = flow(idx + w); tv += (double)fabsf(q.x - f.x) + (double)fabsf(q.y - f.y); }
-        if (xx + 1 < w) { const f32x2 q = flow(idx + 1); tv += (double)fabsf(q.x - f.x) + (double)fabsf(q.y - f.y); }
-    }
-    __shared__ double red[3][4];
-    num = wave_sum(num); den = wave_sum(den); tv = wave_sum(tv);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = num; red[1][wave] = den; red[2][wave] = tv; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const double s = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-        atomicAdd(&sums[3 * n + threadIdx.x], s);
-    }
-}
-
-// pass 2: grad[b,y,x,0:2] = d( scale_mse * mean_b(num_b/den_b) + scale_tv * TV ) / d pf[b,y,x,:]   (grad: [B,h,w,cs_g] pixels)
-__global__ __launch_bounds__(256) void loss_grad_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G,
-                                                        const float *__restrict__ U, int B, int h, int w,
-                                                        const double *__restrict__ sums, float scale_mse, float scale_tv,
-                                                        float *__restrict__ grad, int cs_g)
-{
-    const int n = blockIdx.y;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= h * w) return;
-    const int yy = idx / w, xx = idx - yy * w;
-    const float *fb = pf + (long long)n * h * w * cs_pf;
-    auto flow = [&](int i) { return *reinterpret_cast<const f32x2 *>(fb + (long long)i * cs_pf); };
-    const f32x2 f = flow(idx);
-    const Corners c = corners(xx, yy, f, h, w);
-    const float wa = (c.x1f - c.x) * (c.y1f - c.y), wb = (c.x1f - c.x) * (c.y - c.y0f);
-    const float wc = (c.x - c.x0f) * (c.y1f - c.y), wd = (c.x - c.x0f) * (c.y - c.y0f);
-    const float M = ((wa + wb) + wc) + wd;
-    const float *ub = U + (long long)n * h * w * 3;
-    const float *Ia = ub + (c.y0 * w + c.x0) * 3, *Ib = ub + (c.y1 * w + c.x0) * 3;
-    const float *Ic = ub + (c.y0 * w + c.x1) * 3, *Id = ub + (c.y1 * w + c.x1) * 3;
-    const float *g = G + ((long long)n * h * w + idx) * 3;
-    const float k = scale_mse * 2.f * M * M / ((float)B * (float)sums[3 * n + 1]);
-    float gx = 0.f, gy = 0.f;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float a = Ia[ch], b = Ib[ch], cc = Ic[ch], d = Id[ch];
-        const float P = ((wa * a + wb * b) + wc * cc) + wd * d;
-        const float e = P - g[ch];
-        gx += e * ((c.y1f - c.y) * (cc - a) + (c.y - c.y0f) * (d - b));
-        gy += e * ((c.x1f - c.x) * (b - a) + (c.x - c.x0f) * (d - cc));
-    }
-    gx *= k; gy *= k;
-    // total variation: d|q - f| / df = -sign(q - f) at this pixel, +sign(f - p) from the neighbour above / to the left
-    auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); };
-    float tx = 0.f, ty = 0.f;
-    if (yy + 1 < h) { const f32x2 q = flow(idx + w); tx -= sgn(q.x - f.x); ty -= sgn(q.y - f.y); }
-    if (xx + 1 < w) { const f32x2 q = flow(idx + 1); tx -= sgn(q.x - f.x); ty -= sgn(q.y - f.y); }
-    if (yy > 0) { const f32x2 q = flow(idx - w); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
-    if (xx > 0) { const f32x2 q = flow(idx - 1); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
-    f32x2 o;
-    o.x = gx + scale_tv * tx;
-    o.y = gy + scale_tv * ty;
-    *reinterpret_cast<f32x2 *>(grad + ((long long)n * h * w + idx) * cs_g) = o;
-}
-
-// loss_main = sum over levels of [ mean_b(num/den) + tv_weight * sum_b TV ]  (main:213-217, 269-275)
-struct LossTotalArgs { float tvw[8]; int n; };
-__global__ void loss_total_kernel(const double *__restrict__ sums, int B, LossTotalArgs a, double *__restrict__ out)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double total = 0.0;
-    for (int l = 0; l < a.n; ++l) {
-        const double *s = sums + (long long)l * 3 * B;
-        double mse = 0.0, tv = 0.0;
-        for (int b = 0; b < B; ++b) { mse += s[3 * b] / s[3 * b + 1]; tv += s[3 * b + 2]; }
-        total += mse / (double)B + (double)a.tvw[l] * tv;
-    }
-    out[0] = total;
-}
-
-static hipError_t loss_level_kernels(const float *pf, int cs_pf, const float *G, const float *U, int B, int h, int w, double *sums,
-                                     float scale_mse, float scale_tv, float *grad, int cs_g, hipStream_t stream)
-{
-    const int npix = h * w;
-    loss_sums_kernel<<<dim3((unsigned)((npix + 256 * LOSS_PPT - 1) / (256 * LOSS_PPT)), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, U, h, w,
-                                                                                                                          sums);
-    if (grad)
-        loss_grad_kernel<<<dim3((unsigned)((npix + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, U, B, h, w, sums, scale_mse,
-                                                                                                    scale_tv, grad, cs_g);
-    return hipGetLastError();
-}
-
-hipError_t launch_loss_level(const float *pf, const float *G, const float *U, int B, int h, int w, double *sums, float scale_mse,
-                             float scale_tv, float *grad, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * 3 * (size_t)B, stream);
-    if (e != hipSuccess) return e;
-    return loss_level_kernels(pf, 2, G, U, B, h, w, sums, scale_mse, scale_tv, grad, 2, stream);
-}
-
-size_t loss_main_workspace_bytes(int B, const LossLevel *lv, int n)
-{
-    size_t img = 0;
-    for (int l = 0; l < n; ++l) img = std::max(img, (size_t)B * lv[l].h * lv[l].w * 3 * sizeof(float));
-    img = (img + 255) & ~(size_t)255;
-    return 256 + (((size_t)n * 3 * B * sizeof(double) + 255) & ~(size_t)255) + 2 * img;
-}
-
-// All levels of loss_main in one call: per level the two tf.image.resize_images (main:202-203), the sums and the gradient written
-// straight into the caller's (strided) flow-gradient buffer; then the scalar.  22 launches instead of ~80 through the per-level API.
-hipError_t launch_loss_main(const LossLevel *lv, int n, const float *gtstab, const float *unstab, int B, int H, int W, double *loss_out,
-                            void *workspace, hipStream_t stream)
-{
-    char *p = static_cast<char *>(workspace);
-    double *sums = reinterpret_cast<double *>(p);
-    const size_t sbytes = ((size_t)n * 3 * B * sizeof(double) + 255) & ~(size_t)255;
-    size_t img = 0;
-    for (int l = 0; l < n; ++l) img = std::max(img, (size_t)B * lv[l].h * lv[l].w * 3 * sizeof(float));
-    img = (img + 255) & ~(size_t)255;
-    float *G = reinterpret_cast<float *>(p + sbytes), *U = reinterpret_cast<float *>(p + sbytes + img);
-    hipError_t e = hipMemsetAsync(sums, 0, (size_t)n * 3 * B * sizeof(double), stream);
-    if (e != hipSuccess) return e;
-    LossTotalArgs a;
-    a.n = n;
-    for (int l = 0; l < n; ++l) {
-        a.tvw[l] = lv[l].tv_weight;
-        if ((e = launch_resize_bilinear(gtstab, B, H, W, 3, G, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
-        if ((e = launch_resize_bilinear(unstab, B, H, W, 3, U, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
-        if ((e = loss_level_kernels(lv[l].pf, lv[l].cs_pf, G, U, B, lv[l].h, lv[l].w, sums + (size_t)l * 3 * B, 1.0f, lv[l].tv_weight, lv[l].grad,
-                                    lv[l].cs_grad, stream)) != hipSuccess)
-            return e;
-    }
-    loss_total_kernel<<<1, 64, 0, stream>>>(sums, B, a, loss_out);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------
-// The objective of the reference's other two training scripts (main_flownetS_pyramid.py:200-250 and the highTV file): at every
-// level the warped unstable frame is compared with T targets -- the ground-truth stable frame and five earlier stabilised frames,
-// 3-channel slices of one [B,h,w,Ct] tensor -- each with its own weight c_t:
-//   L = sum_t c_t * mean_b(num_{t,b} / den_b) + scale_tv * TV
-// The warp P, the mask M, sum safe(M) and TV do not depend on the target, so a pixel does its flow read, corners(), four-tap
-// gather, M and TV contribution ONCE and then reads T targets.  The gradient shares 2 M^2 / (B den_b) and the slope; per channel
-// the residual is e = sum_t c_t * (P - g_t), accumulated in float32 in target order with the first term taken as is.  Everything
-// else is loss_sums_kernel / loss_grad_kernel operation for operation: with T = 1 and c = 1 the results are bit-equal to theirs.
-// Per-sample sums: double[T + 2] = num_0..num_{T-1}, den, tv.
-// ---------------------------------------------------------------------------------
+// The T targets of a level: 3-channel slices c_off[t]..c_off[t]+2 of the resized target tensor G [B,h,w,Ct], weighted c[t].
 struct LossTargets { int Ct; int c_off[LOSS_MAX_TARGETS]; float c[LOSS_MAX_TARGETS]; };
+// a target slice resized on its own: G [B,h,w,3] is the target, weight 1
+static LossTargets loss_one_target()
+{
+    LossTargets tg = {};
+    tg.Ct = 3;
+    tg.c[0] = 1.0f;
+    return tg;
+}
 
+// pass 1: per sample b, sums[(T+2)*b + t] += sum (P*M - G_t*M)^2, sums[(T+2)*b + T] += sum safe(M) (3 channels),
+// sums[(T+2)*b + T+1] += TV.  pf: [B,h,w,cs_pf] pixels whose first two channels are the flow (cs_pf even).  A workgroup covers
+// LOSS_PPT * 256 pixels, so a full-resolution level issues ~64 atomics per sample and sum instead of ~1000 (they serialise on one
+// address).
+constexpr int LOSS_PPT = 16;
 template <int T>
-__global__ __launch_bounds__(256) void loss_sums_multi_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G,
-                                                              LossTargets tg, const float *__restrict__ U, int h, int w,
-                                                              double *__restrict__ sums)
+__global__ __launch_bounds__(256) void loss_sums_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G, LossTargets tg,
+                                                        const float *__restrict__ U, int h, int w, double *__restrict__ sums)
 {
     const int n = blockIdx.y;
     double num[T], den = 0.0, tv = 0.0;
 #pragma unroll
     for (int t = 0; t < T; ++t) num[t] = 0.0;
     const float *fb = pf + (long long)n * h * w * cs_pf;
-    auto flow = [&](int i) { return *reinterpret_cast<const f32x2 *>(fb + (long long)i * cs_pf); };
+    const float *ub = U + (long long)n * h * w * 3;
     for (int it = 0; it < LOSS_PPT; ++it) {
         const int idx = (blockIdx.x * LOSS_PPT + it) * 256 + threadIdx.x;
         if (idx >= h * w) break;
         const int yy = idx / w, xx = idx - yy * w;
-        const f32x2 f = flow(idx);
-        const Corners c = corners(xx, yy, f, h, w);
-        const float wa = (c.x1f - c.x) * (c.y1f - c.y), wb = (c.x1f - c.x) * (c.y - c.y0f);
-        const float wc = (c.x - c.x0f) * (c.y1f - c.y), wd = (c.x - c.x0f) * (c.y - c.y0f);
-        const float M = ((wa + wb) + wc) + wd;
-        const float *ub = U + (long long)n * h * w * 3;
-        const float *Ia = ub + (c.y0 * w + c.x0) * 3, *Ib = ub + (c.y1 * w + c.x0) * 3;
-        const float *Ic = ub + (c.y0 * w + c.x1) * 3, *Id = ub + (c.y1 * w + c.x1) * 3;
+        const f32x2 f = flow_at(fb, cs_pf, idx);
+        const LossPixel p = loss_pixel(xx, yy, f, ub, h, w);
+        const float M = p.M;
         const float *g = G + ((long long)n * h * w + idx) * tg.Ct;
         float PM[3];
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) PM[ch] = (((wa * Ia[ch] + wb * Ib[ch]) + wc * Ic[ch]) + wd * Id[ch]) * M;
+        for (int ch = 0; ch < 3; ++ch) PM[ch] = (((p.wa * p.Ia[ch] + p.wb * p.Ib[ch]) + p.wc * p.Ic[ch]) + p.wd * p.Id[ch]) * M;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const float *gt = g + tg.c_off[t];
@@ -262,8 +145,7 @@ __global__ __launch_bounds__(256) void loss_sums_multi_kernel(const float *__res
             }
         }
         den += 3.0 * (double)(M == 0.f ? M + 1e-8f : M);
-        if (yy + 1 < h) { const f32x2 q = flow(idx + w); tv += (double)fabsf(q.x - f.x) + (double)fabsf(q.y - f.y); }
-        if (xx + 1 < w) { const f32x2 q = flow(idx + 1); tv += (double)fabsf(q.x - f.x) + (double)fabsf(q.y - f.y); }
+        tv_forward(fb, cs_pf, idx, xx, yy, h, w, f, [&](float dx, float dy) { tv += (double)fabsf(dx) + (double)fabsf(dy); });
     }
     __shared__ double red[T + 2][4];
     const int wave = threadIdx.x >> 6;
@@ -282,33 +164,28 @@ __global__ __launch_bounds__(256) void loss_sums_multi_kernel(const float *__res
     }
 }
 
+// pass 2: grad[b,y,x,0:2] = d( scale_mse * sum_t c_t * mean_b(num_t,b/den_b) + scale_tv * TV ) / d pf[b,y,x,:]   (grad: [B,h,w,cs_g] pixels)
 template <int T>
-__global__ __launch_bounds__(256) void loss_grad_multi_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G,
-                                                              LossTargets tg, const float *__restrict__ U, int B, int h, int w,
-                                                              const double *__restrict__ sums, float scale_tv, float *__restrict__ grad,
-                                                              int cs_g)
+__global__ __launch_bounds__(256) void loss_grad_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G, LossTargets tg,
+                                                        const float *__restrict__ U, int B, int h, int w, const double *__restrict__ sums,
+                                                        float scale_mse, float scale_tv, float *__restrict__ grad, int cs_g)
 {
     const int n = blockIdx.y;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= h * w) return;
     const int yy = idx / w, xx = idx - yy * w;
     const float *fb = pf + (long long)n * h * w * cs_pf;
-    auto flow = [&](int i) { return *reinterpret_cast<const f32x2 *>(fb + (long long)i * cs_pf); };
-    const f32x2 f = flow(idx);
-    const Corners c = corners(xx, yy, f, h, w);
-    const float wa = (c.x1f - c.x) * (c.y1f - c.y), wb = (c.x1f - c.x) * (c.y - c.y0f);
-    const float wc = (c.x - c.x0f) * (c.y1f - c.y), wd = (c.x - c.x0f) * (c.y - c.y0f);
-    const float M = ((wa + wb) + wc) + wd;
-    const float *ub = U + (long long)n * h * w * 3;
-    const float *Ia = ub + (c.y0 * w + c.x0) * 3, *Ib = ub + (c.y1 * w + c.x0) * 3;
-    const float *Ic = ub + (c.y0 * w + c.x1) * 3, *Id = ub + (c.y1 * w + c.x1) * 3;
+    const f32x2 f = flow_at(fb, cs_pf, idx);
+    const LossPixel p = loss_pixel(xx, yy, f, U + (long long)n * h * w * 3, h, w);
+    const Corners &c = p.c;
+    const float M = p.M;
     const float *g = G + ((long long)n * h * w + idx) * tg.Ct;
-    const float k = 2.f * M * M / ((float)B * (float)sums[(T + 2) * n + T]);
+    const float k = scale_mse * 2.f * M * M / ((float)B * (float)sums[(T + 2) * n + T]);
     float gx = 0.f, gy = 0.f;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const float a = Ia[ch], b = Ib[ch], cc = Ic[ch], d = Id[ch];
-        const float P = ((wa * a + wb * b) + wc * cc) + wd * d;
+        const float a = p.Ia[ch], b = p.Ib[ch], cc = p.Ic[ch], d = p.Id[ch];
+        const float P = ((p.wa * a + p.wb * b) + p.wc * cc) + p.wd * d;
         float e = tg.c[0] * (P - g[tg.c_off[0] + ch]);
 #pragma unroll
         for (int t = 1; t < T; ++t) e += tg.c[t] * (P - g[tg.c_off[t] + ch]);
@@ -316,22 +193,22 @@ __global__ __launch_bounds__(256) void loss_grad_multi_kernel(const float *__res
         gy += e * ((c.x1f - c.x) * (b - a) + (c.x - c.x0f) * (d - cc));
     }
     gx *= k; gy *= k;
+    // total variation: d|q - f| / df = -sign(q - f) at this pixel, +sign(f - p) from the neighbour above / to the left
     auto sgn = [](float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); };
     float tx = 0.f, ty = 0.f;
-    if (yy + 1 < h) { const f32x2 q = flow(idx + w); tx -= sgn(q.x - f.x); ty -= sgn(q.y - f.y); }
-    if (xx + 1 < w) { const f32x2 q = flow(idx + 1); tx -= sgn(q.x - f.x); ty -= sgn(q.y - f.y); }
-    if (yy > 0) { const f32x2 q = flow(idx - w); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
-    if (xx > 0) { const f32x2 q = flow(idx - 1); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
+    tv_forward(fb, cs_pf, idx, xx, yy, h, w, f, [&](float dx, float dy) { tx -= sgn(dx); ty -= sgn(dy); });
+    if (yy > 0) { const f32x2 q = flow_at(fb, cs_pf, idx - w); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
+    if (xx > 0) { const f32x2 q = flow_at(fb, cs_pf, idx - 1); tx += sgn(f.x - q.x); ty += sgn(f.y - q.y); }
     f32x2 o;
     o.x = gx + scale_tv * tx;
     o.y = gy + scale_tv * ty;
     *reinterpret_cast<f32x2 *>(grad + ((long long)n * h * w + idx) * cs_g) = o;
 }
 
-// out[0] = sum over levels of [ sum_t c_t * mean_b(num_t/den) + tv_weight * sum_b TV ]; out[1 + t] = sum over levels of
-// mean_b(num_t/den), target t's unweighted share
-struct LossTotalMultiArgs { float tvw[8]; float c[LOSS_MAX_TARGETS]; int n, T; };
-__global__ void loss_total_multi_kernel(const double *__restrict__ sums, int B, LossTotalMultiArgs a, double *__restrict__ out)
+// out[0] = sum over levels of [ sum_t c_t * mean_b(num_t/den) + tv_weight * sum_b TV ]  (main:213-217, 269-275 for T = 1, c = 1);
+// per_target: out[1 + t] = sum over levels of mean_b(num_t/den), target t's unweighted share
+struct LossTotalArgs { float tvw[8]; float c[LOSS_MAX_TARGETS]; int n, T, per_target; };
+__global__ void loss_total_kernel(const double *__restrict__ sums, int B, LossTotalArgs a, double *__restrict__ out)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const int S = a.T + 2;
@@ -351,27 +228,28 @@ __global__ void loss_total_multi_kernel(const double *__restrict__ sums, int B, 
         total += lvl + (double)a.tvw[l] * tv;
     }
     out[0] = total;
-    for (int t = 0; t < a.T; ++t) out[1 + t] = per[t];
+    if (a.per_target)
+        for (int t = 0; t < a.T; ++t) out[1 + t] = per[t];
 }
 
 template <int T>
-static hipError_t loss_level_multi_kernels(const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B, int h,
-                                           int w, double *sums, float scale_tv, float *grad, int cs_g, hipStream_t stream)
+static hipError_t loss_level_kernels(const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B, int h, int w,
+                                     double *sums, float scale_mse, float scale_tv, float *grad, int cs_g, hipStream_t stream)
 {
     const int npix = h * w;
-    loss_sums_multi_kernel<T><<<dim3((unsigned)((npix + 256 * LOSS_PPT - 1) / (256 * LOSS_PPT)), (unsigned)B), dim3(256), 0, stream>>>(
-        pf, cs_pf, G, tg, U, h, w, sums);
+    loss_sums_kernel<T><<<dim3((unsigned)((npix + 256 * LOSS_PPT - 1) / (256 * LOSS_PPT)), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U,
+                                                                                                                             h, w, sums);
     if (grad)
-        loss_grad_multi_kernel<T><<<dim3((unsigned)((npix + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U, B, h, w, sums,
-                                                                                                          scale_tv, grad, cs_g);
+        loss_grad_kernel<T><<<dim3((unsigned)((npix + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U, B, h, w, sums,
+                                                                                                       scale_mse, scale_tv, grad, cs_g);
     return hipGetLastError();
 }
 
-static hipError_t loss_level_multi_dispatch(int T, const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B,
-                                            int h, int w, double *sums, float scale_tv, float *grad, int cs_g, hipStream_t stream)
+static hipError_t loss_level_dispatch(int T, const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B, int h,
+                                      int w, double *sums, float scale_mse, float scale_tv, float *grad, int cs_g, hipStream_t stream)
 {
     switch (T) {
-#define VSTAB_LOSS_T(N) case N: return loss_level_multi_kernels<N>(pf, cs_pf, G, tg, U, B, h, w, sums, scale_tv, grad, cs_g, stream)
+#define VSTAB_LOSS_T(N) case N: return loss_level_kernels<N>(pf, cs_pf, G, tg, U, B, h, w, sums, scale_mse, scale_tv, grad, cs_g, stream)
         VSTAB_LOSS_T(1); VSTAB_LOSS_T(2); VSTAB_LOSS_T(3); VSTAB_LOSS_T(4); VSTAB_LOSS_T(5); VSTAB_LOSS_T(6); VSTAB_LOSS_T(7); VSTAB_LOSS_T(8);
 #undef VSTAB_LOSS_T
     }
@@ -386,16 +264,16 @@ static LossTargets loss_targets(int Ct, int T, const int *c_off, const float *we
     return tg;
 }
 
-hipError_t launch_loss_level_multi(const float *pf, const float *G, int Ct, int T, const int *c_off, const float *weights, const float *U,
-                                   int B, int h, int w, double *sums, float scale_tv, float *grad, hipStream_t stream)
+hipError_t launch_loss_level(const float *pf, const float *G, int Ct, int T, const int *c_off, const float *weights, const float *U, int B,
+                             int h, int w, double *sums, float scale_mse, float scale_tv, float *grad, hipStream_t stream)
 {
     hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * (size_t)(T + 2) * B, stream);
     if (e != hipSuccess) return e;
-    return loss_level_multi_dispatch(T, pf, 2, G, loss_targets(Ct, T, c_off, weights), U, B, h, w, sums, scale_tv, grad, 2, stream);
+    return loss_level_dispatch(T, pf, 2, G, loss_targets(Ct, T, c_off, weights), U, B, h, w, sums, scale_mse, scale_tv, grad, 2, stream);
 }
 
 // workspace: the sums of every level, then the resized targets [B,h,w,Ct] and the resized unstable frame [B,h,w,3] of the largest level
-static void loss_main_multi_layout(int B, const LossLevel *lv, int n, int Ct, int T, size_t &sbytes, size_t &gbytes, size_t &ubytes)
+static void loss_main_layout(int B, const LossLevel *lv, int n, int Ct, int T, size_t &sbytes, size_t &gbytes, size_t &ubytes)
 {
     size_t pix = 0;
     for (int l = 0; l < n; ++l) pix = std::max(pix, (size_t)B * lv[l].h * lv[l].w);
@@ -404,25 +282,24 @@ static void loss_main_multi_layout(int B, const LossLevel *lv, int n, int Ct, in
     ubytes = (pix * 3 * sizeof(float) + 255) & ~(size_t)255;
 }
 
-size_t loss_main_multi_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int T)
+size_t loss_main_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int T)
 {
     size_t s, g, u;
-    loss_main_multi_layout(B, lv, n, Ct, T, s, g, u);
+    loss_main_layout(B, lv, n, Ct, T, s, g, u);
     return 256 + s + g + u;
 }
 
-// All levels of the multi-target objective in one call: per level ONE resize of the whole target tensor (all Ct channels) and one of
-// the unstable frame, the pair above with the gradient written straight into the caller's (strided) flow-gradient buffer; then the
-// scalars.  No allocation.
+// All levels of the objective in one call: per level ONE resize of the whole target tensor (all Ct channels) and one of the unstable
+// frame (the two tf.image.resize_images of main:202-203), the pair above with the gradient written straight into the caller's (strided)
+// flow-gradient buffer; then the scalars.  No allocation; 22 launches at T = 1 instead of ~80 through the per-level API.
 // ONE target of weight 1 has nothing to share: its levels resize the target's three channels alone (read in place from the Ct-channel
-// tensor) and run loss_sums_kernel / loss_grad_kernel themselves -- the same launches, hence the same fp64 atomics, as launch_loss_main
-// on that slice, so the value is launch_loss_main's bit for bit at every size (with T + 2 = 3 the sums have its layout).  A level the
-// slice resize does not take (same size inside wider pixels, or too large for the tile kernel) goes the general way.
-hipError_t launch_loss_main_multi(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
-                                  const float *unstab, int B, int H, int W, double *loss_out, void *workspace, hipStream_t stream)
+// tensor) and hand the kernels that 3-channel G.  A level the slice resize does not take (same size inside wider pixels, or too large
+// for the tile kernel) resizes all Ct channels; the kernels then read the slice at c_off[0], which gives the same bits.
+hipError_t launch_loss_main(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                            const float *unstab, int B, int H, int W, double *loss_out, bool per_target, void *workspace, hipStream_t stream)
 {
     size_t sbytes, gbytes, ubytes;
-    loss_main_multi_layout(B, lv, n, Ct, T, sbytes, gbytes, ubytes);
+    loss_main_layout(B, lv, n, Ct, T, sbytes, gbytes, ubytes);
     char *p = static_cast<char *>(workspace);
     double *sums = reinterpret_cast<double *>(p);
     float *G = reinterpret_cast<float *>(p + sbytes), *U = reinterpret_cast<float *>(p + sbytes + gbytes);
@@ -430,9 +307,10 @@ hipError_t launch_loss_main_multi(const LossLevel *lv, int n, const float *targe
     hipError_t e = hipMemsetAsync(sums, 0, (size_t)n * S * B * sizeof(double), stream);
     if (e != hipSuccess) return e;
     const LossTargets tg = loss_targets(Ct, T, c_off, weights);
-    LossTotalMultiArgs a = {};
+    LossTotalArgs a = {};
     a.n = n;
     a.T = T;
+    a.per_target = per_target ? 1 : 0;
     for (int t = 0; t < T; ++t) a.c[t] = weights[t];
     const bool single = T == 1 && weights[0] == 1.0f;
     for (int l = 0; l < n; ++l) {
@@ -448,15 +326,11 @@ hipError_t launch_loss_main_multi(const LossLevel *lv, int n, const float *targe
         }
         if (!sliced && (e = launch_resize_bilinear(targets, B, H, W, Ct, G, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
         if ((e = launch_resize_bilinear(unstab, B, H, W, 3, U, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
-        if (sliced) {
-            if ((e = loss_level_kernels(lv[l].pf, lv[l].cs_pf, G, U, B, lv[l].h, lv[l].w, sums + (size_t)l * S * B, 1.0f, lv[l].tv_weight, lv[l].grad,
-                                        lv[l].cs_grad, stream)) != hipSuccess)
-                return e;
-        } else if ((e = loss_level_multi_dispatch(T, lv[l].pf, lv[l].cs_pf, G, tg, U, B, lv[l].h, lv[l].w, sums + (size_t)l * S * B, lv[l].tv_weight,
-                                           lv[l].grad, lv[l].cs_grad, stream)) != hipSuccess)
+        if ((e = loss_level_dispatch(T, lv[l].pf, lv[l].cs_pf, G, sliced ? loss_one_target() : tg, U, B, lv[l].h, lv[l].w, sums + (size_t)l * S * B,
+                                     1.0f, lv[l].tv_weight, lv[l].grad, lv[l].cs_grad, stream)) != hipSuccess)
             return e;
     }
-    loss_total_multi_kernel<<<1, 64, 0, stream>>>(sums, B, a, loss_out);
+    loss_total_kernel<<<1, 64, 0, stream>>>(sums, B, a, loss_out);
     return hipGetLastError();
 }
 

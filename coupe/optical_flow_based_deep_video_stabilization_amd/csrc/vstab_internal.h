@@ -518,21 +518,18 @@ int column_sum_chunks(long long rows, int C);  // scratch floats needed = column
 hipError_t launch_column_sum(const float *g, long long rows, int Cs, int c_off, int C, float *out, int accumulate, float *scratch,
                              hipStream_t stream);
 
-// lossterm / masked_MSE / total_variation of one pyramid level and their gradient w.r.t. the flow (train_ops.hip)
-hipError_t launch_loss_level(const float *pf, const float *G, const float *U, int B, int h, int w, double *sums, float scale_mse,
-                             float scale_tv, float *grad, hipStream_t stream);
-struct LossLevel { const float *pf; float *grad; int h, w, cs_pf, cs_grad; float tv_weight; };     // = vstab_loss_level_desc
-size_t loss_main_workspace_bytes(int B, const LossLevel *lv, int n);
-hipError_t launch_loss_main(const LossLevel *lv, int n, const float *gtstab, const float *unstab, int B, int H, int W, double *loss_out,
-                            void *workspace, hipStream_t stream);
-// the same objective against T weighted 3-channel targets inside one [B,h,w,Ct] tensor (the previous-frame terms of
-// main_flownetS_pyramid.py:200-250): sums = double[(T+2)*B] = num_0..num_{T-1}, den, tv per sample; c_off / weights are host arrays
+// lossterm / masked_MSE / total_variation of one pyramid level against T weighted 3-channel targets inside one [B,h,w,Ct] tensor, and
+// their gradient w.r.t. the flow (train_ops.hip; the previous-frame terms of main_flownetS_pyramid.py:200-250, the one-target loss of
+// main:188-210 at Ct = 3, T = 1, c_off = {0}, weights = {1}): sums = double[(T+2)*B] = num_0..num_{T-1}, den, tv per sample; c_off /
+// weights are host arrays.  B <= 65535 and h * w * 3 < 2^31 (the callers check).
 constexpr int LOSS_MAX_TARGETS = 8;
-hipError_t launch_loss_level_multi(const float *pf, const float *G, int Ct, int T, const int *c_off, const float *weights, const float *U,
-                                   int B, int h, int w, double *sums, float scale_tv, float *grad, hipStream_t stream);
-size_t loss_main_multi_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int T);
-hipError_t launch_loss_main_multi(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
-                                  const float *unstab, int B, int H, int W, double *loss_out, void *workspace, hipStream_t stream);
+hipError_t launch_loss_level(const float *pf, const float *G, int Ct, int T, const int *c_off, const float *weights, const float *U, int B,
+                             int h, int w, double *sums, float scale_mse, float scale_tv, float *grad, hipStream_t stream);
+struct LossLevel { const float *pf; float *grad; int h, w, cs_pf, cs_grad; float tv_weight; };     // = vstab_loss_level_desc
+size_t loss_main_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int T);
+// all levels in one call; loss_out: the objective, and with per_target the T unweighted per-target shares after it
+hipError_t launch_loss_main(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                            const float *unstab, int B, int H, int W, double *loss_out, bool per_target, void *workspace, hipStream_t stream);
 hipError_t launch_flow_medfilt(const float *flow, int B, int h, int w, int kh, int kw, int kc, float *out, hipStream_t stream);
 
 // SSIM structure term, its gradient and the 2x2 SAME average pool (ssim_ops.hip; utils.py:74-166).  win: the 1-D vector whose outer

@@ -30,16 +30,45 @@ def _f32(t, name, c):
     return t.contiguous()
 
 
+def _f32c(t, name):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[3] < 3:
+        raise ValueError(f"{name} must be a float32 CUDA tensor [B,H,W,Ct], Ct >= 3")
+    return t.contiguous()
+
+
+def _level_inputs(predict_flow, targets, unstab_image, name, three: bool):
+    """What lossterm and lossterm_multi do before their library call: the checked flow, the target tensor (`three`: exactly 3 channels,
+    else Ct >= 3) and the unstable frame, both resized to the flow's size (tf.image.resize_images, main:202-203)."""
+    pf = _f32(predict_flow, "predict_flow", 2)
+    B, h, w, _ = pf.shape
+    tg = _f32(targets, name, 3) if three else _f32c(targets, name)
+    unstab = _f32(unstab_image, "unstab_image", 3)
+    if tg.shape[0] != B or unstab.shape[:3] != tg.shape[:3]:
+        raise ValueError(f"{name} / unstab_image must be [B,H,W,{3 if three else '.'}] with the flow's batch size")
+    return pf, resize_images(tg, (h, w)), resize_images(unstab, (h, w))
+
+
+def _level_descs(flows, grads, tv_weights, B):
+    """The vstab_loss_level_desc array of loss_main_fused / loss_main_multi: one entry per LOSS_LEVELS name."""
+    desc = (_lib.LossLevelDesc * len(LOSS_LEVELS))()
+    for d, name, tvw in zip(desc, LOSS_LEVELS, tv_weights):
+        pf = flows[name]
+        if not pf.is_cuda or pf.dtype != torch.float32 or pf.dim() != 4 or pf.shape[0] != B or not pf.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor [B,h,w,C]")
+        d.pf, d.h, d.w, d.cs_pf, d.tv_weight = pf.data_ptr(), pf.shape[1], pf.shape[2], pf.shape[3], tvw
+        if grads is not None:
+            g = grads[name]
+            if g.shape[:3] != pf.shape[:3] or g.dtype != torch.float32 or not g.is_contiguous() or g.device != pf.device:
+                raise ValueError(f"grads[{name}] must be a contiguous float32 tensor [B,h,w,C'] beside the flow")
+            d.grad, d.cs_grad = g.data_ptr(), g.shape[3]
+    return desc
+
+
 def lossterm(predict_flow, stab_image, unstab_image, tv_weight: float = 0.0, need_grad: bool = True):
     """main:200-210 (+ the level's TV term when tv_weight != 0).  Returns (loss [0-dim float64 CUDA tensor],
     d loss / d predict_flow [B,h,w,2] or None)."""
-    pf = _f32(predict_flow, "predict_flow", 2)
+    pf, gt, un = _level_inputs(predict_flow, stab_image, unstab_image, "stab_image", three=True)
     B, h, w, _ = pf.shape
-    stab, unstab = _f32(stab_image, "stab_image", 3), _f32(unstab_image, "unstab_image", 3)
-    if stab.shape[0] != B or unstab.shape != stab.shape:
-        raise ValueError("stab_image / unstab_image must be [B,H,W,3] with the flow's batch size")
-    gt = resize_images(stab, (h, w))                                   # tf.image.resize_images, main:202-203
-    un = resize_images(unstab, (h, w))
     sums = torch.empty(3 * B, dtype=torch.float64, device=pf.device)
     grad = torch.empty_like(pf) if need_grad else None
     with torch.cuda.device(pf.device):
@@ -71,21 +100,11 @@ def loss_main_fused(flows: Dict[str, torch.Tensor], gtstab_image, unstab_image, 
     B, H, W, _ = stab.shape
     if unstab.shape != stab.shape:
         raise ValueError("stab_image / unstab_image must have the same shape")
-    desc = (_lib.LossLevelDesc * len(LOSS_LEVELS))()
-    for d, name, tvw in zip(desc, LOSS_LEVELS, TV_WEIGHTS):
-        pf = flows[name]
-        if not pf.is_cuda or pf.dtype != torch.float32 or pf.dim() != 4 or pf.shape[0] != B or not pf.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor [B,h,w,C]")
-        d.pf, d.h, d.w, d.cs_pf, d.tv_weight = pf.data_ptr(), pf.shape[1], pf.shape[2], pf.shape[3], tvw
-        if grads is not None:
-            g = grads[name]
-            if g.shape[:3] != pf.shape[:3] or g.dtype != torch.float32 or not g.is_contiguous() or g.device != pf.device:
-                raise ValueError(f"grads[{name}] must be a contiguous float32 tensor [B,h,w,C'] beside the flow")
-            d.grad, d.cs_grad = g.data_ptr(), g.shape[3]
+    desc = _level_descs(flows, grads, TV_WEIGHTS, B)
     L = _lib.lib()
     n = L.vstab_loss_main_workspace_bytes(C.addressof(desc), len(LOSS_LEVELS), B)
     if n == 0:
-        raise ValueError("loss_main: bad level descriptors (channel counts must be even)")
+        raise ValueError("loss_main: bad level descriptors (channel counts must be even, level sizes below 2^31 / 3 pixels, B <= 65535)")
     ws = torch.empty(n, dtype=torch.uint8, device=stab.device)
     out = torch.empty((), dtype=torch.float64, device=stab.device)
     with torch.cuda.device(stab.device):
@@ -153,26 +172,15 @@ def _targets(c_off, weights, Ct):
     return T, (C.c_int32 * T)(*c_off), (C.c_float * T)(*weights), weights
 
 
-def _f32c(t, name):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[3] < 3:
-        raise ValueError(f"{name} must be a float32 CUDA tensor [B,H,W,Ct], Ct >= 3")
-    return t.contiguous()
-
-
 def lossterm_multi(predict_flow, targets, unstab_image, c_off, weights, tv_weight: float = 0.0, need_grad: bool = True):
     """One level of main_flownetS_pyramid.py:203-250: sum_t weights[t] * lossterm(predict_flow, targets[..., c_off[t]:c_off[t]+3],
     unstab_image) + tv_weight * TV in one kernel pair (`vstab_loss_level_multi`): the warp, the mask and the denominator are shared.
     targets [B,H,W,Ct] is resized once, all channels.  Returns (loss [0-dim float64 CUDA tensor], d loss / d predict_flow [B,h,w,2]
     or None, per-target lossterms [T] float64, unweighted)."""
-    pf = _f32(predict_flow, "predict_flow", 2)
+    pf, gt, un = _level_inputs(predict_flow, targets, unstab_image, "targets", three=False)
     B, h, w, _ = pf.shape
-    tg, unstab = _f32c(targets, "targets"), _f32(unstab_image, "unstab_image", 3)
-    Ct = tg.shape[3]
-    if tg.shape[0] != B or unstab.shape[:3] != tg.shape[:3]:
-        raise ValueError("targets / unstab_image must be [B,H,W,.] with the flow's batch size")
-    T, offs, wts, wlist = _targets(c_off, weights, Ct)
-    gt = resize_images(tg, (h, w))
-    un = resize_images(unstab, (h, w))
+    Ct = gt.shape[3]
+    T, offs, wts, _w = _targets(c_off, weights, Ct)
     sums = torch.empty((T + 2) * B, dtype=torch.float64, device=pf.device)
     grad = torch.empty_like(pf) if need_grad else None
     with torch.cuda.device(pf.device):
@@ -195,17 +203,7 @@ def loss_main_multi(flows: Dict[str, torch.Tensor], stab_image, unstab_image, ob
     if unstab.shape[:3] != stab.shape[:3]:
         raise ValueError("stab_image / unstab_image must have the same batch and frame size")
     T, offs, wts, _w = _targets(objective.target_channels, objective.target_weights, Ct)
-    desc = (_lib.LossLevelDesc * len(LOSS_LEVELS))()
-    for d, name, tvw in zip(desc, LOSS_LEVELS, objective.tv_weights):
-        pf = flows[name]
-        if not pf.is_cuda or pf.dtype != torch.float32 or pf.dim() != 4 or pf.shape[0] != B or not pf.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous float32 CUDA tensor [B,h,w,C]")
-        d.pf, d.h, d.w, d.cs_pf, d.tv_weight = pf.data_ptr(), pf.shape[1], pf.shape[2], pf.shape[3], tvw
-        if grads is not None:
-            g = grads[name]
-            if g.shape[:3] != pf.shape[:3] or g.dtype != torch.float32 or not g.is_contiguous() or g.device != pf.device:
-                raise ValueError(f"grads[{name}] must be a contiguous float32 tensor [B,h,w,C'] beside the flow")
-            d.grad, d.cs_grad = g.data_ptr(), g.shape[3]
+    desc = _level_descs(flows, grads, objective.tv_weights, B)
     L = _lib.lib()
     n = L.vstab_loss_main_multi_workspace_bytes(C.addressof(desc), len(LOSS_LEVELS), B, Ct, T)
     if n == 0:

@@ -436,7 +436,9 @@ VSTAB_API int vstab_axpby(const float *x, float a, const float *y, float b, floa
  * gt / unstab: [B,h,w,3] already resized to the flow's size (vstab_resize_bilinear = tf.image.resize_images).
  * sums: device double[3*B], overwritten with {sum sq, sum safe(M), TV} per sample -- the level's loss is
  *   scale_mse * mean_b(sums[3b]/sums[3b+1]) + scale_tv * sum_b sums[3b+2]   (the caller adds the levels up).
- * grad_pf (may be NULL): [B,h,w,2] d(that loss)/d(pf), overwritten. */
+ * grad_pf (may be NULL): [B,h,w,2] d(that loss)/d(pf), overwritten.
+ * Limits: B <= 65535 and h * w * 3 < 2^31, VSTAB_E_SHAPE beyond them (nothing is launched).  This is vstab_loss_level_multi below
+ * at Ct = 3, T = 1, c_off = {0}, weights = {1}, plus scale_mse. */
 VSTAB_API int vstab_loss_level(const float *pf, const float *gt, const float *unstab, int B, int h, int w, double *sums,
                                float scale_mse, float scale_tv, float *grad_pf, void *stream);
 
@@ -444,7 +446,10 @@ VSTAB_API int vstab_loss_level(const float *pf, const float *gt, const float *un
  * full-size stable / unstable frames [B,H,W,3] to the flow's size (main:202-203), lossterm + the TV term, and (grad != NULL)
  * d loss_main / d flow written into channels 0..1 of the caller's [B,h,w,cs_grad] buffer.  pf: [B,h,w,cs_pf] pixels whose
  * channels 0..1 are the flow; channel strides even.  loss_out: one device double = sum over levels of
- * mean_b(masked_MSE) + tv_weight * TV. */
+ * mean_b(masked_MSE) + tv_weight * TV.
+ * Limits: 1..8 levels, B <= 65535 and h * w * 3 < 2^31 for every level: beyond them vstab_loss_main returns VSTAB_E_SHAPE before
+ * anything is launched and vstab_loss_main_workspace_bytes returns 0.  This is vstab_loss_main_multi below at Ct = 3, T = 1,
+ * c_off = {0}, weights = {1}, with one double of output. */
 typedef struct vstab_loss_level_desc {
     const float *pf;
     float *grad;
@@ -461,7 +466,8 @@ VSTAB_API int vstab_loss_main(const vstab_loss_level_desc *levels, int n_levels,
  * unstab [B,h,w,3]); c_off / weights are HOST arrays of T entries.  The warp, the mask, sum safe(M) and TV are shared:
  *   loss = sum_t weights[t] * mean_b(num_t / den) + scale_tv * sum_b TV
  * sums: device double[(T+2)*B], overwritten with {num_0 .. num_{T-1}, den, TV} per sample.  grad_pf (may be NULL): [B,h,w,2]
- * d loss / d pf, overwritten.  With T = 1, weights[0] = 1 both outputs are bit-equal to vstab_loss_level(scale_mse = 1).
+ * d loss / d pf, overwritten.  With T = 1, weights[0] = 1 both outputs are those of vstab_loss_level(scale_mse = 1) on that slice: the
+ * same kernels.
  * VSTAB_E_STATE for a NULL buffer or array; VSTAB_E_SHAPE for T outside 1..8, c_off[t] < 0 or c_off[t] + 3 > Ct, bad sizes;
  * VSTAB_E_ALIGN when pf / grad_pf / sums are not 8-byte aligned. */
 VSTAB_API int vstab_loss_level_multi(const float *pf, const float *targets, int Ct, int T, const int *c_off, const float *weights,
@@ -470,8 +476,8 @@ VSTAB_API int vstab_loss_level_multi(const float *pf, const float *targets, int 
  * target tensor [B,H,W,Ct] (all Ct channels) and one of unstab [B,H,W,3], then the level above with its gradient written into
  * channels 0..1 of the level's grad buffer.  loss_out: device double[1 + T] = the objective (sum over levels of
  * sum_t weights[t] * mean_b(masked_MSE_t) + tv_weight * TV), then per target the unweighted sum over levels of mean_b(masked_MSE_t).
- * One target of weight 1 is vstab_loss_main on that slice, launch for launch (only the target's three channels are resized): value
- * and gradients are its bits.  The call allocates nothing; workspace as sized by vstab_loss_main_multi_workspace_bytes (0 for arguments the call would reject),
+ * One target of weight 1 is vstab_loss_main on that slice (only the target's three channels are resized): value and gradients are
+ * its bits.  The call allocates nothing; workspace as sized by vstab_loss_main_multi_workspace_bytes (0 for arguments the call would reject),
  * VSTAB_E_NOMEM when too small.  Errors as above; odd channel strides in a descriptor are VSTAB_E_SHAPE. */
 VSTAB_API size_t vstab_loss_main_multi_workspace_bytes(const vstab_loss_level_desc *levels, int n_levels, int B, int Ct, int T);
 VSTAB_API int vstab_loss_main_multi(const vstab_loss_level_desc *levels, int n_levels, const float *targets, int Ct, int T, const int *c_off,

@@ -1,6 +1,6 @@
 """The objective with the previous-frame terms (main_flownetS_pyramid.py:200-250 and the highTV file) on the GPU:
 `vstab_loss_level_multi` / `vstab_loss_main_multi`, `training.lossterm_multi` / `loss_main_multi` and `Trainer(objective=...)` against
-the existing one-target entry points (bit for bit where the arithmetic is the same) and against the fp64 reference of
+the one-target entry points (bit for bit: two ABI paths onto one kernel pair) and against the fp64 reference of
 tests/loss_prev_ref.py (bounds stated there).  Shapes are those of test_gpu_training.py: the last level of the first case crosses one
 4096-pixel workgroup of pass 1."""
 import ctypes as C
@@ -65,7 +65,7 @@ def _check_against_reference(loss, per, grads, p, obj, what=""):
         assert err <= tol, (k, err, tol)
 
 
-# ----------------------------------------------------------------------------- 1. one target, weight 1: today's kernels bit for bit
+# ----------------------------------------------------------------------------- 1. one target, weight 1: vstab_loss_level bit for bit
 @pytest.mark.parametrize("i", range(len(CASES)))
 def test_one_target_weight_one_is_loss_level_bit_for_bit(i):
     stab, un, flows, _p = _case(i)
@@ -304,9 +304,13 @@ def _noprev_pair():
 
 
 def test_trainer_noprev_objective_is_the_default_path_bit_for_bit():
-    """Level 2 is 94 x 126 here: three workgroups per sample in pass 1, where the fp64 atomics of two DIFFERENT kernels need not arrive
-    in the same order.  One target of weight 1 therefore runs loss_sums_kernel / loss_grad_kernel themselves inside
-    vstab_loss_main_multi, and the loss value is the default path's too."""
+    """One target of weight 1 inside vstab_loss_main_multi resizes the target's three channels alone and runs the T = 1 kernels
+    vstab_loss_main runs, so gradients and loss value are the default path's.
+    Level 2 is 94 x 126 here: three workgroups per sample in pass 1, whose fp64 atomics arrive in no fixed order, so the VALUE comparison
+    below can miss by one ulp from run to run although both sides run the same kernels (measured on an MI355X, before and after the
+    one-target kernels were merged into the T = 1 instance alike: 40 vstab_loss_level calls on this level gave two bit patterns of the
+    sums, 38 : 2; six fused / multi pairs gave 0x1.89360af1a52c7p-1 on one side and ...c8p-1 on the other three times).  Up to two
+    workgroups per sample (8192 pixels) the sum is order-independent.  The gradients read den rounded to float32 and do not see it."""
     a, b = _noprev_pair()
     assert a[0] == b[0], (a[0], b[0])
     for k in LEVELS:
@@ -376,7 +380,59 @@ def test_trainer_prev_objective_flow_gradients_and_descent():
     assert tr.train_epoch([(feats, stab, un)], epoch=0)[0] == pytest.approx(float(after), rel=1e-12)
 
 
-# ----------------------------------------------------------------------------- 7. argument checks
+# ----------------------------------------------------------------------------- 7. scale_mse, argument checks
+def test_scale_mse_scales_the_photometric_gradient_only():
+    """vstab_loss_level's scale_mse enters the gradient as k = scale_mse * 2 M^2 / (B den) and nothing else: the sums do not see it, and
+    with scale_tv = 0 a power of two scales every gradient element exactly."""
+    stab, un, flows, _p = _case(1)
+    pf = flows["predict_flow3"].cuda()
+    B, h, w, _ = pf.shape
+    assert (B, h, w) == (1, 6, 8)
+    G, U = resize_images(stab[..., :3].contiguous().cuda(), (h, w)), resize_images(un.cuda(), (h, w))
+    got = {}
+    for scale in (0.5, 1.0):
+        sums, grad = torch.full((3 * B,), -1.0, dtype=torch.float64, device="cuda"), torch.full_like(pf, 7.0)
+        _lib.check(_lib.lib().vstab_loss_level(pf.data_ptr(), G.data_ptr(), U.data_ptr(), B, h, w, sums.data_ptr(), scale, 0.0, grad.data_ptr(),
+                                               runtime.stream_ptr()))
+        got[scale] = (sums, grad)
+    assert torch.equal(got[0.5][0], got[1.0][0])
+    assert float(got[1.0][1].abs().max()) > 0.0
+    assert torch.equal(2 * got[0.5][1], got[1.0][1])
+
+
+def test_one_target_entry_points_have_the_limits_of_the_multi_target_ones():
+    """B <= 65535 (gridDim.y) and h * w * 3 < 2^31 (32-bit tap offsets): VSTAB_E_SHAPE / a workspace size of 0 before anything is
+    launched -- the buffers here are a few floats."""
+    L = _lib.lib()
+    SHAPE = -1
+    small = torch.zeros(64).cuda()
+    sums = torch.zeros(8, dtype=torch.float64).cuda()
+    st = runtime.stream_ptr()
+
+    def level(B, h, w):
+        return L.vstab_loss_level(small.data_ptr(), small.data_ptr(), small.data_ptr(), B, h, w, sums.data_ptr(), 1.0, 0.0, None, st)
+
+    assert level(1, 1, 2) == 0
+    assert level(1, 1, 715827883) == SHAPE and b"loss_level" in L.vstab_last_error(None)            # h * w * 3 = 2^31 + 1
+    assert level(65536, 1, 1) == SHAPE
+
+    def main_bytes(B, h, w):
+        d = (_lib.LossLevelDesc * 1)()
+        d[0].pf, d[0].h, d[0].w, d[0].cs_pf, d[0].tv_weight = small.data_ptr(), h, w, 2, 0.0
+        return d, L.vstab_loss_main_workspace_bytes(C.addressof(d), 1, B)
+
+    assert main_bytes(1, 1, 715827883)[1] == 0 and main_bytes(65536, 1, 1)[1] == 0
+    assert main_bytes(1, 1, 715827882)[1] > 2 * 4 * (2 ** 31 - 2)                                   # h * w * 3 = 2^31 - 2: sized, not launched
+    d, n = main_bytes(1, 1, 2)
+    out, ws = torch.zeros((), dtype=torch.float64).cuda(), torch.zeros(n, dtype=torch.uint8).cuda()
+    big, _n = main_bytes(1, 1, 715827883)
+    for desc, B in ((big, 1), (d, 65536)):
+        assert L.vstab_loss_main(C.addressof(desc), 1, small.data_ptr(), small.data_ptr(), B, 1, 2, out.data_ptr(), ws.data_ptr(), n, st) == SHAPE
+        assert b"loss_main" in L.vstab_last_error(None)
+    assert L.vstab_loss_main(C.addressof(d), 1, small.data_ptr(), small.data_ptr(), 1, 1, 2, out.data_ptr(), ws.data_ptr(), n, st) == 0
+    torch.cuda.synchronize()
+
+
 def test_argument_checks():
     L = _lib.lib()
     B, h, w, Ct = 2, 5, 6, 24

@@ -121,3 +121,20 @@ def test_instrumentation_entry_points_without_gpu():
     assert (ms.value, n.value, by.value) == (0.0, 0, 0.0)
     assert L.vstab_hbm_profile_read(3, C.byref(ms), C.byref(n), C.byref(by)) == 0 and L.vstab_hbm_profile_read(7, C.byref(ms), C.byref(n), C.byref(by)) < 0
     assert L.vstab_hbm_profile_enable(5) < 0
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("sizes", [[(1, 2), (2, 3), (4, 6), (8, 12), (62, 94)], [(1, 1), (2, 2), (3, 4), (6, 8), (46, 62)],
+                                   [(1, 1), (2, 2), (3, 3), (5, 5), (38, 38)]])
+def test_one_target_loss_workspace_is_the_multi_target_one_at_three_channels(B, sizes):
+    """vstab_loss_main is vstab_loss_main_multi at Ct = 3, T = 1, workspace included (the level lists of test_gpu_loss_prev.CASES).
+    The size query only looks at the descriptors: pf points at host memory here."""
+    anchor = (C.c_double * 1)()
+    d = (_lib.LossLevelDesc * len(sizes))()
+    for e, (h, w) in zip(d, sizes):
+        e.pf, e.h, e.w, e.cs_pf, e.tv_weight = C.addressof(anchor), h, w, 4, 0.0
+    one = L.vstab_loss_main_workspace_bytes(C.addressof(d), len(sizes), B)
+    assert one == L.vstab_loss_main_multi_workspace_bytes(C.addressof(d), len(sizes), B, 3, 1)
+    h, w = sizes[-1]
+    assert one >= len(sizes) * 3 * B * 8 + 2 * B * h * w * 3 * 4
+    assert L.vstab_loss_main_multi_workspace_bytes(C.addressof(d), len(sizes), B, 24, 6) > one
