@@ -6,7 +6,13 @@ per step.  The stage's algorithmic bytes -- LSTM: y (4 N) and c read, the three 
 slice written; GRU: y (2 N), h twice and y2 read, r h, h' and the h slice written; N = B H W F floats -- are given as a fraction of
 8 TB/s.  For scale the same arithmetic composed of torch ops on the same device (F.conv2d in NCHW plus the elementwise and
 reduction ops) is timed interleaved with the library's calls; it is a comparison, not a gate.  Prints one JSON line.  Not part of
-bench.py's workload."""
+bench.py's workload.
+
+--backward adds, per case, the training step of a cell built with differentiable=True: forward + backward of the 8-step run_sequence
+(gradients to the inputs and every parameter; upstream gradients given for every output, and for the LSTM's final c), the
+gate-backward launches alone (training.conv*_backward on one step's saved buffers, their output allocations included), and the same
+8-step training step composed of torch ops under torch.autograd, timed interleaved; also the largest difference of the two input
+gradients.  Without the flag the output is what it was."""
 import argparse
 import json
 import os
@@ -17,7 +23,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from coupe.optical_flow_based_deep_video_stabilization_amd import cell   # noqa: E402
+from coupe.optical_flow_based_deep_video_stabilization_amd import _lib, cell, training   # noqa: E402
 
 PEAK_GBS = 8000.0
 B, H, W, CX, FILTERS, K, T = 8, 64, 64, 256, 256, 3, 8
@@ -87,7 +93,77 @@ def _torch_weights(w):
     return out
 
 
-def case_rows(kind, normalize, iters, warmup):
+def backward_rows(kind, normalize, w, xs, iters, warmup):
+    """the --backward columns of one case"""
+    g = torch.Generator().manual_seed(29)
+    lstm = kind == "lstm"
+    cl = (cell.ConvLSTMCell if lstm else cell.ConvGRUCell)([H, W], FILTERS, [K, K], normalize=normalize, differentiable=True)
+    cl.assign_weights(w)
+    params = list(cl.parameters().values())
+    gout = torch.randn(T, B, H, W, FILTERS, generator=g).cuda()
+    gc = torch.randn(B, H, W, FILTERS, generator=g).cuda()
+    xl = xs.clone().requires_grad_()
+
+    def train():
+        xl.grad = None
+        for p in params:
+            p.grad = None
+        outs, final = cell.run_sequence(cl, xl)
+        torch.autograd.backward([outs, final.c] if lstm else [outs], [gout, gc] if lstm else [gout])
+
+    tw = {n: t.requires_grad_() for n, t in _torch_weights(w).items()}
+    xt = xs.permute(0, 1, 4, 2, 3).contiguous().requires_grad_()
+    gout_t, gc_t = gout.permute(0, 1, 4, 2, 3).contiguous(), gc.permute(0, 3, 1, 2).contiguous()
+
+    def torch_train():
+        xt.grad = None
+        for p in tw.values():
+            p.grad = None
+        h = c = torch.zeros(B, FILTERS, H, W, device="cuda")
+        outs = []
+        for t in range(T):
+            if lstm:
+                c, h = torch_lstm(xt[t], c, h, tw, normalize)
+            else:
+                h = torch_gru(xt[t], h, tw, normalize)
+            outs.append(h)
+        torch.autograd.backward([torch.stack(outs), c] if lstm else [torch.stack(outs)], [gout_t, gc_t] if lstm else [gout_t])
+
+    # one step's saved buffers for the gate backward alone
+    with torch.no_grad():
+        x0, z = xs[0], torch.zeros(B, H, W, FILTERS, device="cuda")
+        cl.call(x0, (z, z) if lstm else z)
+    bufs, L, dev = cl.buffers(B, xs.device), _lib.lib(), cl._dev
+    dh = gout[0]
+    if lstm:
+        stats = tuple(cl._stats(bufs.gate_ws, int(L.vstab_convlstm_gates_stats_offset(B, H, W, FILTERS, q)), n, B)
+                      for q, n in ((0, 3), (1, 2))) if normalize else None
+        pe = tuple(dev[n] for n in ("W_ci", "W_cf", "W_co"))
+
+        def gates():
+            training.convlstm_gates_backward(bufs.y, z, dh, gc, pe, dev.get("gamma"), dev.get("beta"), stats)
+    else:
+        # (the update's statistics are in the workspace; the gates' were overwritten by them: a gates call puts them back)
+        off = int(L.vstab_convgru_stats_offset(B, H, W, FILTERS))
+        stats_c = cl._stats(bufs.gate_ws, off, 1, B) if normalize else None
+        cl._gates(bufs)
+        stats_g = cl._stats(bufs.gate_ws, off, 2, B) if normalize else None
+        h_old, drh = bufs.cat2[..., cl._hoff:cl._hoff + FILTERS], gc
+
+        def gates():
+            du, _, dhh, _ = training.convgru_update_backward(bufs.y2, h_old, bufs.u, dh, dev.get("candidate/gamma"), dev.get("candidate/beta"), stats_c)
+            training.convgru_gates_backward(bufs.y, h_old, du, drh, dhh, dev.get("gates/gamma"), dev.get("gates/beta"), stats_g)
+
+    train()
+    torch_train()
+    diff = float((xl.grad.permute(0, 1, 4, 2, 3) - xt.grad).abs().max())
+    us = time_interleaved({"train": train, "gates": gates, "torch_train": torch_train}, iters, warmup)
+    return {"train_sequence8_us": round(us["train"], 1), "gate_backward_us": round(us["gates"], 1),
+            "torch_train_sequence8_us": round(us["torch_train"], 1), "train_x_torch": round(us["train"] / us["torch_train"], 3),
+            "max_abs_dinputs_diff_vs_torch": diff}
+
+
+def case_rows(kind, normalize, iters, warmup, backward=False):
     g = torch.Generator().manual_seed(17)
     x, c, h = (torch.rand(B, H, W, n, generator=g).mul_(2).sub_(1).cuda() for n in (CX, FILTERS, FILTERS))
     xs = torch.rand(T, B, H, W, CX, generator=g).mul_(2).sub_(1).cuda()
@@ -126,17 +202,21 @@ def case_rows(kind, normalize, iters, warmup):
         step()                                                   # (leaves a whole step's y, y2 and u in the buffers that `post` reads)
         us = time_interleaved({"step": step, "post_conv": post, "sequence8": lambda: cell.run_sequence(cl, xs), "torch_step": tstep},
                               iters, warmup)
-    return {"cell": kind, "normalize": normalize, "max_abs_diff_vs_torch": diff, "step_us": round(us["step"], 1),
+    row = {"cell": kind, "normalize": normalize, "max_abs_diff_vs_torch": diff, "step_us": round(us["step"], 1),
             "post_conv_us": round(us["post_conv"], 1), "post_conv_alg_bytes": alg,
             "post_conv_frac_8TBs": round(alg / (us["post_conv"] * 1e-6) / 1e9 / PEAK_GBS, 4),
             "sequence8_us_per_step": round(us["sequence8"] / T, 1), "torch_step_us": round(us["torch_step"], 1),
             "step_x_torch": round(us["step"] / us["torch_step"], 3)}
+    if backward:
+        row.update(backward_rows(kind, normalize, w, xs, iters, warmup))
+    return row
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--backward", action="store_true", help="add the training step (forward + backward of the 8-step sequence) per case")
     args = ap.parse_args()
     if args.iters < 20:
         ap.error("--iters must be >= 20")
@@ -144,7 +224,7 @@ def main():
         raise SystemExit("bench_cell.py needs a GPU")
     result = {"bench": "conv_rnn_cells", "batch": B, "height": H, "width": W, "in_channels": CX, "filters": FILTERS, "kernel": K,
               "iters": args.iters, "device": torch.cuda.get_device_name(0),
-              "cases": [case_rows(kind, norm, args.iters, args.warmup) for kind in ("lstm", "gru") for norm in (True, False)]}
+              "cases": [case_rows(kind, norm, args.iters, args.warmup, args.backward) for kind in ("lstm", "gru") for norm in (True, False)]}
     print(json.dumps(result))
 
 

@@ -170,6 +170,17 @@ EXPORTS = {
                             [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "vstab_convgru_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 6 +
                              [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_convlstm_gates_stats_offset": (C.c_size_t, [C.c_int] * 5),
+    "vstab_convlstm_gates_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "vstab_convlstm_gates_backward": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float] +
+                                      [C.c_int] * 3 + [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_convgru_stats_offset": (C.c_size_t, [C.c_int] * 4),
+    "vstab_convgru_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "vstab_convgru_update_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 7 +
+                                      [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
+    "vstab_convgru_gates_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 6 +
+                                     [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "vstab_host_xcd_remap": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int32)]),
     "vstab_level_sizes": (C.c_int, [C.c_int, C.c_int, c_int32_p]),
     "vstab_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -1,6 +1,7 @@
 """Drop-in for the reference's cell.py: ConvLSTMCell (cell.py:5-76) and ConvGRUCell (cell.py:78-136) on float32 CUDA tensors in NHWC.
 
-Forward only: results carry no `grad_fn`, whatever the inputs require (as the bicubic sampler's).  A step is the SAME convolution over
+By default forward only: results carry no `grad_fn`, whatever the inputs require (as the bicubic sampler's).  Built with
+`differentiable=True` a cell trains (last paragraph).  A step is the SAME convolution over
 concat([x, h]) on the MFMA implicit-GEMM kernel (`vstab_conv_forward`) followed by the fused gate launches of csrc/cell_ops.hip
 (`vstab_convlstm_gates`, `vstab_convgru_gates`, `vstab_convgru_update`).  x and h live side by side in one persistent NHWC buffer per
 cell and batch size whose channel stride and h offset are rounded up to multiples of 4 (pad channels zero, the kernel tensor padded
@@ -24,7 +25,16 @@ Weights are given, not created: `assign_weights(dict)` with the names TensorFlow
         candidate/LayerNorm/{gamma,beta};  else gates/bias [2F], candidate/bias [F].
 `filters == 1` is the same formulas (the reference's m = 4 and m = 2).
 
-Not built: the backward, data_format='channels_first' (the reference passes 'NC' with feature axis 0 for it, which is wrong for a
+Differentiable mode (constructor keyword `differentiable=True`; the default path is untouched): `assign_weights` (re)creates
+`parameters()`, a dict name -> float32 CUDA leaf with requires_grad in the reference's shapes; every `call` / `run_sequence` reads their
+current values (the padded device copies are rebuilt once per call, not per step), so an optimiser's in-place step takes effect.  When
+grad mode is on and x, the state or a parameter requires grad, the results hang on one torch.autograd.Function per `call` /
+`run_sequence` (the whole sequence: back-propagation through time inside it); gradients flow to the inputs, the initial state and every
+parameter, `needs_input_grad` decides what is computed, forward values are bit-equal to the default path's.  Backward of a step: the
+gate-stage backward kernels of csrc/cell_ops.hip (`training.convlstm_gates_backward`, `convgru_update_backward`,
+`convgru_gates_backward`), then `training.conv_wgrad` and `training.conv_dgrad` on the concat buffer.  First derivatives only.
+
+Not built: data_format='channels_first' (the reference passes 'NC' with feature axis 0 for it, which is wrong for a
 batched tensor: NotImplementedError here), even or rectangular kernels, kernels wider than 7, and the commented-out
 spatial-transformer GRU of cell.py:138-208.
 """
@@ -71,7 +81,7 @@ class _Buffers:
 
 
 class _ConvCell:
-    def __init__(self, shape, filters, kernel, activation, normalize, data_format):
+    def __init__(self, shape, filters, kernel, activation, normalize, data_format, differentiable=False):
         if data_format == "channels_first":
             raise NotImplementedError("data_format='channels_first' is not built (the reference's own form of it is wrong for a batch)")
         if data_format != "channels_last":
@@ -92,6 +102,8 @@ class _ConvCell:
         self._cx = None                       # input channels: known once the weights are
         self._dev = {}                        # device tensors of the weights
         self._bufs = {}
+        self._differentiable = bool(differentiable)
+        self._params = None                   # differentiable: name -> float32 CUDA leaf, the reference's shapes
 
     @property
     def output_size(self):
@@ -133,6 +145,47 @@ class _ConvCell:
     def _ptr(self, name):
         t = self._dev.get(name)
         return t.data_ptr() if t is not None else None
+
+    # ---- differentiable mode
+    def parameters(self):
+        """name -> tensor with the names and shapes of `weight_shapes()`: float32 CUDA leaves with requires_grad, (re)created by
+        `assign_weights`.  Every `call` / `run_sequence` reads their current values."""
+        if not self._differentiable:
+            raise ValueError("parameters(): construct the cell with differentiable=True")
+        if self._params is None:
+            raise ValueError("assign_weights() first")
+        return dict(self._params)
+
+    def _set_parameters(self, cx, host):
+        runtime._require_gpu()
+        self._cx, self._hoff, self._cs = cx, _up4(cx), _up4(cx) + _up4(self._filters)
+        self._params = {n: torch.from_numpy(a).cuda().requires_grad_() for n, a in host.items()}
+        self._bufs = {}
+        self._refresh()
+
+    def _padded_kernel_dev(self, w):
+        """`_padded_kernel` on the device, twice: ([k,k,cs,m] for the forward, the same with the output channels zero-padded to a
+        multiple of 4 for `vstab_conv_dgrad`)"""
+        k, F, cx, m = self._k, self._filters, self._cx, w.shape[3]
+        out = torch.zeros((k, k, self._cs, _up4(m)), dtype=torch.float32, device=w.device)
+        out[:, :, :cx, :m] = w[:, :, :cx]
+        out[:, :, self._hoff:self._hoff + F, :m] = w[:, :, cx:]
+        return (out if m % 4 == 0 else out[..., :m].contiguous()), out
+
+    def _refresh(self):
+        """the device copies the kernels read, from the parameters' current values: once per call / run_sequence"""
+        with torch.no_grad():
+            self._dev = self._dev_from({n: t.detach() for n, t in self._params.items()})
+
+    def _wants_graph(self, *tensors):
+        return torch.is_grad_enabled() and any(t.requires_grad for t in tensors + tuple(self._params.values()))
+
+    def _kernel_grad(self, dW):
+        """[k,k,cs,m] in the concat layout -> the reference's [k,k,Cx+F,m]"""
+        return torch.cat([dW[:, :, :self._cx], dW[:, :, self._hoff:self._hoff + self._filters]], dim=2)
+
+    def _stats(self, ws, offset, Q, B):
+        return ws[offset:offset + B * Q * 8].clone()
 
     # ---- checks
     def _check_tensor(self, t, name, channels):
@@ -194,8 +247,8 @@ class ConvLSTMCell(_ConvCell):
     tensors without `grad_fn`."""
 
     def __init__(self, shape, filters, kernel, forget_bias=1.0, activation="tanh", normalize=True, peephole=True, data_format="channels_last",
-                 reuse=None):
-        super().__init__(shape, filters, kernel, activation, normalize, data_format)
+                 reuse=None, differentiable=False):
+        super().__init__(shape, filters, kernel, activation, normalize, data_format, differentiable)
         self._forget_bias = float(forget_bias)
         self._peephole = bool(peephole)
 
@@ -218,6 +271,8 @@ class ConvLSTMCell(_ConvCell):
     def assign_weights(self, weights):
         cx = self._kernel_in_channels(weights, "kernel", 4 * self._filters)
         host = {n: self._take(weights, n, s) for n, s in self.weight_shapes(cx).items()}
+        if self._differentiable:
+            return self._set_parameters(cx, host)
         dev = {"kernel": self._padded_kernel(host["kernel"], cx)}
         for n in ("bias", "W_ci", "W_cf", "W_co"):
             if n in host:
@@ -226,6 +281,14 @@ class ConvLSTMCell(_ConvCell):
             dev["gamma"] = np.stack([host[ln + "/gamma"] for ln in _LSTM_LN])
             dev["beta"] = np.stack([host[ln + "/beta"] for ln in _LSTM_LN])
         self._set_weights(cx, dev)
+
+    def _dev_from(self, p):
+        dev = {n: p[n].contiguous() for n in ("bias", "W_ci", "W_cf", "W_co") if n in p}
+        dev["kernel"], dev["kernel4"] = self._padded_kernel_dev(p["kernel"])
+        if self._normalize:
+            dev["gamma"] = torch.stack([p[ln + "/gamma"] for ln in _LSTM_LN])
+            dev["beta"] = torch.stack([p[ln + "/beta"] for ln in _LSTM_LN])
+        return dev
 
     def synthetic_weights(self, seed, in_channels, random_ln=False):
         """Weights for tests and the benchmark as a dict of numpy arrays: the kernel scaled so that pre-activations of U(-1,1) inputs are
@@ -261,6 +324,13 @@ class ConvLSTMCell(_ConvCell):
         except (TypeError, ValueError):
             raise ValueError("state must be a (c, h) pair") from None
         self._check_call(x, (("c", c), ("h", h)))
+        if self._differentiable:
+            self._refresh()
+            if self._wants_graph(x, c, h):
+                with torch.cuda.device(x.device):
+                    outs, c_new = _LstmSequence.apply(self, x.unsqueeze(0), c, h, *self._params.values())
+                h_new = outs[0]
+                return h_new, LSTMStateTuple(c_new, h_new)
         with torch.no_grad(), torch.cuda.device(x.device):
             b = self.buffers(x.shape[0], x.device)
             b.cat[..., :self._cx].copy_(x)
@@ -285,12 +355,20 @@ class ConvLSTMCell(_ConvCell):
             self._step(b, c, c, outputs[t])
         return outputs, LSTMStateTuple(c, outputs[T - 1].clone())
 
+    def _sequence_graph(self, inputs, state):
+        if state is None:
+            c0 = h0 = torch.zeros((inputs.shape[1],) + tuple(self._size), dtype=torch.float32, device=inputs.device)
+        else:
+            c0, h0 = state
+        outputs, c = _LstmSequence.apply(self, inputs, c0, h0, *self._params.values())
+        return outputs, LSTMStateTuple(c, outputs[-1].clone())
+
 
 class ConvGRUCell(_ConvCell):
     """The reference's ConvGRUCell (cell.py:78-136); module docstring.  `call(x, h)` returns `(h', h')`, a new tensor without `grad_fn`."""
 
-    def __init__(self, shape, filters, kernel, activation="tanh", normalize=True, data_format="channels_last", reuse=None):
-        super().__init__(shape, filters, kernel, activation, normalize, data_format)
+    def __init__(self, shape, filters, kernel, activation="tanh", normalize=True, data_format="channels_last", reuse=None, differentiable=False):
+        super().__init__(shape, filters, kernel, activation, normalize, data_format, differentiable)
 
     @property
     def state_size(self):
@@ -310,6 +388,8 @@ class ConvGRUCell(_ConvCell):
     def assign_weights(self, weights):
         cx = self._kernel_in_channels(weights, "gates/kernel", 2 * self._filters)
         host = {n: self._take(weights, n, s) for n, s in self.weight_shapes(cx).items()}
+        if self._differentiable:
+            return self._set_parameters(cx, host)
         dev = {"gates/kernel": self._padded_kernel(host["gates/kernel"], cx), "candidate/kernel": self._padded_kernel(host["candidate/kernel"], cx)}
         if self._normalize:
             dev["gates/gamma"] = np.stack([host["gates/LayerNorm/gamma"], host["gates/LayerNorm_1/gamma"]])
@@ -320,6 +400,20 @@ class ConvGRUCell(_ConvCell):
             dev["gates/bias"] = host["gates/bias"]
             dev["candidate/bias"] = host["candidate/bias"]
         self._set_weights(cx, dev)
+
+    def _dev_from(self, p):
+        dev = {}
+        for n in ("gates", "candidate"):
+            dev[n + "/kernel"], dev[n + "/kernel4"] = self._padded_kernel_dev(p[n + "/kernel"])
+        if self._normalize:
+            dev["gates/gamma"] = torch.stack([p["gates/LayerNorm/gamma"], p["gates/LayerNorm_1/gamma"]])
+            dev["gates/beta"] = torch.stack([p["gates/LayerNorm/beta"], p["gates/LayerNorm_1/beta"]])
+            dev["candidate/gamma"] = p["candidate/LayerNorm/gamma"].contiguous()
+            dev["candidate/beta"] = p["candidate/LayerNorm/beta"].contiguous()
+        else:
+            dev["gates/bias"] = p["gates/bias"].contiguous()
+            dev["candidate/bias"] = p["candidate/bias"].contiguous()
+        return dev
 
     def synthetic_weights(self, seed, in_channels, random_ln=False):
         """As ConvLSTMCell.synthetic_weights; the reference's initialisers: gates/bias ones, candidate/bias zeros."""
@@ -337,11 +431,14 @@ class ConvGRUCell(_ConvCell):
         b.gate_ws = _ws(_lib.lib().vstab_convgru_workspace_bytes(B, self._H, self._W, F, int(self._normalize)), device)
         return b
 
-    def _step(self, b, h_out):
-        """one step on loaded buffers: b.cat holds x and h, b.cat2 holds x; h' -> h_out and the h slice of b.cat"""
+    def _step(self, b, h_out, between=None):
+        """one step on loaded buffers: b.cat holds x and h, b.cat2 holds x; h' -> h_out and the h slice of b.cat.  between: called
+        after the gates stage (the update reuses the place of its statistics)"""
         F = self._filters
         self._conv(b.cat, self._dev["gates/kernel"], self._dev.get("gates/bias"), b.y, 2 * F, b.conv_ws)
         self._gates(b)
+        if between is not None:
+            between()
         self._conv(b.cat2, self._dev["candidate/kernel"], self._dev.get("candidate/bias"), b.y2, F, b.conv_ws)
         self._update(b, h_out)
 
@@ -363,6 +460,12 @@ class ConvGRUCell(_ConvCell):
 
     def call(self, x, h):
         self._check_call(x, (("h", h),))
+        if self._differentiable:
+            self._refresh()
+            if self._wants_graph(x, h):
+                with torch.cuda.device(x.device):
+                    h_new = _GruSequence.apply(self, x.unsqueeze(0), h, *self._params.values())[0]
+                return h_new, h_new
         with torch.no_grad(), torch.cuda.device(x.device):
             b = self.buffers(x.shape[0], x.device)
             self._load_x(b, x)
@@ -384,6 +487,166 @@ class ConvGRUCell(_ConvCell):
             self._load_x(b, inputs[t])
             self._step(b, outputs[t])
         return outputs, outputs[T - 1].clone()
+
+    def _sequence_graph(self, inputs, state):
+        h0 = torch.zeros((inputs.shape[1],) + tuple(self._size), dtype=torch.float32, device=inputs.device) if state is None else state
+        outputs = _GruSequence.apply(self, inputs, h0, *self._params.values())
+        return outputs, outputs[-1].clone()
+
+
+# ---------------------------------------------------------------------------------------------------- differentiable mode
+# One torch.autograd.Function per call / run_sequence.  The forward is the loop of `_sequence` on the same buffers (the same bits) and
+# keeps, per step, a snapshot of the concat buffer(s), the convolution output(s), the old c (LSTM) / u (GRU) and the layer-norm
+# statistics.  The backward walks t = T-1 .. 0: gate backward (training.conv*_backward), filter gradient (training.conv_wgrad,
+# accumulating into a [k,k,cs,.] buffer in the concat layout), input gradient (training.conv_dgrad, with the kernel's output channels
+# zero-padded to the gate gradient's row stride) into a concat-shaped buffer whose x slice is dx_t and whose h slice joins dh of step t-1.
+def _sum_or(a, b):
+    return a if b is None else a + b
+
+
+def _save_steps(ctx, steps):
+    """the per-step snapshots through save_for_backward (None entries remembered in ctx.layout)"""
+    ctx.layout = [[t is not None for t in s] for s in steps]
+    ctx.save_for_backward(*(t for s in steps for t in s if t is not None))
+
+
+def _saved_steps(ctx):
+    it = iter(ctx.saved_tensors)
+    return [tuple(next(it) if has else None for has in s) for s in ctx.layout]
+
+
+class _LstmSequence(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cell, inputs, c0, h0, *params):
+        T, B = inputs.shape[0], inputs.shape[1]
+        H, W, F = cell._H, cell._W, cell._filters
+        b = cell.buffers(B, inputs.device)
+        outputs = torch.empty((T, B) + tuple(cell._size), dtype=torch.float32, device=inputs.device)
+        b.cat[..., cell._hoff:cell._hoff + F].copy_(h0)
+        c = c0.detach().contiguous()
+        offs = [int(_lib.lib().vstab_convlstm_gates_stats_offset(B, H, W, F, q)) for q in (0, 1)] if cell._normalize else None
+        steps = []
+        for t in range(T):
+            b.cat[..., :cell._cx].copy_(inputs[t])
+            cat_t, c_new = b.cat.clone(), cell._new_state(B, inputs.device)
+            cell._step(b, c, c_new, outputs[t])
+            stats = (cell._stats(b.gate_ws, offs[0], 3, B), cell._stats(b.gate_ws, offs[1], 2, B)) if cell._normalize else (None, None)
+            steps.append((cat_t, b.y.clone(), c) + stats)
+            c = c_new
+        _save_steps(ctx, steps)
+        ctx.cell, ctx.dev, ctx.names = cell, cell._dev, list(cell._params)
+        return outputs, c
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_c):
+        from . import training
+        cell, dev, steps = ctx.cell, ctx.dev, _saved_steps(ctx)
+        T, F, cx, hoff, k, m = len(steps), cell._filters, cell._cx, cell._hoff, cell._k, 4 * cell._filters
+        need_in, need_c0, need_h0 = ctx.needs_input_grad[1:4]
+        need = dict(zip(ctx.names, ctx.needs_input_grad[4:]))
+        need_peep = cell._peephole and any(need[n] for n in ("W_ci", "W_cf", "W_co"))
+        need_ln = cell._normalize and any(v for n, v in need.items() if "LayerNorm" in n)
+        need_w = need["kernel"] or need.get("bias", False)
+        cat0 = steps[0][0]
+        B, H, W, cs = cat0.shape
+        g_out = None if g_out is None else g_out.contiguous()
+        d_in = torch.empty((T, B, H, W, cx), dtype=torch.float32, device=cat0.device) if need_in else None
+        dcat = torch.empty_like(cat0)
+        dW = torch.empty((k, k, cs, m), dtype=torch.float32, device=cat0.device) if need_w else None
+        db = torch.empty((m,), dtype=torch.float32, device=cat0.device) if need.get("bias", False) else None
+        pe = tuple(dev[n] for n in ("W_ci", "W_cf", "W_co")) if cell._peephole else None
+        dc, carry, pg = g_c, None, None
+        for n, t in enumerate(range(T - 1, -1, -1)):
+            cat_t, y, c_old = steps[t][:3]
+            stats = steps[t][3:] if cell._normalize else None
+            dh = carry if g_out is None else _sum_or(g_out[t], carry)
+            dy, dc, pg = training.convlstm_gates_backward(y, c_old, dh, dc, pe, dev.get("gamma"), dev.get("beta"), stats, cell._forget_bias, cell._act,
+                                                          need_peepholes=need_peep, need_ln=need_ln, grads=pg, accumulate=n > 0)
+            if need_w:
+                training.conv_wgrad(cat_t, dy, k, 1, (k - 1) // 2, cin=cs, cout=m, dW=dW, db=db, accumulate=n > 0, want_db=db is not None)
+            if t > 0 or need_in or need_h0:
+                training.conv_dgrad(dy, dev["kernel4"], 1, (k - 1) // 2, (H, W), cout=_up4(m), dx=dcat)
+                if need_in:
+                    d_in[t].copy_(dcat[..., :cx])
+                carry = dcat[..., hoff:hoff + F]
+        grads = {"kernel": cell._kernel_grad(dW) if need["kernel"] else None, "bias": db}
+        grads.update({n: pg[n] for n in ("W_ci", "W_cf", "W_co")})
+        for q, ln in enumerate(_LSTM_LN):
+            for leaf in ("gamma", "beta"):
+                grads[f"{ln}/{leaf}"] = pg[leaf][q] if pg[leaf] is not None else None
+        return (None, d_in, dc if need_c0 else None, carry.contiguous() if need_h0 else None) + tuple(grads[n] if need[n] else None for n in ctx.names)
+
+
+class _GruSequence(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cell, inputs, h0, *params):
+        T, B = inputs.shape[0], inputs.shape[1]
+        H, W, F = cell._H, cell._W, cell._filters
+        b = cell.buffers(B, inputs.device)
+        outputs = torch.empty((T, B) + tuple(cell._size), dtype=torch.float32, device=inputs.device)
+        b.cat[..., cell._hoff:cell._hoff + F].copy_(h0)
+        off = int(_lib.lib().vstab_convgru_stats_offset(B, H, W, F)) if cell._normalize else None
+        steps = []
+        for t in range(T):
+            cell._load_x(b, inputs[t])
+            cat_t, stats_g = b.cat.clone(), []
+            cell._step(b, outputs[t], between=(lambda: stats_g.append(cell._stats(b.gate_ws, off, 2, B))) if cell._normalize else None)
+            stats_c = cell._stats(b.gate_ws, off, 1, B) if cell._normalize else None
+            steps.append((cat_t, b.cat2.clone(), b.y.clone(), b.y2.clone(), b.u.clone(), stats_g[0] if stats_g else None, stats_c))
+        _save_steps(ctx, steps)
+        ctx.cell, ctx.dev, ctx.names = cell, cell._dev, list(cell._params)
+        return outputs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        from . import training
+        cell, dev, steps = ctx.cell, ctx.dev, _saved_steps(ctx)
+        T, F, cx, hoff, k = len(steps), cell._filters, cell._cx, cell._hoff, cell._k
+        need_in, need_h0 = ctx.needs_input_grad[1:3]
+        need = dict(zip(ctx.names, ctx.needs_input_grad[3:]))
+        need_ln = {p: cell._normalize and any(v for n, v in need.items() if n.startswith(p + "/LayerNorm")) for p in ("gates", "candidate")}
+        need_w = {p: need[p + "/kernel"] or need.get(p + "/bias", False) for p in ("gates", "candidate")}
+        cat0 = steps[0][0]
+        B, H, W, cs = cat0.shape
+        g_out = g_out.contiguous()
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=cat0.device)          # noqa: E731
+        d_in = new(T, B, H, W, cx) if need_in else None
+        dcat = torch.empty_like(cat0)
+        dW = {"gates": new(k, k, cs, 2 * F) if need_w["gates"] else None, "candidate": new(k, k, cs, F) if need_w["candidate"] else None}
+        db = {"gates": new(2 * F) if need.get("gates/bias", False) else None, "candidate": new(F) if need.get("candidate/bias", False) else None}
+        carry, pgg, pgc, pad = None, None, None, (k - 1) // 2
+        for n, t in enumerate(range(T - 1, -1, -1)):
+            cat_t, cat2_t, y, y2, u, stats_g, stats_c = steps[t]
+            h_old = cat_t[..., hoff:hoff + F]
+            du, dy2, dh, pgc = training.convgru_update_backward(y2, h_old, u, _sum_or(g_out[t], carry), dev.get("candidate/gamma"), dev.get("candidate/beta"),
+                                                                stats_c, cell._act, need_ln=need_ln["candidate"], grads=pgc, accumulate=n > 0)
+            if need_w["candidate"]:
+                training.conv_wgrad(cat2_t, dy2, k, 1, pad, cin=cs, cout=F, dW=dW["candidate"], db=db["candidate"], accumulate=n > 0,
+                                    want_db=db["candidate"] is not None)
+            training.conv_dgrad(dy2, dev["candidate/kernel4"], 1, pad, (H, W), cout=_up4(F), dx=dcat)
+            drh = dcat[..., hoff:hoff + F]
+            dy, pgg = training.convgru_gates_backward(y, h_old, du, drh, dh, dev.get("gates/gamma"), dev.get("gates/beta"), stats_g,
+                                                      need_ln=need_ln["gates"], grads=pgg, accumulate=n > 0)
+            if need_w["gates"]:
+                training.conv_wgrad(cat_t, dy, k, 1, pad, cin=cs, cout=2 * F, dW=dW["gates"], db=db["gates"], accumulate=n > 0,
+                                    want_db=db["gates"] is not None)
+            drh.zero_()                       # (d(r h) is spent: the slice now collects the gates convolution's gradient of h)
+            if t > 0 or need_in or need_h0:
+                training.conv_dgrad(dy, dev["gates/kernel4"], 1, pad, (H, W), cout=_up4(2 * F), dx=dcat, accumulate=True)
+                if need_in:
+                    d_in[t].copy_(dcat[..., :cx])
+                carry = dh + drh
+        grads = {}
+        for p, pg, names in (("gates", pgg, ("gates/LayerNorm", "gates/LayerNorm_1")), ("candidate", pgc, ("candidate/LayerNorm",))):
+            grads[p + "/kernel"] = cell._kernel_grad(dW[p]) if need[p + "/kernel"] else None
+            grads[p + "/bias"] = db[p]
+            for q, ln in enumerate(names):
+                for leaf in ("gamma", "beta"):
+                    g = pg[leaf]
+                    grads[f"{ln}/{leaf}"] = None if g is None else (g[q] if g.dim() == 2 else g)
+        return (None, d_in, carry if need_h0 else None) + tuple(grads[n] if need[n] else None for n in ctx.names)
 
 
 def _synthetic(shapes, seed, random_ln, constants):
@@ -417,5 +680,10 @@ def run_sequence(cell, inputs, state=None):
     else:
         states = () if state is None else (("h", state),)
     cell._check_call(inputs[0], states)
+    if cell._differentiable:
+        cell._refresh()
+        if cell._wants_graph(inputs, *(s for _, s in states)):
+            with torch.cuda.device(inputs.device):
+                return cell._sequence_graph(inputs, state)
     with torch.no_grad(), torch.cuda.device(inputs.device):
         return cell._sequence(inputs.detach(), state)

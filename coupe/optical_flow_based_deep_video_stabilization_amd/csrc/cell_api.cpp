@@ -80,3 +80,100 @@ extern "C" int vstab_convgru_update(const float *y2, int ys, const float *h, int
                                            (hipStream_t)stream));
     return VSTAB_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- backward
+namespace {
+
+// the checks every backward entry point shares after its own NULL / shape tests: the workspace, when the flags need one
+int bwd_workspace_ok(const char *who, void *workspace, size_t workspace_bytes, size_t need)
+{
+    if (need == 0) return VSTAB_OK;
+    if (!workspace) return fail(nullptr, VSTAB_E_STATE, "%s: NULL workspace", who);
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(nullptr, VSTAB_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
+    if (workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    return VSTAB_OK;
+}
+
+}  // namespace
+
+extern "C" size_t vstab_convlstm_gates_stats_offset(int B, int H, int W, int F, int which)
+{
+    if (!cell_shape_ok(B, H, W, F, F) || which < 0 || which > 1) return 0;
+    return convlstm_stats_offset(B, H * W, F, which);
+}
+
+extern "C" size_t vstab_convgru_stats_offset(int B, int H, int W, int F)
+{
+    if (!cell_shape_ok(B, H, W, F, F)) return 0;
+    return convgru_stats_offset(B, H * W, F);
+}
+
+extern "C" size_t vstab_convlstm_gates_backward_workspace_bytes(int B, int H, int W, int F, int normalize, int peephole)
+{
+    if (!cell_shape_ok(B, H, W, F, 10LL * F)) return 0;
+    return convlstm_backward_workspace_bytes(B, H * W, F, normalize != 0, peephole != 0);
+}
+
+extern "C" int vstab_convlstm_gates_backward(const float *y, int ys, const float *c, const float *w_ci, const float *w_cf, const float *w_co,
+                                             const float *gamma, const float *beta, const float *stats_jif, const float *stats_oc,
+                                             const float *dh, int dhs, const float *dc_new, int B, int H, int W, int F, float forget_bias, int act,
+                                             int normalize, int peephole, float *dy, int dys, float *dc, float *dw_ci, float *dw_cf,
+                                             float *dw_co, float *dgamma, float *dbeta, int accumulate, void *workspace, size_t workspace_bytes,
+                                             void *stream)
+{
+    const int npeep = (dw_ci != nullptr) + (dw_cf != nullptr) + (dw_co != nullptr);
+    if (!y || !c || !dy || !dc || (peephole && (!w_ci || !w_cf || !w_co)) || (normalize && (!gamma || !beta || !stats_jif || !stats_oc)) ||
+        (npeep != 0 && (npeep != 3 || !peephole)) || (!dgamma != !dbeta) || (dgamma && !normalize))
+        return fail(nullptr, VSTAB_E_STATE, "convlstm_gates_backward: NULL buffer (the peephole gradients go together, as do dgamma and dbeta)");
+    if (!cell_shape_ok(B, H, W, F, 10LL * F) || !cell_shape_ok(B, H, W, F, ys) || ys < 4LL * F || !cell_shape_ok(B, H, W, F, dys) || dys < 4LL * F ||
+        act < 0 || act > 2 || (dh && !cell_shape_ok(B, H, W, F, dhs)))
+        return fail(nullptr, VSTAB_E_SHAPE, "convlstm_gates_backward: need B, H, W, F >= 1, ys, dys >= 4 F, dhs >= F, act 0..2 and every tensor below 2^31 elements");
+    const int rc = bwd_workspace_ok("convlstm_gates_backward", workspace, workspace_bytes,
+                                    convlstm_backward_workspace_bytes(B, H * W, F, normalize != 0, peephole != 0));
+    if (rc != VSTAB_OK) return rc;
+    HIP_TRY(nullptr, launch_convlstm_gates_backward(y, ys, c, w_ci, w_cf, w_co, gamma, beta, stats_jif, stats_oc, dh, dhs, dc_new, B, H * W, F,
+                                                    forget_bias, act, normalize != 0, peephole != 0, dy, dys, dc, dw_ci, dw_cf, dw_co, dgamma, dbeta,
+                                                    accumulate ? 1 : 0, workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" size_t vstab_convgru_backward_workspace_bytes(int B, int H, int W, int F, int normalize)
+{
+    if (!cell_shape_ok(B, H, W, F, 4LL * F)) return 0;
+    return convgru_backward_workspace_bytes(B, H * W, F, normalize != 0);
+}
+
+extern "C" int vstab_convgru_update_backward(const float *y2, int ys, const float *h, int hs, const float *u, const float *gamma, const float *beta,
+                                             const float *stats, const float *dh_new, int dhns, int B, int H, int W, int F, int act, int normalize,
+                                             float *dy2, int dys, float *du, float *dh, int dhs, float *dgamma, float *dbeta, int accumulate,
+                                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!y2 || !h || !u || !dh_new || !dy2 || !du || !dh || (normalize && (!gamma || !beta || !stats)) || (!dgamma != !dbeta) ||
+        (dgamma && !normalize))
+        return fail(nullptr, VSTAB_E_STATE, "convgru_update_backward: NULL buffer (dgamma and dbeta go together)");
+    if (!cell_shape_ok(B, H, W, F, 4LL * F) || !cell_shape_ok(B, H, W, F, ys) || !cell_shape_ok(B, H, W, F, hs) || !cell_shape_ok(B, H, W, F, dhns) ||
+        !cell_shape_ok(B, H, W, F, dys) || !cell_shape_ok(B, H, W, F, dhs) || act < 0 || act > 2)
+        return fail(nullptr, VSTAB_E_SHAPE, "convgru_update_backward: need B, H, W, F >= 1, every stride >= F, act 0..2 and every tensor below 2^31 elements");
+    const int rc = bwd_workspace_ok("convgru_update_backward", workspace, workspace_bytes, convgru_backward_workspace_bytes(B, H * W, F, normalize != 0));
+    if (rc != VSTAB_OK) return rc;
+    HIP_TRY(nullptr, launch_convgru_update_backward(y2, ys, h, hs, u, gamma, beta, stats, dh_new, dhns, B, H * W, F, act, normalize != 0, dy2, dys, du,
+                                                    dh, dhs, dgamma, dbeta, accumulate ? 1 : 0, workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_convgru_gates_backward(const float *y, int ys, const float *h, int hs, const float *gamma, const float *beta, const float *stats,
+                                            const float *du, const float *drh, int drhs, int B, int H, int W, int F, int normalize, float *dy, int dys,
+                                            float *dh, int dhs, float *dgamma, float *dbeta, int accumulate, void *workspace,
+                                            size_t workspace_bytes, void *stream)
+{
+    if (!y || !h || !du || !drh || !dy || !dh || (normalize && (!gamma || !beta || !stats)) || (!dgamma != !dbeta) || (dgamma && !normalize))
+        return fail(nullptr, VSTAB_E_STATE, "convgru_gates_backward: NULL buffer (dgamma and dbeta go together)");
+    if (!cell_shape_ok(B, H, W, F, 4LL * F) || !cell_shape_ok(B, H, W, F, ys) || ys < 2LL * F || !cell_shape_ok(B, H, W, F, dys) || dys < 2LL * F ||
+        !cell_shape_ok(B, H, W, F, hs) || !cell_shape_ok(B, H, W, F, drhs) || !cell_shape_ok(B, H, W, F, dhs))
+        return fail(nullptr, VSTAB_E_SHAPE, "convgru_gates_backward: need B, H, W, F >= 1, ys, dys >= 2 F, hs, drhs, dhs >= F and every tensor below 2^31 elements");
+    const int rc = bwd_workspace_ok("convgru_gates_backward", workspace, workspace_bytes, convgru_backward_workspace_bytes(B, H * W, F, normalize != 0));
+    if (rc != VSTAB_OK) return rc;
+    HIP_TRY(nullptr, launch_convgru_gates_backward(y, ys, h, hs, gamma, beta, stats, du, drh, drhs, B, H * W, F, normalize != 0, dy, dys, dh, dhs, dgamma,
+                                                   dbeta, accumulate ? 1 : 0, workspace, (hipStream_t)stream));
+    return VSTAB_OK;
+}

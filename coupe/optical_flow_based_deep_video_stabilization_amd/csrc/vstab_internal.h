@@ -560,6 +560,25 @@ hipError_t launch_convgru_gates(const float *y, int ys, const float *h, int hs, 
 hipError_t launch_convgru_update(const float *y2, int ys, const float *h, int hs, const float *u, const float *gamma, const float *beta, int B,
                                  int HW, int F, int act, bool normalize, float *h_out, float *h_new, int hns, void *workspace,
                                  hipStream_t stream);
+// The backward of the same stages.  stats_*: the forward's {mean, rstd} pairs, found in ITS workspace at conv*_stats_offset() bytes
+// (LSTM which 0: [B][3] j, i, f; 1: [B][2] o, c.  GRU: [B][2] r, u after the gates call, [B][1] after the update call).  dy rows are
+// written whole: pad channels zero.  Parameter gradients may be NULL (not wanted); accumulate adds into them.
+size_t convlstm_stats_offset(int B, int HW, int F, int which);
+size_t convgru_stats_offset(int B, int HW, int F);
+size_t convlstm_backward_workspace_bytes(int B, int HW, int F, bool normalize, bool peephole);
+size_t convgru_backward_workspace_bytes(int B, int HW, int F, bool normalize);
+hipError_t launch_convlstm_gates_backward(const float *y, int ys, const float *c, const float *wci, const float *wcf, const float *wco,
+                                          const float *gamma, const float *beta, const float *stats_jif, const float *stats_oc, const float *dh,
+                                          int dhs, const float *dc_new, int B, int HW, int F, float forget_bias, int act, bool normalize,
+                                          bool peephole, float *dy, int dys, float *dc, float *dwci, float *dwcf, float *dwco, float *dgamma,
+                                          float *dbeta, int accumulate, void *workspace, hipStream_t stream);
+hipError_t launch_convgru_update_backward(const float *y2, int ys, const float *h, int hs, const float *u, const float *gamma, const float *beta,
+                                          const float *stats, const float *dh_new, int dhns, int B, int HW, int F, int act, bool normalize,
+                                          float *dy2, int dys, float *du, float *dh, int dhs, float *dgamma, float *dbeta, int accumulate,
+                                          void *workspace, hipStream_t stream);
+hipError_t launch_convgru_gates_backward(const float *y, int ys, const float *h, int hs, const float *gamma, const float *beta, const float *stats,
+                                         const float *du, const float *drh, int drhs, int B, int HW, int F, bool normalize, float *dy, int dys,
+                                         float *dh, int dhs, float *dgamma, float *dbeta, int accumulate, void *workspace, hipStream_t stream);
 
 // dense-flow homography fit + cv2.warpPerspective on 8-bit frames (homography_ops.hip)
 int homography_moment_blocks(int H, int W);

@@ -513,7 +513,7 @@ VSTAB_API int vstab_ssim_backward(const float *img1, const float *img2, int B, i
 VSTAB_API int vstab_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, void *stream);
 VSTAB_API int vstab_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, void *stream);
 
-/* The recurrent cells of cell.py (ConvLSTMCell :5-76, ConvGRUCell :78-136), forward only: what follows each cell's SAME convolution
+/* The recurrent cells of cell.py (ConvLSTMCell :5-76, ConvGRUCell :78-136), forward (backward: next block): what follows each cell's SAME convolution
  * over concat([x, h]) -- that convolution is vstab_conv_forward on the caller's concat buffer.  y: the convolution's output
  * [B,H,W,ys] (ys >= the gate channels; rows may be padded); states [B,H,W,F] contiguous, or slices of a wider NHWC buffer given as
  * the address of the slice's first channel in pixel 0 plus the buffer's channel stride.  act: 0 tanh, 1 relu, 2 identity.
@@ -543,6 +543,46 @@ VSTAB_API int vstab_convgru_gates(const float *y, int ys, const float *h, int hs
 VSTAB_API int vstab_convgru_update(const float *y2, int ys, const float *h, int hs, const float *u, const float *gamma, const float *beta, int B,
                                    int H, int W, int F, int act, int normalize, float *h_out, float *h_new, int hns, void *workspace,
                                    size_t workspace_bytes, void *stream);
+/* The backward of the three stages above: gradients with respect to the convolution output(s), the old state and the stage's own
+ * parameters; the convolutions' own gradients are vstab_conv_wgrad / vstab_conv_dgrad on the caller's concat buffer.  Gate values are
+ * recomputed from y, the old state and the forward's per-sample {mean, rstd} pairs, which the forward call left in ITS workspace at
+ * *_stats_offset() bytes (0: bad shape): LSTM which = 0: [B][3] pairs of j, i, f, which = 1: [B][2] of o, c';  GRU: [B][2] (r, u) after
+ * vstab_convgru_gates, [B][1] after vstab_convgru_update (the same place: copy the first before the second call).  NULL without
+ * normalize.  Layer-norm adjoint, per sample over the N = H*W*F numbers of a gate, xhat = (v - mean) rstd, g = dout gamma[ch]:
+ * dv = rstd (g - mean_N(g) - xhat mean_N(g xhat)), dgamma[ch] = sum_{b,pixel} dout xhat, dbeta[ch] = sum_{b,pixel} dout.
+ * Same index space and guarantees as the forward: every reduction is combined in double in a fixed order, no atomics, two runs
+ * give the same bits, and a sample's dy / state gradients depend on that sample only.  dy rows [B,H,W,dys] are written whole (pad
+ * channels zero).  Parameter gradients may be NULL (not wanted; the three peephole gradients go together, as do dgamma and dbeta);
+ * accumulate != 0 adds into them (BPTT: t = T-1 down to 0).  Errors as the forward's; a workspace of *_backward_workspace_bytes()
+ * (which may be 0: then NULL is allowed) is needed whatever gradients are wanted.
+ *
+ * LSTM: dh (slice: pointer + stride dhs) and dc_new [B,H,W,F] are the gradients of the returned h' and c' (either may be NULL = zero).
+ * do_n = dh act(c_n) sigmoid'(o_n), dc_n = dc_new + dh sigmoid(o_n) act'(c_n); through LN_3 / LN_4; dc_raw += w_co do_raw;
+ * df = dc_raw c, di = dc_raw act(j), dj = dc_raw i act'(j), dc = dc_raw f; through the sigmoids and LN_0..2; dc += w_ci di + w_cf df.
+ * dy = [dj, di, df, do]; dc [B,H,W,F]; dw_ci, dw_cf, dw_co [H,W,F] = sum_b of di c, df c, do c_raw; dgamma, dbeta [5][F].
+ * Launches with normalize: pass, sums, pass, sums, pass (+ the parameter reductions); 1 without. */
+VSTAB_API size_t vstab_convlstm_gates_stats_offset(int B, int H, int W, int F, int which);
+VSTAB_API size_t vstab_convlstm_gates_backward_workspace_bytes(int B, int H, int W, int F, int normalize, int peephole);
+VSTAB_API int vstab_convlstm_gates_backward(const float *y, int ys, const float *c, const float *w_ci, const float *w_cf, const float *w_co,
+                                            const float *gamma, const float *beta, const float *stats_jif, const float *stats_oc,
+                                            const float *dh, int dhs, const float *dc_new, int B, int H, int W, int F, float forget_bias, int act,
+                                            int normalize, int peephole, float *dy, int dys, float *dc, float *dw_ci, float *dw_cf,
+                                            float *dw_co, float *dgamma, float *dbeta, int accumulate, void *workspace, size_t workspace_bytes,
+                                            void *stream);
+/* GRU update: from dh_new (slice) du [B,H,W,F] = dh_new (h - act(y2_n)), dy2 = dh_new (1 - u) act'(y2_n) through the candidate's layer
+ * norm, dh (slice, WRITTEN) = dh_new u; dgamma, dbeta [F].
+ * GRU gates: from du and drh (slice: the r h part of the candidate convolution's input gradient) dr = drh h, dh (slice) += drh r,
+ * through both sigmoids and layer norms to dy = [dr, du]; dgamma, dbeta [2][F].  One workspace serves both calls. */
+VSTAB_API size_t vstab_convgru_stats_offset(int B, int H, int W, int F);
+VSTAB_API size_t vstab_convgru_backward_workspace_bytes(int B, int H, int W, int F, int normalize);
+VSTAB_API int vstab_convgru_update_backward(const float *y2, int ys, const float *h, int hs, const float *u, const float *gamma, const float *beta,
+                                            const float *stats, const float *dh_new, int dhns, int B, int H, int W, int F, int act, int normalize,
+                                            float *dy2, int dys, float *du, float *dh, int dhs, float *dgamma, float *dbeta, int accumulate,
+                                            void *workspace, size_t workspace_bytes, void *stream);
+VSTAB_API int vstab_convgru_gates_backward(const float *y, int ys, const float *h, int hs, const float *gamma, const float *beta, const float *stats,
+                                           const float *du, const float *drh, int drhs, int B, int H, int W, int F, int normalize, float *dy, int dys,
+                                           float *dh, int dhs, float *dgamma, float *dbeta, int accumulate, void *workspace,
+                                           size_t workspace_bytes, void *stream);
 
 /* Weight and bias gradient of PadLayer(pad) -> Conv2d(k, stride, VALID) (model.py:807-844; what tf.gradients yields for
  * the filter of tf.nn.conv2d): dW[ky,kx,ci,co] = sum_{n,oy,ox} x[n, s*oy+ky-pad, s*ox+kx-pad, ci] * gout[n,oy,ox,co] in the
