@@ -87,6 +87,13 @@ def backward_rows(img, th6, out_size, iters, warmup):
 
     us = time_interleaved({"d_img": run_tps(True, False), "d_theta": run_tps(False, True), "both": run_tps(True, True)}, iters, warmup)
     rows.update({f"elastic_g4_{k}": {"us": round(v, 1), "alg_bytes": int(nbytes[k] * npix)} for k, v in us.items()})
+
+    # the affine transformer's bicubic sampler: the same algorithmic bytes (16 taps per pixel instead of 4 come from the caches)
+    def run_bc(need_img, need_theta):
+        return lambda: training.st_transform_backward(img, th6, dout, out_size, need_img=need_img, need_theta=need_theta, interp='bicubic')
+
+    us = time_interleaved({"d_img": run_bc(True, False), "d_theta": run_bc(False, True), "both": run_bc(True, True)}, iters, warmup)
+    rows.update({f"bicubic_{k}": {"us": round(v, 1), "alg_bytes": int(nbytes[k] * npix)} for k, v in us.items()})
     # warp.py's homography warp (plain form): M = the canonical-to-pixel map of the frame times a near-identity homography; the
     # same bytes per pixel as the affine rows
     ref = torch.tensor([[(W - 1) / 2, 0.0, (W - 1) / 2], [0.0, (H - 1) / 2, (H - 1) / 2], [0.0, 0.0, 1.0]])
@@ -143,7 +150,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", default="", help="comma-separated variant names (default: all)")
-    ap.add_argument("--backward", action="store_true", help="add the gradients of the affine and the elastic (g = 4) bilinear transformers (rows 'backward')")
+    ap.add_argument("--backward", action="store_true", help="add the gradients of the affine (bilinear and bicubic) and the elastic (g = 4) transformers (rows 'backward')")
     ap.add_argument("--volume", action="store_true", help="add the 3-D volume transformer at B = 4, 256^3, C = 1 (rows 'volume')")
     args = ap.parse_args()
     if args.iters < 20:

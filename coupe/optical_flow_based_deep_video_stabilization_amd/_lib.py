@@ -72,6 +72,16 @@ EXPORTS = {
     "vstab_st_symmetry_transform_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "vstab_st_symmetry_transform_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # the bicubic sampler's backward, and the three backwards above with a choice of sampler (`interp` after theta_dim | kind | linv_t)
+    "vstab_st_bicubic_interp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_st_transform_interp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_st_symmetry_transform_interp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                             C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_st_elastic_transform_interp_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                            C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                            C.c_void_p]),
     "vstab_st3d_meshgrid": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "vstab_st3d_bilinear_interp": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "vstab_st3d_transform": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),

@@ -379,21 +379,52 @@ extern "C" size_t vstab_st_transform_backward_workspace_bytes(int B, int H, int 
     return st_transform_backward_ws_bytes(B, H, W, C, oh, ow);
 }
 
+static bool interp_ok(int interp) { return interp == VSTAB_INTERP_BILINEAR || interp == VSTAB_INTERP_BICUBIC; }
+
+// One set of checks, in one order, for an entry point and its _interp_ form (`name` is the one called): the backward of either sampler
+static int st_transform_backward_checked(const char *name, const float *img, int B, int H, int W, int C, const float *theta, int theta_dim,
+                                         int interp, const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
+                                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!img || !theta || !dout) return fail(nullptr, VSTAB_E_STATE, "%s: NULL buffer", name);
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL || (theta_dim != 6 && theta_dim != 8))
+        return fail(nullptr, VSTAB_E_SHAPE, "%s: bad shape (theta must be [B,6] or [B,8], B <= 65535)", name);
+    if (!interp_ok(interp)) return fail(nullptr, VSTAB_E_SHAPE, "%s: unknown interp %d", name, interp);
+    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "%s: d_img and d_theta are both NULL", name);
+    if (d_theta) {
+        const size_t need = st_transform_backward_ws_bytes(B, H, W, C, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "%s: workspace needs %zu bytes", name, need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "%s: workspace must be 8-byte aligned", name);
+    }
+    HIP_TRY(nullptr, launch_st_transform_backward(img, B, H, W, C, theta, theta_dim, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
+                                                  (double *)workspace, (hipStream_t)stream, interp));
+    return VSTAB_OK;
+}
+
 extern "C" int vstab_st_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim, const float *dout,
                                            int oh, int ow, float *d_img, int accumulate, float *d_theta, void *workspace,
                                            size_t workspace_bytes, void *stream)
 {
-    if (!img || !theta || !dout) return fail(nullptr, VSTAB_E_STATE, "st_transform_backward: NULL buffer");
-    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL || (theta_dim != 6 && theta_dim != 8))
-        return fail(nullptr, VSTAB_E_SHAPE, "st_transform_backward: bad shape (theta must be [B,6] or [B,8], B <= 65535)");
-    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "st_transform_backward: d_img and d_theta are both NULL");
-    if (d_theta) {
-        const size_t need = st_transform_backward_ws_bytes(B, H, W, C, oh, ow);
-        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "st_transform_backward: workspace needs %zu bytes", need);
-        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "st_transform_backward: workspace must be 8-byte aligned");
-    }
-    HIP_TRY(nullptr, launch_st_transform_backward(img, B, H, W, C, theta, theta_dim, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
-                                                  (double *)workspace, (hipStream_t)stream));
+    return st_transform_backward_checked("st_transform_backward", img, B, H, W, C, theta, theta_dim, VSTAB_INTERP_BILINEAR, dout, oh, ow, d_img,
+                                         accumulate, d_theta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vstab_st_transform_interp_backward(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim, int interp,
+                                                  const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
+                                                  void *workspace, size_t workspace_bytes, void *stream)
+{
+    return st_transform_backward_checked("st_transform_interp_backward", img, B, H, W, C, theta, theta_dim, interp, dout, oh, ow, d_img,
+                                         accumulate, d_theta, workspace, workspace_bytes, stream);
+}
+
+static int st_interp_backward_checked(const char *name, int interp, const float *img, int B, int H, int W, int C, const float *x, const float *y,
+                                      const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x, float *d_y, void *stream)
+{
+    if (!img || !x || !y || !dout) return fail(nullptr, VSTAB_E_STATE, "%s: NULL buffer", name);
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL)
+        return fail(nullptr, VSTAB_E_SHAPE, "%s: bad shape (B <= 65535)", name);
+    if (!d_img && !d_x && !d_y) return fail(nullptr, VSTAB_E_SHAPE, "%s: d_img, d_x and d_y are all NULL", name);
+    HIP_TRY(nullptr, launch_st_interp_backward(img, B, H, W, C, x, y, dout, oh, ow, d_img, accumulate ? 1 : 0, d_x, d_y, (hipStream_t)stream, interp));
     return VSTAB_OK;
 }
 
@@ -401,12 +432,16 @@ extern "C" int vstab_st_bilinear_interp_backward(const float *img, int B, int H,
                                                  const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x, float *d_y,
                                                  void *stream)
 {
-    if (!img || !x || !y || !dout) return fail(nullptr, VSTAB_E_STATE, "st_bilinear_interp_backward: NULL buffer");
-    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL)
-        return fail(nullptr, VSTAB_E_SHAPE, "st_bilinear_interp_backward: bad shape (B <= 65535)");
-    if (!d_img && !d_x && !d_y) return fail(nullptr, VSTAB_E_SHAPE, "st_bilinear_interp_backward: d_img, d_x and d_y are all NULL");
-    HIP_TRY(nullptr, launch_st_interp_backward(img, B, H, W, C, x, y, dout, oh, ow, d_img, accumulate ? 1 : 0, d_x, d_y, (hipStream_t)stream));
-    return VSTAB_OK;
+    return st_interp_backward_checked("st_bilinear_interp_backward", VSTAB_INTERP_BILINEAR, img, B, H, W, C, x, y, dout, oh, ow, d_img, accumulate,
+                                      d_x, d_y, stream);
+}
+
+extern "C" int vstab_st_bicubic_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y,
+                                                const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x, float *d_y,
+                                                void *stream)
+{
+    return st_interp_backward_checked("st_bicubic_interp_backward", VSTAB_INTERP_BICUBIC, img, B, H, W, C, x, y, dout, oh, ow, d_img, accumulate,
+                                      d_x, d_y, stream);
 }
 
 // ---- ElasticTransformer: the coordinates the forward samples at, and the backward of its bilinear sampler
@@ -428,22 +463,39 @@ extern "C" size_t vstab_st_elastic_transform_backward_workspace_bytes(int B, int
     return st_elastic_backward_ws_bytes(B, H, W, C, g, oh, ow);
 }
 
+static int st_elastic_backward_checked(const char *name, const float *img, int B, int H, int W, int C, const float *theta, int g,
+                                       const float *linv_t, int interp, const float *dout, int oh, int ow, float *d_img, int accumulate,
+                                       float *d_theta, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!img || !theta || !linv_t || !dout) return fail(nullptr, VSTAB_E_STATE, "%s: NULL buffer", name);
+    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL || !tps_g_ok(g))
+        return fail(nullptr, VSTAB_E_SHAPE, "%s: bad shape (B <= 65535, grid side must be in [2, %d])", name, VSTAB_TPS_GMAX);
+    if (!interp_ok(interp)) return fail(nullptr, VSTAB_E_SHAPE, "%s: unknown interp %d", name, interp);
+    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "%s: d_img and d_theta are both NULL", name);
+    if (d_theta) {
+        const size_t need = st_elastic_backward_ws_bytes(B, H, W, C, g, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "%s: workspace needs %zu bytes", name, need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "%s: workspace must be 8-byte aligned", name);
+    }
+    HIP_TRY(nullptr, launch_st_elastic_transform_backward(img, B, H, W, C, theta, g, linv_t, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
+                                                          (double *)workspace, (hipStream_t)stream, interp));
+    return VSTAB_OK;
+}
+
 extern "C" int vstab_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                                    const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
                                                    void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!img || !theta || !linv_t || !dout) return fail(nullptr, VSTAB_E_STATE, "st_elastic_transform_backward: NULL buffer");
-    if (!stx_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL || !tps_g_ok(g))
-        return fail(nullptr, VSTAB_E_SHAPE, "st_elastic_transform_backward: bad shape (B <= 65535, grid side must be in [2, %d])", VSTAB_TPS_GMAX);
-    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "st_elastic_transform_backward: d_img and d_theta are both NULL");
-    if (d_theta) {
-        const size_t need = st_elastic_backward_ws_bytes(B, H, W, C, g, oh, ow);
-        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "st_elastic_transform_backward: workspace needs %zu bytes", need);
-        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "st_elastic_transform_backward: workspace must be 8-byte aligned");
-    }
-    HIP_TRY(nullptr, launch_st_elastic_transform_backward(img, B, H, W, C, theta, g, linv_t, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
-                                                          (double *)workspace, (hipStream_t)stream));
-    return VSTAB_OK;
+    return st_elastic_backward_checked("st_elastic_transform_backward", img, B, H, W, C, theta, g, linv_t, VSTAB_INTERP_BILINEAR, dout, oh, ow,
+                                       d_img, accumulate, d_theta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vstab_st_elastic_transform_interp_backward(const float *img, int B, int H, int W, int C, const float *theta, int g,
+                                                          const float *linv_t, int interp, const float *dout, int oh, int ow, float *d_img,
+                                                          int accumulate, float *d_theta, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return st_elastic_backward_checked("st_elastic_transform_interp_backward", img, B, H, W, C, theta, g, linv_t, interp, dout, oh, ow, d_img,
+                                       accumulate, d_theta, workspace, workspace_bytes, stream);
 }
 
 // ---- the symmetric-pad transformers: the matrices and coordinates the forward uses, and the backward of their bilinear sampler
@@ -479,25 +531,42 @@ extern "C" size_t vstab_st_symmetry_transform_backward_workspace_bytes(int B, in
     return st_symmetry_backward_ws_bytes(B, H, W, C, oh, ow);
 }
 
+static int st_symmetry_backward_checked(const char *name, const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
+                                        const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta, void *workspace,
+                                        size_t workspace_bytes, void *stream)
+{
+    if (!img || !theta || !dout) return fail(nullptr, VSTAB_E_STATE, "%s: NULL buffer", name);
+    if (!sym_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL)
+        return fail(nullptr, VSTAB_E_SHAPE, "%s: bad shape (B <= 65535)", name);
+    if (H < 100 || W < 100)
+        return fail(nullptr, VSTAB_E_SHAPE, "%s: the 100-pixel symmetric pad needs H, W >= 100 (got %dx%d)", name, H, W);
+    if (!sym_kind_ok(kind)) return fail(nullptr, VSTAB_E_SHAPE, "%s: unknown kind %d", name, kind);
+    if (!interp_ok(interp)) return fail(nullptr, VSTAB_E_SHAPE, "%s: unknown interp %d", name, interp);
+    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "%s: d_img and d_theta are both NULL", name);
+    if (d_theta) {
+        const size_t need = st_symmetry_backward_ws_bytes(B, H, W, C, oh, ow);
+        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "%s: workspace needs %zu bytes", name, need);
+        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "%s: workspace must be 8-byte aligned", name);
+    }
+    HIP_TRY(nullptr, launch_st_symmetry_transform_backward(img, B, H, W, C, theta, kind, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
+                                                           (double *)workspace, (hipStream_t)stream, interp));
+    return VSTAB_OK;
+}
+
 extern "C" int vstab_st_symmetry_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind, const float *dout,
                                                     int oh, int ow, float *d_img, int accumulate, float *d_theta, void *workspace,
                                                     size_t workspace_bytes, void *stream)
 {
-    if (!img || !theta || !dout) return fail(nullptr, VSTAB_E_STATE, "st_symmetry_transform_backward: NULL buffer");
-    if (!sym_shape_ok(B, H, W, C, oh, ow) || (long long)B * H * W * C > 0x7fffffffLL)
-        return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: bad shape (B <= 65535)");
-    if (H < 100 || W < 100)
-        return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: the 100-pixel symmetric pad needs H, W >= 100 (got %dx%d)", H, W);
-    if (!sym_kind_ok(kind)) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: unknown kind %d", kind);
-    if (!d_img && !d_theta) return fail(nullptr, VSTAB_E_SHAPE, "st_symmetry_transform_backward: d_img and d_theta are both NULL");
-    if (d_theta) {
-        const size_t need = st_symmetry_backward_ws_bytes(B, H, W, C, oh, ow);
-        if (!workspace || workspace_bytes < need) return fail(nullptr, VSTAB_E_NOMEM, "st_symmetry_transform_backward: workspace needs %zu bytes", need);
-        if ((uintptr_t)workspace & 7) return fail(nullptr, VSTAB_E_ALIGN, "st_symmetry_transform_backward: workspace must be 8-byte aligned");
-    }
-    HIP_TRY(nullptr, launch_st_symmetry_transform_backward(img, B, H, W, C, theta, kind, dout, oh, ow, d_img, accumulate ? 1 : 0, d_theta,
-                                                           (double *)workspace, (hipStream_t)stream));
-    return VSTAB_OK;
+    return st_symmetry_backward_checked("st_symmetry_transform_backward", img, B, H, W, C, theta, kind, VSTAB_INTERP_BILINEAR, dout, oh, ow, d_img,
+                                        accumulate, d_theta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vstab_st_symmetry_transform_interp_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind, int interp,
+                                                           const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
+                                                           void *workspace, size_t workspace_bytes, void *stream)
+{
+    return st_symmetry_backward_checked("st_symmetry_transform_interp_backward", img, B, H, W, C, theta, kind, interp, dout, oh, ow, d_img,
+                                        accumulate, d_theta, workspace, workspace_bytes, stream);
 }
 
 // ---- the 3-D volume transformer (sampler3d_ops.hip).  The shape is judged before the pointers: a shape outside the contract is

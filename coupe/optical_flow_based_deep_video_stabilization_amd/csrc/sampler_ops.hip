@@ -6,7 +6,8 @@
 // function (st_axis in st_axis.h, st_taps, homog_taps, st_blend, cubic_axis, st_coords) that both kernels call.  The bilinear sampler of the theta,
 // explicit-coordinate, symmetric-pad and thin-plate-spline sources has a backward (st3_tile_bwd_kernel / st_pixel_bwd_kernel and, for the spline,
 // st3_tile_tps_bwd_kernel / st_pixel_tps_bwd_kernel, at the end of the file) that calls the same functions; its d img is summed by
-// float atomics and depends on their arrival order in its last bits, its d theta is reproducible.  The homography source has its own
+// float atomics and depends on their arrival order in its last bits, its d theta is reproducible.  The bicubic sampler of the same four
+// sources has its backward in the same kernels (INTERP = XI_BICUBIC: st_cubic_bwd_point / st3_cubic_bwd_point).  The homography source has its own
 // backward arithmetic (homog_bwd_point / homog3_bwd_point, d M [B,9]) on the same two kernel skeletons, and vec2mtrx its own kernel.
 // -ffp-contract=off keeps the weight arithmetic the reference's op-by-op fp32 sequence.
 #include "vstab_internal.h"
@@ -300,10 +301,14 @@ __device__ __forceinline__ void st_coords(const StSrc &S, const float *th, const
 
 // bicubic_interp's taps and weights along one axis (ST:988-1050): clip to [-1,1] first (NaN -> -1), scale, x0 = floor, taps in
 // the reference's order [x0, max(x0-1,0), min(x0+1,n-1), min(x0+2,n-1)] (edges replicate: no zero border), alpha = -0.75 weights
-// w_i = ((c_i0 + c_i1 t) + c_i2 t^2) + c_i3 t^3
-__device__ __forceinline__ void cubic_axis(float v, int n, int *ix, float *w)
+// w_i = ((c_i0 + c_i1 t) + c_i2 t^2) + c_i3 t^3.  DERIV (the backward): also the weights' derivatives in t from the same table,
+// w'_i = (c_i1 + 2 c_i2 t) + 3 c_i3 t^2 (t = v - floor(v) has derivative 1 in v), and whether the clip passes a gradient:
+// -1 <= v <= 1 inclusive, not for NaN -- st_axis_chain's convention for the bilinear clip.
+template <bool DERIV = false>
+__device__ __forceinline__ void cubic_axis(float v, int n, int *ix, float *w, float *dw = nullptr, bool *pass = nullptr)
 {
     const float nf = (float)n;
+    if (DERIV) *pass = v >= -1.0f && v <= 1.0f;
     v = fminf(fmaxf(v, -1.0f), 1.0f);
     v = (v + 1.0f) / 2.0f * (nf - 1.0f);
     const float v0f = floorf(v);
@@ -314,6 +319,12 @@ __device__ __forceinline__ void cubic_axis(float v, int n, int *ix, float *w)
     w[1] = ((0.0f + -0.75f * t) + 1.5f * t2) + -0.75f * t3;
     w[2] = ((0.0f + 0.75f * t) + 1.5f * t2) + -1.25f * t3;
     w[3] = ((0.0f + 0.0f * t) + -0.75f * t2) + 0.75f * t3;
+    if (DERIV) {
+        dw[0] = (0.0f + (2.0f * -2.25f) * t) + (3.0f * 1.25f) * t2;
+        dw[1] = (-0.75f + (2.0f * 1.5f) * t) + (3.0f * -0.75f) * t2;
+        dw[2] = (0.75f + (2.0f * 1.5f) * t) + (3.0f * -1.25f) * t2;
+        dw[3] = (0.0f + (2.0f * -0.75f) * t) + (3.0f * 0.75f) * t2;
+    }
 }
 
 struct Cubic { int x[4], y[4]; float wx[4], wy[4]; };
@@ -844,6 +855,117 @@ __device__ __forceinline__ void st3_bwd_point(const rgb3 *b, float *di, const rg
 }
 
 // ---------------------------------------------------------------------------------
+// Backward of the BICUBIC sampler (XI_BICUBIC) for the theta, explicit-coordinate, symmetric-pad and thin-plate-spline sources: what
+// TensorFlow's autodiff gives for ST:966-1072, out_c = sum_i sum_j wy_i wx_j I[ys_i, xs_j, c].  Taps and weights are cubic_axis's, the
+// forward's own, so every floor, clip and edge decision is shared.  One tap row at a time, so that no more than four taps are held:
+//   d img    the gather's adjoint, wx_j * (wy_i * dout_c) added to each of the 16 taps by float atomics (arrival order in the last
+//            bits).  The replicate-clamp folds several taps onto one edge pixel and all of them add: there is no zero border.  XS_SYM:
+//            the taps are the padded extent's (st_extent) mapped through st_src, as in the forward.
+//   d x, d y floor and the int casts have zero derivative, t = v - floor(v) has derivative 1: per channel d out / d x =
+//            sum_i wy_i (sum_j w'x_j I_ij), d out / d y = sum_i w'y_i (sum_j wx_j I_ij), each times dout, summed over the channels,
+//            times (W - 1) / 2 (H for y).  The clip to [-1,1] passes the gradient where -1 <= x <= 1 inclusive, 0 outside and for NaN
+//            (which the forward reads as -1): st_axis_chain's convention.
+// gxn, gyn feed each source's d theta chain unchanged (st_theta_accum, the symmetric-pad pre-map, the TPS coefficient sums).
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ float cubic_chain(bool pass, float g, int n) { return pass ? g * (((float)n - 1.0f) / 2.0f) : 0.0f; }
+
+// any channel count:
+template <bool DIMG, bool DCOORD, int SRC = XS_THETA>
+__device__ __forceinline__ void st_cubic_bwd_point(const float *__restrict__ b, float *di, const float *__restrict__ g, int H, int W, int C, float xs,
+                                                   float ys, float &gxn, float &gyn)
+{
+    Cubic q;
+    float dwx[4], dwy[4];
+    bool px = false, py = false;
+    cubic_axis<DCOORD>(xs, st_extent<SRC>(W), q.x, q.wx, dwx, &px);
+    cubic_axis<DCOORD>(ys, st_extent<SRC>(H), q.y, q.wy, dwy, &py);
+    long long row[4], col[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { row[i] = (long long)st_src<SRC>(q.y[i], H) * W; col[i] = st_src<SRC>(q.x[i], W); }
+    float gx = 0.f, gy = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float gc = g[c];
+        float sx = 0.f, sy = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long i0 = (row[i] + col[0]) * C + c, i1 = (row[i] + col[1]) * C + c, i2 = (row[i] + col[2]) * C + c, i3 = (row[i] + col[3]) * C + c;
+            if (DCOORD) {
+                const float I0 = b[i0], I1 = b[i1], I2 = b[i2], I3 = b[i3];
+                const float r = ((q.wx[0] * I0 + q.wx[1] * I1) + q.wx[2] * I2) + q.wx[3] * I3;
+                const float d = ((dwx[0] * I0 + dwx[1] * I1) + dwx[2] * I2) + dwx[3] * I3;
+                sx = sx + q.wy[i] * d;
+                sy = sy + dwy[i] * r;
+            }
+            if (DIMG) {
+                const float wg = q.wy[i] * gc;
+                atomicAdd(di + i0, q.wx[0] * wg); atomicAdd(di + i1, q.wx[1] * wg);
+                atomicAdd(di + i2, q.wx[2] * wg); atomicAdd(di + i3, q.wx[3] * wg);
+            }
+        }
+        gx = gx + sx * gc;
+        gy = gy + sy * gc;
+    }
+    gxn = DCOORD ? cubic_chain(px, gx, st_extent<SRC>(W)) : 0.0f;
+    gyn = DCOORD ? cubic_chain(py, gy, st_extent<SRC>(H)) : 0.0f;
+}
+
+// 3-channel frames (3 H W < 2^31: host): the same sums in the same order, a tap read as one 3-dword load
+template <bool DIMG, bool DCOORD, int SRC = XS_THETA>
+__device__ __forceinline__ void st3_cubic_bwd_point(const rgb3 *b, float *di, const rgb3 g, int H, int W, float xs, float ys, float &gxn, float &gyn)
+{
+    Cubic q;
+    float dwx[4], dwy[4];
+    bool px = false, py = false;
+    cubic_axis<DCOORD>(xs, st_extent<SRC>(W), q.x, q.wx, dwx, &px);
+    cubic_axis<DCOORD>(ys, st_extent<SRC>(H), q.y, q.wy, dwy, &py);
+    int col[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) col[j] = st_src<SRC>(q.x[j], W);
+    rgb3 sx = {0.f, 0.f, 0.f}, sy = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int ro = st_src<SRC>(q.y[i], H) * W;
+        if (DCOORD) {
+            const rgb3 I0 = b[ro + col[0]], I1 = b[ro + col[1]], I2 = b[ro + col[2]], I3 = b[ro + col[3]];
+            sx.r = sx.r + q.wy[i] * (((dwx[0] * I0.r + dwx[1] * I1.r) + dwx[2] * I2.r) + dwx[3] * I3.r);
+            sx.g = sx.g + q.wy[i] * (((dwx[0] * I0.g + dwx[1] * I1.g) + dwx[2] * I2.g) + dwx[3] * I3.g);
+            sx.b = sx.b + q.wy[i] * (((dwx[0] * I0.b + dwx[1] * I1.b) + dwx[2] * I2.b) + dwx[3] * I3.b);
+            sy.r = sy.r + dwy[i] * (((q.wx[0] * I0.r + q.wx[1] * I1.r) + q.wx[2] * I2.r) + q.wx[3] * I3.r);
+            sy.g = sy.g + dwy[i] * (((q.wx[0] * I0.g + q.wx[1] * I1.g) + q.wx[2] * I2.g) + q.wx[3] * I3.g);
+            sy.b = sy.b + dwy[i] * (((q.wx[0] * I0.b + q.wx[1] * I1.b) + q.wx[2] * I2.b) + q.wx[3] * I3.b);
+        }
+        if (DIMG) {
+            const float wr = q.wy[i] * g.r, wg = q.wy[i] * g.g, wb = q.wy[i] * g.b;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float *p = di + ((long long)ro + col[j]) * 3;
+                atomicAdd(p, q.wx[j] * wr); atomicAdd(p + 1, q.wx[j] * wg); atomicAdd(p + 2, q.wx[j] * wb);
+            }
+        }
+    }
+    gxn = gyn = 0.0f;
+    if (DCOORD) {
+        const float gx = (sx.r * g.r + sx.g * g.g) + sx.b * g.b, gy = (sy.r * g.r + sy.g * g.g) + sy.b * g.b;
+        gxn = cubic_chain(px, gx, st_extent<SRC>(W)); gyn = cubic_chain(py, gy, st_extent<SRC>(H));
+    }
+}
+
+// a pixel's backward with the sampler of the launch
+template <bool DIMG, bool DCOORD, int SRC, int INTERP>
+__device__ __forceinline__ void st_point_bwd(const float *__restrict__ b, float *di, const float *__restrict__ g, int H, int W, int C, float xs, float ys,
+                                             float &gxn, float &gyn)
+{
+    if (INTERP == XI_BICUBIC) st_cubic_bwd_point<DIMG, DCOORD, SRC>(b, di, g, H, W, C, xs, ys, gxn, gyn);
+    else st_bwd_point<DIMG, DCOORD, SRC>(b, di, g, H, W, C, xs, ys, gxn, gyn);
+}
+template <bool DIMG, bool DCOORD, int SRC, int INTERP>
+__device__ __forceinline__ void st3_point_bwd(const rgb3 *b, float *di, const rgb3 g, int H, int W, float xs, float ys, float &gxn, float &gyn)
+{
+    if (INTERP == XI_BICUBIC) st3_cubic_bwd_point<DIMG, DCOORD, SRC>(b, di, g, H, W, xs, ys, gxn, gyn);
+    else st3_bwd_point<DIMG, DCOORD, SRC>(b, di, g, H, W, xs, ys, gxn, gyn);
+}
+
+// ---------------------------------------------------------------------------------
 // Backward of XS_HOMOG (warp.transformImage / transformCropImage / warpImage): what TensorFlow's autodiff gives for warp.py:46-86 and
 // 89-129.  The coordinates and taps are homog_coords / homog_taps, the forward's, so every floor, ceil and inside decision is shared.
 // floor, ceil and to_int32 have zero derivative and there is no clip: with xr = xw - floor(xw), yr likewise, per channel
@@ -931,7 +1053,7 @@ template <int SRC>
 constexpr int st_part_width() { return SRC == XS_HOMOG ? 9 : 8; }
 
 // any channel count, one thread per pixel (st_pixel_kernel's layout); d img the plain way
-template <int SRC, bool DIMG, bool DCOORD>
+template <int SRC, bool DIMG, bool DCOORD, int INTERP = XI_BILINEAR>
 __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restrict__ img, int H, int W, int C, StSrc S, StBwd G, int FH, int FW, unsigned bps)
 {
     constexpr int NP = st_part_width<SRC>();
@@ -959,8 +1081,8 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
             float xs, ys, xh, yh, zs, gxn, gyn;
             const float xt = st_grid_t(gx, S.sx), yt = st_grid_t(gy, S.sy);
             st_sym_coords(th, S.kind == 1, xt, yt, xh, yh, zs, xs, ys);
-            st_bwd_point<DIMG, DCOORD, SRC>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
-                                            G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
+            st_point_bwd<DIMG, DCOORD, SRC, INTERP>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
+                                                    G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
             if (DCOORD) st_theta_accum(acc, S.tdim, gxn, gyn, xt, yt, xh, yh, zs);          // S.tdim: 8 projective, 6 otherwise (host)
         }
     } else if (ok) {
@@ -970,8 +1092,8 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
         if (SRC == XS_THETA) st_theta_coords(th, S.tdim, xt, yt, xh, yh, zs, xs, ys);
         else st_coords<SRC>(S, th, nullptr, n, fx, fy, xs, ys);
         float gxn, gyn;
-        st_bwd_point<DIMG, DCOORD>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
-                                   G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
+        st_point_bwd<DIMG, DCOORD, XS_THETA, INTERP>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
+                                                     G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
         if (DCOORD) {
             if (SRC == XS_COORDS) {
                 if (G.d_x) G.d_x[(long long)n * FH * FW + p] = gxn;
@@ -985,7 +1107,7 @@ __global__ __launch_bounds__(256) void st_pixel_bwd_kernel(const float *__restri
 }
 
 // 3-channel frames on the tile skeleton (st3_tile_kernel's pixels: a wave instruction works on a 4 x 16 patch)
-template <int SRC, bool DIMG, bool DCOORD>
+template <int SRC, bool DIMG, bool DCOORD, int INTERP = XI_BILINEAR>
 __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restrict__ img, int H, int W, StSrc S, StBwd G, int FH, int FW,
                                                            int tiles_x, int tiles_y)
 {
@@ -1018,7 +1140,7 @@ __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restri
             float xs, ys, xh, yh, zs, gxn, gyn;
             const float xt = st_grid_t(gx, S.sx), yt = st_grid_t(gy, S.sy);
             st_sym_coords(th, S.kind == 1, xt, yt, xh, yh, zs, xs, ys);
-            st3_bwd_point<DIMG, DCOORD, SRC>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[((long long)n * FH + fy) * FW + fx], H, W, xs, ys, gxn, gyn);
+            st3_point_bwd<DIMG, DCOORD, SRC, INTERP>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[((long long)n * FH + fy) * FW + fx], H, W, xs, ys, gxn, gyn);
             if (DCOORD) st_theta_accum(acc, S.tdim, gxn, gyn, xt, yt, xh, yh, zs);          // S.tdim: 8 projective, 6 otherwise (host)
             continue;
         }
@@ -1028,7 +1150,7 @@ __global__ __launch_bounds__(256) void st3_tile_bwd_kernel(const float *__restri
         else st_coords<SRC>(S, th, nullptr, n, fx, fy, xs, ys);
         const long long po = ((long long)n * FH + fy) * FW + fx;
         float gxn, gyn;
-        st3_bwd_point<DIMG, DCOORD>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[po], H, W, xs, ys, gxn, gyn);
+        st3_point_bwd<DIMG, DCOORD, XS_THETA, INTERP>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[po], H, W, xs, ys, gxn, gyn);
         if (DCOORD) {
             if (SRC == XS_COORDS) {
                 if (G.d_x) G.d_x[po] = gxn;
@@ -1065,7 +1187,7 @@ size_t st_transform_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow
     return (size_t)wgs * B * 8 * sizeof(double);
 }
 
-template <int SRC>
+template <int SRC, int INTERP = XI_BILINEAR>
 static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, StSrc S, StBwd G, int FH, int FW, hipStream_t stream)
 {
     S.B = B;
@@ -1076,7 +1198,7 @@ static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, St
     dim3 grid;
     long long wgs;
     if (st_bwd_plan(B, H, W, C, FH, FW, tx, ty, grid, wgs)) {
-#define ST_BWD_TILE(D, K) st3_tile_bwd_kernel<SRC, D, K><<<grid, dim3(256), 0, stream>>>(img, H, W, S, G, FH, FW, tx, ty)
+#define ST_BWD_TILE(D, K) st3_tile_bwd_kernel<SRC, D, K, INTERP><<<grid, dim3(256), 0, stream>>>(img, H, W, S, G, FH, FW, tx, ty)
         if (dimg && dcoord) ST_BWD_TILE(true, true);
         else if (dimg) ST_BWD_TILE(true, false);
         else ST_BWD_TILE(false, true);
@@ -1085,7 +1207,7 @@ static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, St
     }
     if (wgs * B >= (1ll << 31)) return hipErrorInvalidValue;
     const dim3 pgrid((unsigned)(wgs * B));
-#define ST_BWD_PIXEL(D, K) st_pixel_bwd_kernel<SRC, D, K><<<pgrid, dim3(256), 0, stream>>>(img, H, W, C, S, G, FH, FW, (unsigned)wgs)
+#define ST_BWD_PIXEL(D, K) st_pixel_bwd_kernel<SRC, D, K, INTERP><<<pgrid, dim3(256), 0, stream>>>(img, H, W, C, S, G, FH, FW, (unsigned)wgs)
     if (dimg && dcoord) ST_BWD_PIXEL(true, true);
     else if (dimg) ST_BWD_PIXEL(true, false);
     else ST_BWD_PIXEL(false, true);
@@ -1094,7 +1216,7 @@ static hipError_t launch_st_bwd(const float *img, int B, int H, int W, int C, St
 }
 
 hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int tdim, const float *dout, int oh,
-                                        int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream)
+                                        int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream, int interp)
 {
     if (d_img && !accumulate) {
         const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
@@ -1103,7 +1225,8 @@ hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, i
     StSrc S = st_plain(oh, ow);
     S.theta = theta; S.tdim = tdim;
     StBwd G{dout, d_img, nullptr, nullptr, d_theta ? part : nullptr};
-    const hipError_t e = launch_st_bwd<XS_THETA>(img, B, H, W, C, S, G, oh, ow, stream);
+    const hipError_t e = interp == XI_BICUBIC ? launch_st_bwd<XS_THETA, XI_BICUBIC>(img, B, H, W, C, S, G, oh, ow, stream)
+                                              : launch_st_bwd<XS_THETA>(img, B, H, W, C, S, G, oh, ow, stream);
     if (e != hipSuccess || !d_theta) return e;
     int tx, ty;
     dim3 grid;
@@ -1114,7 +1237,7 @@ hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, i
 }
 
 hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y, const float *dout, int oh,
-                                     int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream)
+                                     int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream, int interp)
 {
     if (d_img && !accumulate) {
         const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
@@ -1123,6 +1246,7 @@ hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int 
     StSrc S = st_plain(oh, ow);
     S.x = x; S.y = y;
     StBwd G{dout, d_img, d_x, d_y, nullptr};
+    if (interp == XI_BICUBIC) return launch_st_bwd<XS_COORDS, XI_BICUBIC>(img, B, H, W, C, S, G, oh, ow, stream);
     return launch_st_bwd<XS_COORDS>(img, B, H, W, C, S, G, oh, ow, stream);
 }
 
@@ -1199,7 +1323,8 @@ size_t st_symmetry_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow)
 }
 
 hipError_t launch_st_symmetry_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind, const float *dout,
-                                                 int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream)
+                                                 int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream,
+                                                 int interp)
 {
     if (d_img && !accumulate) {
         const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
@@ -1208,7 +1333,8 @@ hipError_t launch_st_symmetry_transform_backward(const float *img, int B, int H,
     int th, tw;
     const StSrc S = st_sym_src(theta, kind, oh, ow, th, tw);
     StBwd G{dout, d_img, nullptr, nullptr, d_theta ? part : nullptr};
-    const hipError_t e = launch_st_bwd<XS_SYM>(img, B, H, W, C, S, G, th, tw, stream);
+    const hipError_t e = interp == XI_BICUBIC ? launch_st_bwd<XS_SYM, XI_BICUBIC>(img, B, H, W, C, S, G, th, tw, stream)
+                                              : launch_st_bwd<XS_SYM>(img, B, H, W, C, S, G, th, tw, stream);
     if (e != hipSuccess || !d_theta) return e;
     int tx, ty;
     dim3 grid;
@@ -1375,7 +1501,7 @@ __device__ __forceinline__ void st_tps_part(StTpsLds<P> &L, double *acc, double 
 }
 
 // any channel count: a step is a run of 256 pixels, one per thread
-template <bool DIMG, bool DTHETA>
+template <bool DIMG, bool DTHETA, int INTERP = XI_BILINEAR>
 __global__ __launch_bounds__(256) void st_pixel_tps_bwd_kernel(const float *__restrict__ img, int H, int W, int C, StSrc S, StTpsBwd G, int FH, int FW,
                                                                int steps)
 {
@@ -1393,8 +1519,8 @@ __global__ __launch_bounds__(256) void st_pixel_tps_bwd_kernel(const float *__re
             xt = st_grid_t(fx, S.sx); yt = st_grid_t(fy, S.sy);
             float xs, ys;
             st_coords<XS_TPS>(S, nullptr, L.cf, n, fx, fy, xs, ys);
-            st_bwd_point<DIMG, DTHETA>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
-                                       G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
+            st_point_bwd<DIMG, DTHETA, XS_TPS, INTERP>(img + (long long)n * H * W * C, DIMG ? G.d_img + (long long)n * H * W * C : nullptr,
+                                                       G.dout + ((long long)n * FH * FW + p) * C, H, W, C, xs, ys, gxn, gyn);
             if (DTHETA) st_theta_accum(acc, 6, gxn, gyn, xt, yt, 0.f, 0.f, 1.f);
         }
         if (DTHETA) {
@@ -1408,7 +1534,7 @@ __global__ __launch_bounds__(256) void st_pixel_tps_bwd_kernel(const float *__re
 }
 
 // 3-channel frames: a step is a tile of the tile skeleton (a wave instruction works on a 4 x 16 patch)
-template <bool DIMG, bool DTHETA>
+template <bool DIMG, bool DTHETA, int INTERP = XI_BILINEAR>
 __global__ __launch_bounds__(256) void st3_tile_tps_bwd_kernel(const float *__restrict__ img, int H, int W, StSrc S, StTpsBwd G, int FH, int FW,
                                                                int tiles_x, int tiles_y)
 {
@@ -1433,7 +1559,7 @@ __global__ __launch_bounds__(256) void st3_tile_tps_bwd_kernel(const float *__re
                 float xs, ys;
                 st_coords<XS_TPS>(S, nullptr, L.cf, n, fx, fy, xs, ys);
                 const long long po = ((long long)n * FH + fy) * FW + fx;
-                st3_bwd_point<DIMG, DTHETA>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[po], H, W, xs, ys, gxn, gyn);
+                st3_point_bwd<DIMG, DTHETA, XS_TPS, INTERP>(b, di, reinterpret_cast<const rgb3 *>(G.dout)[po], H, W, xs, ys, gxn, gyn);
                 if (DTHETA) st_theta_accum(acc, 6, gxn, gyn, xt, yt, 0.f, 0.f, 1.f);
             }
             if (DTHETA) L.px[tile.staged(j)] = f32x4{gxn, gyn, xt, yt};
@@ -1491,7 +1617,7 @@ size_t st_elastic_backward_ws_bytes(int B, int H, int W, int C, int g, int oh, i
 
 hipError_t launch_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part,
-                                                hipStream_t stream)
+                                                hipStream_t stream, int interp)
 {
     if (d_img && !accumulate) {
         const hipError_t e = hipMemsetAsync(d_img, 0, (size_t)B * H * W * C * sizeof(float), stream);
@@ -1506,13 +1632,21 @@ hipError_t launch_st_elastic_transform_backward(const float *img, int B, int H, 
     const bool dimg = d_img != nullptr, dtheta = d_theta != nullptr;
     const dim3 grid((unsigned)((long long)B * wps));
     if (tiled) {
-#define ST_TPS_TILE(D, T) st3_tile_tps_bwd_kernel<D, T><<<grid, dim3(256), 0, stream>>>(img, H, W, S, G, oh, ow, tx, ty)
+#define ST_TPS_TILE(D, T)                                                                                                            \
+    do {                                                                                                                             \
+        if (interp == XI_BICUBIC) st3_tile_tps_bwd_kernel<D, T, XI_BICUBIC><<<grid, dim3(256), 0, stream>>>(img, H, W, S, G, oh, ow, tx, ty); \
+        else st3_tile_tps_bwd_kernel<D, T><<<grid, dim3(256), 0, stream>>>(img, H, W, S, G, oh, ow, tx, ty);                         \
+    } while (0)
         if (dimg && dtheta) ST_TPS_TILE(true, true);
         else if (dimg) ST_TPS_TILE(true, false);
         else ST_TPS_TILE(false, true);
 #undef ST_TPS_TILE
     } else {
-#define ST_TPS_PIXEL(D, T) st_pixel_tps_bwd_kernel<D, T><<<grid, dim3(256), 0, stream>>>(img, H, W, C, S, G, oh, ow, (int)steps)
+#define ST_TPS_PIXEL(D, T)                                                                                                           \
+    do {                                                                                                                             \
+        if (interp == XI_BICUBIC) st_pixel_tps_bwd_kernel<D, T, XI_BICUBIC><<<grid, dim3(256), 0, stream>>>(img, H, W, C, S, G, oh, ow, (int)steps); \
+        else st_pixel_tps_bwd_kernel<D, T><<<grid, dim3(256), 0, stream>>>(img, H, W, C, S, G, oh, ow, (int)steps);                  \
+    } while (0)
         if (dimg && dtheta) ST_TPS_PIXEL(true, true);
         else if (dimg) ST_TPS_PIXEL(true, false);
         else ST_TPS_PIXEL(false, true);

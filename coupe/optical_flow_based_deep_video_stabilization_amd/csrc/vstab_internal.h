@@ -411,13 +411,14 @@ hipError_t launch_st_symmetry_transform(const float *img, int B, int H, int W, i
                                         float *out, int oh, int ow, hipStream_t stream);
 hipError_t launch_st_elastic_transform(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                        int interp, float *out, int oh, int ow, hipStream_t stream);
-// backward of launch_st_transform / launch_st_interp (bilinear sampler).  d_img (nullable) is zero-filled on `stream` first unless
-// `accumulate`; `part`: st_transform_backward_ws_bytes of scratch for the d theta partials
+// backward of launch_st_transform / launch_st_interp and, with interp = 1, of their bicubic forms (launch_st_transform_interp /
+// launch_st_bicubic_interp; likewise the elastic and symmetric-pad backwards below).  d_img (nullable) is zero-filled on `stream`
+// first unless `accumulate`; `part`: st_transform_backward_ws_bytes of scratch for the d theta partials, the same for both samplers
 size_t st_transform_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow);
 hipError_t launch_st_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int tdim, const float *dout, int oh,
-                                        int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream);
+                                        int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream, int interp = 0);
 hipError_t launch_st_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y, const float *dout, int oh,
-                                     int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream);
+                                     int ow, float *d_img, int accumulate, float *d_x, float *d_y, hipStream_t stream, int interp = 0);
 // backward of launch_homography_warp (d img, d M [B,9]; with `ref`: M holds pMtrx and d_M receives d pMtrx = ref^T . d (ref . pMtrx)) and
 // of launch_vec2mtrx (d p [B,dim] from d_out [B,9]); conventions as launch_st_transform_backward, `part`: homography_warp_backward_ws_bytes
 size_t homography_warp_backward_ws_bytes(int B, int Hi, int Wi, int C, int oh, int ow);
@@ -431,7 +432,7 @@ hipError_t launch_st_elastic_coords(const float *theta, int B, int g, const floa
 size_t st_elastic_backward_ws_bytes(int B, int H, int W, int C, int g, int oh, int ow);
 hipError_t launch_st_elastic_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int g, const float *linv_t,
                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part,
-                                                hipStream_t stream);
+                                                hipStream_t stream, int interp = 0);
 // The symmetric-pad transformers: their pre-mapped matrices out [B,9], the source coordinates per final pixel x_out, y_out
 // [B*ow*oh] (0 where the crop-or-pad pads), and the backward of their bilinear sampler, conventions as launch_st_transform_backward
 // (dout [B,ow,oh,C]), `part`: st_symmetry_backward_ws_bytes of scratch for the d M partials and d M
@@ -439,7 +440,8 @@ hipError_t launch_st_symmetry_matrix(const float *theta, int B, int kind, float 
 hipError_t launch_st_symmetry_coords(const float *theta, int B, int kind, int oh, int ow, float *x_out, float *y_out, hipStream_t stream);
 size_t st_symmetry_backward_ws_bytes(int B, int H, int W, int C, int oh, int ow);
 hipError_t launch_st_symmetry_transform_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind, const float *dout,
-                                                 int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream);
+                                                 int oh, int ow, float *d_img, int accumulate, float *d_theta, double *part, hipStream_t stream,
+                                                 int interp = 0);
 
 // The 3-D volume transformer (sampler3d_ops.hip): AffineVolumeTransformer / bilinear_interp3d / _meshgrid3d and their backward.
 // st3d_plan: bricks along each axis and per sample of a [B, od, oh, ow] output; false when the launch grid does not fit.  d_vol

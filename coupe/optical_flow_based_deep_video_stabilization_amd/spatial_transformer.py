@@ -11,9 +11,14 @@ Differentiable (torch.autograd, HIP backward kernels): `AffineTransformer.transf
 elastic one: the control-point offsets; for the symmetric-pad ones: through each class's pre-map, which makes `AffineSymmetryTransformer`'s
 theta gradient exactly zero and couples the samples of a `SimilarityTransformer` batch), and `bilinear_interp` with respect to the image, `x` and `y`; `AffineVolumeTransformer.transform` with respect to the volume and `theta`, `bilinear_interp3d` with respect to the
 volume, `x`, `y` and `z`.  The gradient of the image or volume is summed by float atomics (last bits may differ between runs); those of `theta`, `x`, `y`,
-`z` are bit-reproducible.  NOT differentiable -- the result has no `grad_fn`, whatever requires grad: `bicubic_interp` and
-`interp_method='bicubic'` (on `ElasticTransformer` and the symmetric-pad transformers too), `ElasticTransformer.transform_coords`, and the
-symmetric-pad transformers' `matrix` and `transform_coords`.
+`z` are bit-reproducible.  The BICUBIC sampler is differentiable on request: `bicubic_interp(..., differentiable=True)` and
+`differentiable=True` on the constructor of `AffineTransformer`, `ProjectiveTransformer`, `SimilarityTransformer`,
+`AffineSymmetryTransformer`, `ProjectiveSymmetryTransformer` or `ElasticTransformer` (passed through by `transformer()`) with
+`interp_method='bicubic'` go through HIP backward kernels too -- the image's gradient by float atomics (all 16 taps add, the
+replicated edge taps onto their one pixel), those of `theta`, `x`, `y` reproducible, zero where a coordinate lies outside [-1, 1] or is
+NaN (the sampler's clip).  Without the keyword a bicubic result has no `grad_fn`, whatever requires grad; with the bilinear sampler
+the keyword changes nothing.  NOT differentiable: `ElasticTransformer.transform_coords`, and the symmetric-pad transformers'
+`matrix` and `transform_coords`.
 The homography samplers of the reference's `warp.py` (`warp.transformImage` and its kin) are differentiable too: see `warp.py`."""
 from __future__ import annotations
 
@@ -99,10 +104,39 @@ def bilinear_interp(im, x, y, out_size):
     return _bilinear_interp_call(im, x, y, oh, ow)
 
 
-def bicubic_interp(im, x, y, out_size):
+def _bicubic_interp_call(im, x, y, oh, ow):
+    B, H, W, Cc = im.shape
+    out = torch.empty((B * oh * ow, Cc), dtype=torch.float32, device=im.device)
+    with torch.cuda.device(im.device):
+        _lib.check(_lib.lib().vstab_st_bicubic_interp(im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow,
+                                                      out.data_ptr(), runtime.stream_ptr()))
+    return out
+
+
+class _BicubicInterpFn(torch.autograd.Function):
+    """bicubic_interp with its HIP backward (training.st_bicubic_interp_backward)."""
+
+    @staticmethod
+    def forward(ctx, im, x, y, oh, ow):
+        ctx.save_for_backward(im, x, y)
+        ctx.out_size = (oh, ow)
+        return _bicubic_interp_call(im, x, y, oh, ow)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        from . import training
+        im, x, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_im, d_x, d_y = training.st_bicubic_interp_backward(im, x, y, dout, ctx.out_size, need_img=need[0], need_x=need[1], need_y=need[2])
+        return d_im, d_x, d_y, None, None
+
+
+def bicubic_interp(im, x, y, out_size, differentiable=False):
     """im [B,H,W,C]; x, y flat [B*out_h*out_w] normalised to [-1,1] -> [B*out_h*out_w, C].
     Coordinates are clipped to [-1, 1] before the scaling (NaN reads as -1); 4 x 4 taps, edges replicate
-    (no zero border), alpha = -0.75.  Not differentiable."""
+    (no zero border), alpha = -0.75.  differentiable=True: with respect to im, x and y (module docstring); otherwise the result
+    carries no graph."""
     im = _f32_cuda(im, "im")
     B, H, W, Cc = im.shape
     x = _f32_cuda(x.to(torch.float32), "x").reshape(-1)
@@ -111,11 +145,9 @@ def bicubic_interp(im, x, y, out_size):
     npix = oh * ow
     if x.numel() != B * npix or y.numel() != B * npix:
         raise ValueError(f"x/y must have B*out_h*out_w = {B * npix} elements")
-    out = torch.empty((B * npix, Cc), dtype=torch.float32, device=im.device)
-    with torch.cuda.device(im.device):
-        _lib.check(_lib.lib().vstab_st_bicubic_interp(im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow,
-                                                      out.data_ptr(), runtime.stream_ptr()))
-    return out
+    if differentiable and _wants_grad(im, x, y):
+        return _BicubicInterpFn.apply(im, x, y, oh, ow)
+    return _bicubic_interp_call(im, x, y, oh, ow)
 
 
 def _interpolate(im, x, y, out_size, method):
@@ -146,13 +178,13 @@ def _theta_transform_call(inp, theta, param_dim, oh, ow, interp):
 
 
 class _ThetaTransformFn(torch.autograd.Function):
-    """Affine / ProjectiveTransformer.transform (bilinear) with its HIP backward (training.st_transform_backward); theta flat."""
+    """Affine / ProjectiveTransformer.transform with its HIP backward (training.st_transform_backward); theta flat, method the sampler."""
 
     @staticmethod
-    def forward(ctx, inp, theta, param_dim, oh, ow):
+    def forward(ctx, inp, theta, param_dim, oh, ow, method='bilinear'):
         ctx.save_for_backward(inp, theta)
-        ctx.out_size = (oh, ow)
-        return _theta_transform_call(inp, theta, param_dim, oh, ow, 0)
+        ctx.out_size, ctx.method = (oh, ow), method
+        return _theta_transform_call(inp, theta, param_dim, oh, ow, _INTERP[method])
 
     @staticmethod
     @once_differentiable
@@ -160,17 +192,18 @@ class _ThetaTransformFn(torch.autograd.Function):
         from . import training
         inp, theta = ctx.saved_tensors
         need = ctx.needs_input_grad
-        d_inp, d_theta = training.st_transform_backward(inp, theta, dout, ctx.out_size, need_img=need[0], need_theta=need[1])
-        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None
+        d_inp, d_theta = training.st_transform_backward(inp, theta, dout, ctx.out_size, need_img=need[0], need_theta=need[1], interp=ctx.method)
+        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None
 
 
 class _ThetaTransformer(object):
     param_dim = 0
 
-    def __init__(self, out_size, name, interp_method='bilinear', **kwargs):
+    def __init__(self, out_size, name, interp_method='bilinear', differentiable=False, **kwargs):
         self.name = name
         self.out_size = (int(out_size[0]), int(out_size[1]))
         self.interp_method = interp_method
+        self.differentiable = bool(differentiable)          # the bicubic sampler's graph is opt-in; the bilinear one always has it
         self._grid = None
 
     @property
@@ -187,28 +220,28 @@ class _ThetaTransformer(object):
         if theta.numel() != B * self.param_dim:
             raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
         oh, ow = self.out_size
-        if interp == 0 and _wants_grad(inp, theta):          # bilinear only: the bicubic sampler has no backward
-            return _ThetaTransformFn.apply(inp, theta, self.param_dim, oh, ow)
+        if (interp == 0 or self.differentiable) and _wants_grad(inp, theta):
+            return _ThetaTransformFn.apply(inp, theta, self.param_dim, oh, ow, self.interp_method)
         return _theta_transform_call(inp, theta, self.param_dim, oh, ow, interp)
 
 
 class AffineTransformer(_ThetaTransformer):
     """theta [B,6] = row-major 2x3 matrix acting on (x_t, y_t, 1), x_t, y_t in [-1,1].  With the bilinear sampler `transform` is
-    differentiable with respect to the image and theta."""
+    differentiable with respect to the image and theta; with the bicubic one when constructed with differentiable=True."""
     param_dim = 6
 
-    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', **kwargs):
-        super().__init__(out_size, name, interp_method, **kwargs)
+    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', differentiable=False, **kwargs):
+        super().__init__(out_size, name, interp_method, differentiable, **kwargs)
 
 
 class ProjectiveTransformer(_ThetaTransformer):
     """theta [B,8] = first 8 entries of a 3x3 homography (last entry 1); divides by z,
     z == 0 replaced by 1e-8 (:598).  With the bilinear sampler `transform` is differentiable with respect to the image and theta
-    (8 entries per sample: the ninth is the constant 1)."""
+    (8 entries per sample: the ninth is the constant 1); with the bicubic one when constructed with differentiable=True."""
     param_dim = 8
 
-    def __init__(self, out_size, name='SpatialProjectiveTransformer', interp_method='bilinear', **kwargs):
-        super().__init__(out_size, name, interp_method, **kwargs)
+    def __init__(self, out_size, name='SpatialProjectiveTransformer', interp_method='bilinear', differentiable=False, **kwargs):
+        super().__init__(out_size, name, interp_method, differentiable, **kwargs)
 
 
 def _symmetry_transform_call(inp, theta, kind, oh, ow, interp):
@@ -221,13 +254,13 @@ def _symmetry_transform_call(inp, theta, kind, oh, ow, interp):
 
 
 class _SymmetryTransformFn(torch.autograd.Function):
-    """The symmetric-pad transformers' transform (bilinear) with its HIP backward (training.st_symmetry_transform_backward); theta flat."""
+    """The symmetric-pad transformers' transform with its HIP backward (training.st_symmetry_transform_backward); theta flat."""
 
     @staticmethod
-    def forward(ctx, inp, theta, kind, oh, ow):
+    def forward(ctx, inp, theta, kind, oh, ow, method='bilinear'):
         ctx.save_for_backward(inp, theta)
-        ctx.kind, ctx.out_size = kind, (oh, ow)
-        return _symmetry_transform_call(inp, theta, kind, oh, ow, 0)
+        ctx.kind, ctx.out_size, ctx.method = kind, (oh, ow), method
+        return _symmetry_transform_call(inp, theta, kind, oh, ow, _INTERP[method])
 
     @staticmethod
     @once_differentiable
@@ -235,8 +268,9 @@ class _SymmetryTransformFn(torch.autograd.Function):
         from . import training
         inp, theta = ctx.saved_tensors
         need = ctx.needs_input_grad
-        d_inp, d_theta = training.st_symmetry_transform_backward(inp, theta, dout, ctx.out_size, ctx.kind, need_img=need[0], need_theta=need[1])
-        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None
+        d_inp, d_theta = training.st_symmetry_transform_backward(inp, theta, dout, ctx.out_size, ctx.kind, need_img=need[0], need_theta=need[1],
+                                                                 interp=ctx.method)
+        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None
 
 
 class _SymmetryTransformer(object):
@@ -244,14 +278,16 @@ class _SymmetryTransformer(object):
     (H, W >= 100, as tf.pad requires; never materialised), sampled on the linspace grid of (oh+200) x (ow+200) points, then
     tf.image.resize_image_with_crop_or_pad(out, out_size[1], out_size[0]) -- target height ow, width oh: the result is
     [B, ow, oh, C].  For square outputs the swap does not show.  With the bilinear sampler `transform` is differentiable with
-    respect to the image and theta (through the pre-map of each class); with the bicubic one it is not (no `grad_fn`)."""
+    respect to the image and theta (through the pre-map of each class); with the bicubic one when constructed with
+    differentiable=True (no `grad_fn` otherwise)."""
     param_dim = 0
     kind = -1
 
-    def __init__(self, out_size, name, interp_method='bilinear', **kwargs):
+    def __init__(self, out_size, name, interp_method='bilinear', differentiable=False, **kwargs):
         self.name = name
         self.out_size = (int(out_size[0]), int(out_size[1]))
         self.interp_method = interp_method
+        self.differentiable = bool(differentiable)
 
     def _theta(self, theta, B=None):
         theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
@@ -267,8 +303,8 @@ class _SymmetryTransformer(object):
             raise ValueError(f"{type(self).__name__}: the 100-pixel symmetric pad needs H, W >= 100, got {H}x{W}")
         theta = self._theta(theta, B)
         oh, ow = self.out_size
-        if interp == 0 and _wants_grad(inp, theta):          # bilinear only: the bicubic sampler has no backward
-            return _SymmetryTransformFn.apply(inp, theta, self.kind, oh, ow)
+        if (interp == 0 or self.differentiable) and _wants_grad(inp, theta):
+            return _SymmetryTransformFn.apply(inp, theta, self.kind, oh, ow, self.interp_method)
         return _symmetry_transform_call(inp, theta, self.kind, oh, ow, interp)
 
     def matrix(self, theta):
@@ -306,8 +342,8 @@ class SimilarityTransformer(_SymmetryTransformer):
     param_dim = 4
     kind = 2
 
-    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', **kwargs):
-        super().__init__(out_size, name, interp_method, **kwargs)
+    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', differentiable=False, **kwargs):
+        super().__init__(out_size, name, interp_method, differentiable, **kwargs)
 
 
 class AffineSymmetryTransformer(_SymmetryTransformer):
@@ -318,8 +354,8 @@ class AffineSymmetryTransformer(_SymmetryTransformer):
     param_dim = 6
     kind = 0
 
-    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', **kwargs):
-        super().__init__(out_size, name, interp_method, **kwargs)
+    def __init__(self, out_size, name='SpatialAffineTransformer', interp_method='bilinear', differentiable=False, **kwargs):
+        super().__init__(out_size, name, interp_method, differentiable, **kwargs)
 
     def transform(self, inp, theta):
         out = super().transform(inp, theta)
@@ -333,8 +369,8 @@ class ProjectiveSymmetryTransformer(_SymmetryTransformer):
     param_dim = 8
     kind = 1
 
-    def __init__(self, out_size, name='SpatialProjectiveTransformer', interp_method='bilinear', **kwargs):
-        super().__init__(out_size, name, interp_method, **kwargs)
+    def __init__(self, out_size, name='SpatialProjectiveTransformer', interp_method='bilinear', differentiable=False, **kwargs):
+        super().__init__(out_size, name, interp_method, differentiable, **kwargs)
 
 
 def _tps_linv(g):
@@ -356,13 +392,13 @@ def _elastic_transform_call(inp, theta, g, linv_t, oh, ow, interp):
 
 
 class _ElasticTransformFn(torch.autograd.Function):
-    """ElasticTransformer.transform (bilinear) with its HIP backward (training.st_elastic_transform_backward); theta flat."""
+    """ElasticTransformer.transform with its HIP backward (training.st_elastic_transform_backward); theta flat."""
 
     @staticmethod
-    def forward(ctx, inp, theta, g, linv_t, oh, ow):
+    def forward(ctx, inp, theta, g, linv_t, oh, ow, method='bilinear'):
         ctx.save_for_backward(inp, theta, linv_t)
-        ctx.g, ctx.out_size = g, (oh, ow)
-        return _elastic_transform_call(inp, theta, g, linv_t, oh, ow, 0)
+        ctx.g, ctx.out_size, ctx.method = g, (oh, ow), method
+        return _elastic_transform_call(inp, theta, g, linv_t, oh, ow, _INTERP[method])
 
     @staticmethod
     @once_differentiable
@@ -370,8 +406,9 @@ class _ElasticTransformFn(torch.autograd.Function):
         from . import training
         inp, theta, linv_t = ctx.saved_tensors
         need = ctx.needs_input_grad
-        d_inp, d_theta = training.st_elastic_transform_backward(inp, theta, dout, ctx.out_size, ctx.g, linv_t, need_img=need[0], need_theta=need[1])
-        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None
+        d_inp, d_theta = training.st_elastic_transform_backward(inp, theta, dout, ctx.out_size, ctx.g, linv_t, need_img=need[0], need_theta=need[1],
+                                                                interp=ctx.method)
+        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None, None
 
 
 class ElasticTransformer(object):
@@ -379,9 +416,10 @@ class ElasticTransformer(object):
     meshgrid, x fastest); theta [B, 2*g*g] = x offsets then y offsets of the control points.  L_inv is computed once at
     construction, in double, and kept on the device as fp32 transpose(L_inv[:,3:]); the kernel computes each sample's
     coefficients once and U = r^2 ln r^2 per output pixel.  Output [B, oh, ow, C].  With the bilinear sampler `transform` is
-    differentiable with respect to the image and theta; with the bicubic one it is not (no `grad_fn`)."""
+    differentiable with respect to the image and theta; with the bicubic one when constructed with differentiable=True (no `grad_fn`
+    otherwise)."""
 
-    def __init__(self, out_size, param_dim, name='SpatialElasticTransformer', interp_method='bilinear', **kwargs):
+    def __init__(self, out_size, param_dim, name='SpatialElasticTransformer', interp_method='bilinear', differentiable=False, **kwargs):
         g = int(param_dim)
         if g < 2:
             raise ValueError("ElasticTransformer: param_dim (control grid side) must be >= 2; g = 1 makes L singular")
@@ -390,6 +428,7 @@ class ElasticTransformer(object):
         self.num_control_points = g * g
         self.param_dim = 2 * g * g
         self.interp_method = interp_method
+        self.differentiable = bool(differentiable)
         self.out_size = (int(out_size[0]), int(out_size[1]))
         self.num_pixels = self.out_size[0] * self.out_size[1]
         linv = _tps_linv(g)                       # ValueError for g > VSTAB_TPS_GMAX
@@ -413,8 +452,8 @@ class ElasticTransformer(object):
         if theta.device != inp.device:
             raise ValueError("theta must be on inp's device")
         oh, ow = self.out_size
-        if interp == 0 and _wants_grad(inp, theta):          # bilinear only: the bicubic sampler has no backward
-            return _ElasticTransformFn.apply(inp, theta, self.grid_size, self.L_inv, oh, ow)
+        if (interp == 0 or self.differentiable) and _wants_grad(inp, theta):
+            return _ElasticTransformFn.apply(inp, theta, self.grid_size, self.L_inv, oh, ow, self.interp_method)
         return _elastic_transform_call(inp, theta, self.grid_size, self.L_inv, oh, ow, interp)
 
     def transform_coords(self, theta):
@@ -570,5 +609,6 @@ class AffineVolumeTransformer(object):
 
 def transformer(inp, theta, out_size, name='SpatialTransformer', **kwargs):
     """Legacy wrapper (:34-38).  The reference passes `out_size` to `transform`, which does not take
-    it (a TypeError there); here the call does what the wrapper evidently means."""
-    return AffineTransformer(out_size).transform(inp, theta)
+    it (a TypeError there); here the call does what the wrapper evidently means.  `differentiable` (and `interp_method`) among the
+    keywords go to AffineTransformer."""
+    return AffineTransformer(out_size, **kwargs).transform(inp, theta)

@@ -2,7 +2,7 @@
 `lossterm` / `masked_MSE` (main:188-210, "main" = main_flownetS_pyramid_noprevloss_dataloader.py), the total-variation
 terms and `loss_main` (main:213-275) with their gradient with respect to every predicted flow; filter / input gradients
 of the conv and transposed-conv layers; BatchNorm(lrelu) in training mode and its backward; the resamplers' adjoints; the
-gradients of the bilinear spatial transformers (`st_transform_backward`, `st_symmetry_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`)
+gradients of the spatial transformers, bilinear and bicubic (`st_bicubic_interp_backward`, `st_transform_backward`, `st_symmetry_transform_backward`, `st_elastic_transform_backward`, `st_bilinear_interp_backward`)
 and of warp.py's homography warp and matrix exponential (`homography_warp_backward`, `vec2mtrx_backward`), of utils.py's SSIM (`ssim_backward`)
 and of cell.py's gate stages (`convlstm_gates_backward`, `convgru_update_backward`, `convgru_gates_backward`).
 `train_step.Trainer` strings them into the whole step (forward, loss, backward, Adam: main:184-185, 333-335).
@@ -365,11 +365,22 @@ def _st_backward_args(img, dout, out_hw, d_img, need_img):
     return img, dout.contiguous(), (B, H, W, C, oh, ow), d_img, acc
 
 
-def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, need_theta: bool = True, d_img=None):
-    """Gradients of AffineTransformer / ProjectiveTransformer.transform (bilinear sampler) for the output gradient dout
-    [B,oh,ow,C]: (d img [B,H,W,C] or None, d theta [B,6|8] or None).  A given d_img is added into (the `accumulate` convention),
-    otherwise it is allocated and overwritten.  need_img / need_theta False skips that gradient's work.  d img is summed by float
-    atomics (its last bits may differ between runs); d theta is bit-reproducible."""
+_ST_INTERP = {'bilinear': 0, 'bicubic': 1}          # VSTAB_INTERP_*
+
+
+def _st_interp(interp):
+    if interp not in _ST_INTERP:
+        raise ValueError("interp must be 'bilinear' or 'bicubic'")
+    return _ST_INTERP[interp]
+
+
+def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, need_theta: bool = True, d_img=None, interp='bilinear'):
+    """Gradients of AffineTransformer / ProjectiveTransformer.transform for the output gradient dout [B,oh,ow,C]: (d img [B,H,W,C] or
+    None, d theta [B,6|8] or None).  A given d_img is added into (the `accumulate` convention), otherwise it is allocated and
+    overwritten.  need_img / need_theta False skips that gradient's work.  d img is summed by float atomics (its last bits may differ
+    between runs); d theta is bit-reproducible.  interp: the forward's sampler, 'bilinear' (the default: today's library call) or
+    'bicubic' -- here and in the symmetric-pad and elastic backwards below."""
+    ip = _st_interp(interp)
     need_img = need_img or d_img is not None
     img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
     theta = theta.contiguous()
@@ -383,23 +394,27 @@ def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, nee
         n = int(L.vstab_st_transform_backward_workspace_bytes(B, H, W, C, oh, ow))
         ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
     with torch.cuda.device(img.device):
-        _lib.check(L.vstab_st_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), tdim, dout.data_ptr(), oh, ow,
-                                                 d_img.data_ptr() if need_img else None, 1 if acc else 0,
-                                                 d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
-                                                 runtime.stream_ptr()))
+        tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_theta.data_ptr() if need_theta else None,
+                ws.data_ptr() if need_theta else None, n, runtime.stream_ptr())
+        if ip == 0:
+            _lib.check(L.vstab_st_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), tdim, *tail))
+        else:
+            _lib.check(L.vstab_st_transform_interp_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), tdim, ip, *tail))
     return (d_img if need_img else None), d_theta
 
 
 _SYM_THETA_DIM = {0: 6, 1: 8, 2: 4}          # VSTAB_SYM_AFFINE, _PROJECTIVE, _SIMILARITY
 
 
-def st_symmetry_transform_backward(img, theta, dout, out_size, kind, need_img: bool = True, need_theta: bool = True, d_img=None):
+def st_symmetry_transform_backward(img, theta, dout, out_size, kind, need_img: bool = True, need_theta: bool = True, d_img=None,
+                                   interp='bilinear'):
     """Gradients of SimilarityTransformer (kind 2) / AffineSymmetryTransformer (0) / ProjectiveSymmetryTransformer (1) .transform with
-    the bilinear sampler, for the output gradient dout in the forward's output layout [B,ow,oh,C] (out_size = (oh, ow)): (d img
+    the sampler `interp`, for the output gradient dout in the forward's output layout [B,ow,oh,C] (out_size = (oh, ow)): (d img
     [B,H,W,C] or None, d theta [B,4|6|8] or None).  H, W >= 100.  d_img, need_img, need_theta as in st_transform_backward; d img is
     summed by float atomics (its last bits may differ between runs), d theta is bit-reproducible.  The affine kind's pre-map
     multiplies theta by 0: its d theta is exactly zero for finite gradients.  The similarity kind's d theta couples the samples of a
     batch for B > 1, as the reference's interleave does."""
+    ip = _st_interp(interp)
     kind = int(kind)
     if kind not in _SYM_THETA_DIM:
         raise ValueError("kind must be 0 (affine), 1 (projective) or 2 (similarity)")
@@ -418,10 +433,12 @@ def st_symmetry_transform_backward(img, theta, dout, out_size, kind, need_img: b
         n = int(L.vstab_st_symmetry_transform_backward_workspace_bytes(B, H, W, C, oh, ow))
         ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
     with torch.cuda.device(img.device):
-        _lib.check(L.vstab_st_symmetry_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), kind, dout.data_ptr(), oh, ow,
-                                                          d_img.data_ptr() if need_img else None, 1 if acc else 0,
-                                                          d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
-                                                          runtime.stream_ptr()))
+        tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_theta.data_ptr() if need_theta else None,
+                ws.data_ptr() if need_theta else None, n, runtime.stream_ptr())
+        if ip == 0:
+            _lib.check(L.vstab_st_symmetry_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), kind, *tail))
+        else:
+            _lib.check(L.vstab_st_symmetry_transform_interp_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), kind, ip, *tail))
     return (d_img if need_img else None), d_theta
 
 
@@ -475,11 +492,13 @@ def vec2mtrx_backward(p, d_out, warp_type, warp_approx):
     return d_p
 
 
-def st_elastic_transform_backward(img, theta, dout, out_size, g, linv_t, need_img: bool = True, need_theta: bool = True, d_img=None):
-    """Gradients of ElasticTransformer.transform (thin-plate spline, bilinear sampler) for the output gradient dout [B,oh,ow,C]:
+def st_elastic_transform_backward(img, theta, dout, out_size, g, linv_t, need_img: bool = True, need_theta: bool = True, d_img=None,
+                                  interp='bilinear'):
+    """Gradients of ElasticTransformer.transform (thin-plate spline, sampler `interp`) for the output gradient dout [B,oh,ow,C]:
     (d img [B,H,W,C] or None, d theta [B, 2*g*g] or None).  g is the control grid's side, linv_t the transformer's device table
     [g*g, g*g+3] (ElasticTransformer.L_inv).  d_img, need_img, need_theta as in st_transform_backward; d img is summed by float
     atomics (its last bits may differ between runs), d theta is bit-reproducible."""
+    ip = _st_interp(interp)
     need_img = need_img or d_img is not None
     img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
     g = int(g)
@@ -497,16 +516,28 @@ def st_elastic_transform_backward(img, theta, dout, out_size, g, linv_t, need_im
         n = int(L.vstab_st_elastic_transform_backward_workspace_bytes(B, H, W, C, g, oh, ow))
         ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
     with torch.cuda.device(img.device):
-        _lib.check(L.vstab_st_elastic_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), g, linv_t.data_ptr(), dout.data_ptr(),
-                                                         oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0,
-                                                         d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
-                                                         runtime.stream_ptr()))
+        tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_theta.data_ptr() if need_theta else None,
+                ws.data_ptr() if need_theta else None, n, runtime.stream_ptr())
+        if ip == 0:
+            _lib.check(L.vstab_st_elastic_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), g, linv_t.data_ptr(), *tail))
+        else:
+            _lib.check(L.vstab_st_elastic_transform_interp_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), g, linv_t.data_ptr(), ip, *tail))
     return (d_img if need_img else None), d_theta
 
 
 def st_bilinear_interp_backward(img, x, y, dout, out_size, need_img: bool = True, need_x: bool = True, need_y: bool = True, d_img=None):
     """Gradients of bilinear_interp(img, x, y, out_size) for dout [B*oh*ow, C]: (d img or None, d x [B*oh*ow] or None, d y or None);
     d_img as in st_transform_backward."""
+    return _st_interp_backward("vstab_st_bilinear_interp_backward", img, x, y, dout, out_size, need_img, need_x, need_y, d_img)
+
+
+def st_bicubic_interp_backward(img, x, y, dout, out_size, need_img: bool = True, need_x: bool = True, need_y: bool = True, d_img=None):
+    """Gradients of bicubic_interp(img, x, y, out_size), arguments and results as st_bilinear_interp_backward.  d x, d y are zero
+    where a coordinate is outside [-1, 1] or NaN (the clip), and reproducible; d img is summed by float atomics."""
+    return _st_interp_backward("vstab_st_bicubic_interp_backward", img, x, y, dout, out_size, need_img, need_x, need_y, d_img)
+
+
+def _st_interp_backward(entry, img, x, y, dout, out_size, need_img, need_x, need_y, d_img):
     need_img = need_img or d_img is not None
     img, dout, (B, H, W, C, oh, ow), d_img, acc = _st_backward_args(img, dout, out_size, d_img, need_img)
     x, y = x.contiguous().reshape(-1), y.contiguous().reshape(-1)
@@ -516,10 +547,9 @@ def st_bilinear_interp_backward(img, x, y, dout, out_size, need_img: bool = True
     d_x = torch.empty_like(x) if need_x else None
     d_y = torch.empty_like(y) if need_y else None
     with torch.cuda.device(img.device):
-        _lib.check(_lib.lib().vstab_st_bilinear_interp_backward(img.data_ptr(), B, H, W, C, x.data_ptr(), y.data_ptr(), dout.data_ptr(), oh, ow,
-                                                                d_img.data_ptr() if need_img else None, 1 if acc else 0,
-                                                                d_x.data_ptr() if need_x else None, d_y.data_ptr() if need_y else None,
-                                                                runtime.stream_ptr()))
+        _lib.check(getattr(_lib.lib(), entry)(img.data_ptr(), B, H, W, C, x.data_ptr(), y.data_ptr(), dout.data_ptr(), oh, ow,
+                                              d_img.data_ptr() if need_img else None, 1 if acc else 0,
+                                              d_x.data_ptr() if need_x else None, d_y.data_ptr() if need_y else None, runtime.stream_ptr()))
     return (d_img if need_img else None), d_x, d_y
 
 

@@ -211,7 +211,7 @@ VSTAB_API int vstab_st_elastic_transform(const float *img, int B, int H, int W, 
                                          int interp, float *out, int oh, int ow, void *stream);
 /* ---- backward of the BILINEAR sampler: vstab_st_transform (affine and projective) and vstab_st_bilinear_interp.  These two are the
  * differentiable samplers besides the thin-plate spline, the symmetric-pad transformers and the homography warps (further down);
- * the bicubic sampler has no backward.
+ * the bicubic sampler's backward (vstab_st_bicubic_interp_backward and the _interp_backward entry points) follows these two.
  * What TensorFlow's autodiff gives for ST:902-964 / 438-452 / 578-608: floor and the casts have zero derivative, the clip passes the
  * gradient where -1 <= x <= W inclusive (0 outside and for NaN), taps on the zero border receive nothing; coordinates and taps are
  * the forward's fp32 values.  img, B, H, W, C, theta | x, y, oh, ow as in the forward (B <= 65535, B*H*W*C < 2^31);
@@ -231,6 +231,33 @@ VSTAB_API int vstab_st_transform_backward(const float *img, int B, int H, int W,
 VSTAB_API int vstab_st_bilinear_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y,
                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x,
                                                 float *d_y, void *stream);
+/* ---- backward of the BICUBIC sampler, and the backwards above and below with a choice of sampler.  What TensorFlow's autodiff gives
+ * for bicubic_interp (ST:966-1072), out_c = sum_i sum_j wy_i wx_j I[ys_i, xs_j, c]: taps and weights are the forward's (every floor, clip
+ * and edge decision is shared); floor and the casts have zero derivative, so the weights' derivatives w'_i = c_i1 + 2 c_i2 t + 3 c_i3 t^2
+ * carry d x, d y; the clip to [-1,1] passes the gradient where -1 <= x <= 1 INCLUSIVE, 0 outside and for NaN (which the forward
+ * reads as -1) -- the convention of the bilinear clip above.
+ *   d_img   by float atomics like the bilinear one (last bits depend on arrival order): wy_i wx_j dout added to each of the 16 taps; at
+ *           the image edge the replicate-clamp folds several taps onto one pixel and all of them add (there is no zero border).  The
+ *           symmetric-pad kinds' taps are those of the padded extent mapped through the symmetric pad, as in the forward.
+ *   d_theta, d_x, d_y  reproducible: d x, d y feed each source's existing chain, summed in double in a fixed order without atomics.
+ * vstab_st_bicubic_interp_backward is vstab_st_bilinear_interp_backward for bicubic_interp.  The three _interp_backward entry points
+ * take `interp` (VSTAB_INTERP_*; anything else is VSTAB_E_SHAPE) after theta_dim | kind | linv_t; with VSTAB_INTERP_BILINEAR each IS
+ * the entry point without _interp (d_theta bit-equal).  Nullable outputs, accumulate, limits (B <= 65535, B*H*W*C < 2^31), error
+ * codes and the order of the checks are those of the bilinear backwards, and the existing *_backward_workspace_bytes functions serve
+ * both samplers: the partial-row workspace does not depend on the sampler. */
+VSTAB_API int vstab_st_bicubic_interp_backward(const float *img, int B, int H, int W, int C, const float *x, const float *y,
+                                               const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_x, float *d_y,
+                                               void *stream);
+VSTAB_API int vstab_st_transform_interp_backward(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim, int interp,
+                                                 const float *dout, int oh, int ow, float *d_img, int accumulate, float *d_theta,
+                                                 void *workspace, size_t workspace_bytes, void *stream);
+VSTAB_API int vstab_st_symmetry_transform_interp_backward(const float *img, int B, int H, int W, int C, const float *theta, int kind,
+                                                          int interp, const float *dout, int oh, int ow, float *d_img, int accumulate,
+                                                          float *d_theta, void *workspace, size_t workspace_bytes, void *stream);
+VSTAB_API int vstab_st_elastic_transform_interp_backward(const float *img, int B, int H, int W, int C, const float *theta, int g,
+                                                         const float *linv_t, int interp, const float *dout, int oh, int ow, float *d_img,
+                                                         int accumulate, float *d_theta, void *workspace, size_t workspace_bytes,
+                                                         void *stream);
 /* ---- ElasticTransformer (thin-plate spline): its source coordinates, and the backward of its BILINEAR sampler.  theta, g, linv_t,
  * oh, ow as in vstab_st_elastic_transform.
  * vstab_st_elastic_coords: x_out, y_out [B*oh*ow], the normalised source coordinates (x_s_flat, y_s_flat of ST:140-158) that
