@@ -325,7 +325,8 @@ static int forward_chunk(vstab_ctx *ctx, const float *feats, int B, int H, int W
             q.in = buf(B_WINO_V); q.out = buf(B_WINO_M);
             q.wpk = dw + ctx->wino_w[i]; q.bias = dw + ctx->zero_b; q.partial = buf(B_PARTIAL);
             const int T_i = ((pl.eh[i] + 1) / 2) * ((pl.ew[i] + 1) / 2);
-            const int P_i = wino_gemm_stream_positions(B, T_i, cin_i, e.cout);
+            // (VSTAB_PLAN_NO_WINO_STREAM: the tiled launch below for every stage -- the B side of the stream form's A/B, same bits)
+            const int P_i = (pin.flags & VSTAB_PLAN_NO_WINO_STREAM) ? 0 : wino_gemm_stream_positions(B, T_i, cin_i, e.cout);
             if (P_i > 0) {       // streams of positions (wino_gemm_stream.hip): B=8 512x512 conv3_1 (8 positions per workgroup), conv4_1 (4)
                 HIP_TRY(ctx, launch_wino_gemm_stream(q.in, q.wpk, q.out, B, T_i, cin_i, e.cout, P_i, stream, EV_A(i), EV_B(i)));
                 PROF_NAME(i, "wino_gemm_stream_kernel");

@@ -9,7 +9,9 @@
 // accumulators are copied to registers, the next position starts with srcC = 0, and the finished tile leaves as four-byte stores
 // between the MFMAs of the next position's first K-tile (tools/gen_conv_kloop.py, GemmStreamGen, documents the schedule).  The last
 // position's tile goes through the LDS-transposing epilogue below.  Same K-tile order, same MFMA order per accumulator, same `+ 0.0`
-// of the zero bias as the implicit-GEMM launch it replaces: bit-identical to it.
+// of the zero bias as the implicit-GEMM launch it replaces: bit-identical to it.  tests/test_gpu_wino_gemm_stream.py pins that: the kernel
+// by itself (vstab_wino_domain_gemm, both forms on one packed operand) at every P, on random operands against fp64, on exact integers and
+// with torch.equal against the tiled launch, and inside the network under VSTAB_PLAN_NO_WINO_STREAM.
 //
 // Needs T % 128 == 0 (a tile never straddles two samples: row offsets are linear in the tile), C_in % 64 == 0 (an even number >= 4 of
 // 32-float K-tiles, all whole), C_out % 64 == 0: the launcher checks and the plan falls back to launch_conv otherwise.

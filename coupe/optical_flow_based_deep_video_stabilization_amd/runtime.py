@@ -67,7 +67,8 @@ class Context:
 
     def set_plan_flags(self, flags: int):
         """VSTAB_PLAN_* bits (diagnostic; 1 = few-row layers stay on the tiled kernel + split-K combine launch, 2 = refinement levels as four
-        launches, 4 = the one-call stabiliser's last two launches kept apart, 32 = conv1 on the fp32 MFMA instead of bf16 piece-products: A/B runs and tests)."""
+        launches, 4 = the one-call stabiliser's last two launches kept apart, 32 = conv1 on the fp32 MFMA instead of bf16 piece-products,
+        64 = Winograd-domain GEMMs as tiled launches, never as streams of positions: A/B runs and tests)."""
         _lib.check(_lib.lib().vstab_set_plan_flags(self._h, int(flags)), self._h)
         self.plan_flags = int(flags)
         self._ws.clear()

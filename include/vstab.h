@@ -753,7 +753,24 @@ VSTAB_API int vstab_warp_perspective_u8(const uint8_t *src, int B, int sh, int s
 #define VSTAB_PLAN_FORCE_WDEC 16u  /* deconv4 / deconv3 in Winograd F(2x2,2x2) form whatever their size (tests: small shapes) */
 #define VSTAB_PLAN_CONV1_FP32 32u  /* conv1 on the fp32 MFMA (conv_rowwin.hip) instead of six bf16 piece-products per multiply on the bf16 MFMA
                                     * (conv1_bf16x3.hip: fp32 operands split into three bf16 pieces, fp32 accumulation); the A side of its A/B */
+#define VSTAB_PLAN_NO_WINO_STREAM 64u  /* the 16 Winograd-domain GEMMs of every F(2x2,3x3) stage as one tiled launch, never as streams of positions
+                                        * (wino_gemm_stream.hip); same sums in the same order (bit-identical), same workspace: the plan is unchanged */
 VSTAB_API int vstab_set_plan_flags(vstab_ctx *ctx, unsigned flags);
+
+/* The 16 Winograd-domain GEMMs of a 3x3 stride-1 stage by themselves, without the transforms around them: M[b][xi] = V[b][xi] . U[xi] for the
+ * positions xi = 0..15 of the transformed 4x4 tile.  V [B][16][T][cin], U [16][cin][cout] plain row-major, M [B][16][T][cout], all in device
+ * memory and 16-byte aligned; every tensor below 2 GiB; cin % 32 == 0, cout % 64 == 0.  U is packed on the device into the first
+ * 16*cin*cout*4 bytes of the workspace (16 positions x [cin/32][cout][32], the layout vstab_load_weights gives a stage's operand) and both
+ * forms read that operand: form 0 = the tiled launch (128x64 tiles, zero bias, no split-K), form 1 = streams of positions
+ * (csrc/wino_gemm_stream.hip) with the number of positions per workgroup vstab_host_wino_stream_positions() gives -- VSTAB_E_SHAPE,
+ * and no launch, when that is 0.  workspace: vstab_wino_domain_gemm_workspace_bytes() bytes, 256-byte aligned (VSTAB_E_NOMEM when smaller;
+ * the query returns 0 for a shape the call refuses).  VSTAB_E_STATE for a NULL buffer, VSTAB_E_ALIGN for a misaligned one. */
+VSTAB_API size_t vstab_wino_domain_gemm_workspace_bytes(int B, int T, int cin, int cout);
+VSTAB_API int vstab_wino_domain_gemm(const float *V, const float *U, float *M, int B, int T, int cin, int cout, int form, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+/* The stream launcher itself with a caller-chosen number of positions per workgroup (wpk: an operand packed as above): VSTAB_E_SHAPE, and
+ * no launch, unless P is what vstab_host_wino_stream_positions() gives for the shape. */
+VSTAB_API int vstab_wino_gemm_stream_launch(const float *V, const float *wpk, float *M, int B, int T, int cin, int cout, int P, void *stream);
 
 /* conv1 alone, in the form this context's plan flags choose (six bf16 piece-products on the bf16 MFMA, or VSTAB_PLAN_CONV1_FP32's fp32 MFMA):
  * feats [B][H][W][Cin] -> channels c_off .. c_off + 64 of out [B][Ho][Wo][cs_out]; the other channels of a pixel are not touched.
@@ -834,6 +851,13 @@ VSTAB_API long long vstab_host_pack_layer(int Cin, int layer, const float *W, co
  * builds them (W = the reference-layout filter [4][4][Cout][Cin]; 9 positions x [KT][4 Cout][32]). */
 VSTAB_API int vstab_host_wdec_plan(int B, int H, int W, int Cin, int l, int32_t *out, int cap);
 VSTAB_API long long vstab_host_pack_wdec(int l, const float *W, const double *scale, float *wpk, long long cap);
+
+/* Positions per workgroup of the stream form of a Winograd stage's 16 GEMMs (csrc/wino_gemm_stream.hip) for B samples of T tiles, cin -> cout
+ * channels: 16, 8, 4 or 2, or 0 when the stage does not qualify (the forward then takes the tiled launch). */
+VSTAB_API int vstab_host_wino_stream_positions(int B, int T, int cin, int cout);
+/* The Winograd-domain operand of a 3x3 stride-1 stage as vstab_load_weights packs it: W [3][3][cin][cout], scale (may be NULL = ones) per
+ * output channel; 16 positions x [cin/32][cout][32] floats to `wpk`.  Returns the number of floats, or a negative error. */
+VSTAB_API long long vstab_host_pack_winograd(const float *W, const double *scale, int cin, int cout, float *wpk, long long cap);
 
 #ifdef __cplusplus
 }

@@ -298,3 +298,75 @@ def test_winograd_deconv_geometry_packing_and_transforms(l, HW):
     assert issued / direct >= 9 / 16                                  # 9 multiplies per 4x4 outputs x 4 ... / 64, plus the ragged grid
     if min(d["Hi"], d["Wi"]) >= 12:
         assert issued / direct < 0.75, issued / direct
+
+
+# ---- the stream form of a Winograd stage's 16 GEMMs (csrc/wino_gemm_stream.hip): the launcher's rule, and the layout of the operand that
+# tests/test_gpu_wino_gemm_stream.py hands both forms of the GEMM
+def stream_positions(B, T, cin, cout):
+    return _lib.lib().vstab_host_wino_stream_positions(B, T, cin, cout)
+
+
+# B, T, cin, cout, positions per workgroup: B * (T/128) * (cout/64) * (16/P) == 512 workgroups each (the cases of the GPU test)
+STREAM_CASES = [
+    (8, 1024, 256, 256, 8),        # conv3_1 at B=8 512x512
+    (8, 256, 512, 512, 4),         # conv4_1 at B=8 512x512
+    (4, 256, 512, 512, 2),         # conv4_1 at B=4: two row tiles per sample
+    (8, 1024, 128, 512, 16),       # one workgroup owns all 16 positions; four K-tiles per position: one pair of loop bodies
+    (2, 4096, 128, 64, 2),         # a single column tile
+    (1, 1024, 192, 512, 2),        # one sample; six K-tiles per position
+    (8, 128, 1024, 512, 2),        # one row tile per sample: sample index = tile index; 32 K-tiles per position
+]
+
+
+def test_wino_stream_positions_rule():
+    # the network's two streamed stages (conv3_1: 32x32 tiles of 256 -> 256 channels, conv4_1: 16x16 tiles of 512 -> 512) at 512x512
+    for B, p3, p4 in ((4, 4, 2), (8, 8, 4), (16, 16, 8)):
+        assert stream_positions(B, 1024, 256, 256) == p3 and stream_positions(B, 256, 512, 512) == p4, B
+    for B, T, cin, cout, P in STREAM_CASES:
+        assert B * (T // 128) * (cout // 64) * (16 // P) == 512
+        assert stream_positions(B, T, cin, cout) == P, (B, T, cin, cout)
+    # each of these breaks one condition; with that condition dropped the tile count would still lead to 512 workgroups for some P
+    assert stream_positions(64, 64, 256, 512) == 0           # T below a row tile
+    assert stream_positions(8, 192, 512, 512) == 0           # T not whole row tiles
+    assert stream_positions(8, 1024, 64, 256) == 0           # two K-tiles per position: below the loop's shortest stream
+    assert stream_positions(8, 1024, 160, 256) == 0          # an odd number of K-tiles
+    assert stream_positions(8, 1024, 256, 96) == 0           # cout not whole column tiles
+    # tiles per position that no P in {2, 4, 8, 16} brings to 512 workgroups
+    assert 25 * (512 // 128) * (64 // 64) == 100 and stream_positions(25, 512, 128, 64) == 0
+    assert 16 * (1024 // 128) * (512 // 64) == 1024 and stream_positions(16, 1024, 256, 512) == 0
+
+
+def blocked_pack_np(U):
+    """[K][N] row-major -> the MFMA kernels' operand [K/32][N][32]: K-tile kt, column n holds U[32 kt .. 32 kt + 31][n], its 16-byte chunks
+    XOR-swizzled by (n >> 1) & 7 (pack.cpp's layout, restated)"""
+    K, N = U.shape
+    assert K % 32 == 0
+    pos = np.array([[swz32(n, k) for k in range(32)] for n in range(N)])                     # [N, 32]: where logical k sits
+    out = np.empty((K // 32, N, 32), U.dtype)
+    np.put_along_axis(out, np.broadcast_to(pos, out.shape), U.reshape(K // 32, 32, N).transpose(0, 2, 1), axis=2)
+    return out
+
+
+def test_winograd_operand_layout_is_the_blocked_layout_per_position():
+    # what vstab_load_weights packs for a Winograd stage (pack_winograd) is, position by position, blocked_pack_np of U[xi] = G g G^T:
+    # the layout the GPU test checks the device-side packing of vstab_wino_domain_gemm against.  Integer filters: G g G^T is exact
+    # (multiples of 1/4), so the comparison is bit for bit; the scale is folded in double and rounded once on both sides.
+    cin, cout = 96, 128
+    rng = np.random.default_rng(7)
+    Wt = rng.integers(-4, 5, (3, 3, cin, cout)).astype(np.float32)
+    scale = rng.uniform(0.5, 1.5, cout)
+    G = np.array([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]])
+    U = np.einsum("ia,jb,abkn->ijkn", G, G, Wt.astype(np.float64)).reshape(16, cin, cout)
+    n = 16 * cin * cout
+    for sc in (None, scale):
+        wpk = np.full(n + 32, np.nan, np.float32)
+        got = _lib.lib().vstab_host_pack_winograd(Wt.ctypes.data_as(_lib.c_float_p),
+                                                  None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_double)), cin, cout,
+                                                  wpk.ctypes.data_as(_lib.c_float_p), n)
+        assert got == n and np.isnan(wpk[n:]).all()
+        want = U if sc is None else U * sc
+        for xi in range(16):
+            assert np.array_equal(wpk[xi * cin * cout:(xi + 1) * cin * cout].reshape(cin // 32, cout, 32),
+                                  blocked_pack_np(want[xi].astype(np.float32))), xi
+    assert _lib.lib().vstab_host_pack_winograd(Wt.ctypes.data_as(_lib.c_float_p), None, cin, cout, wpk.ctypes.data_as(_lib.c_float_p), n - 1) == -4
+    assert _lib.lib().vstab_host_pack_winograd(None, None, cin, cout, wpk.ctypes.data_as(_lib.c_float_p), n) == -1
