@@ -175,7 +175,25 @@ WgradSplit wgrad_split(int M, int cout, int K)
     }
     return s;
 }
+bool wino_wgrad_shape(int B, int H, int W, int cin, int cout, WgradParams &p, int &TH, int &TW);      // (below, with its entry point)
 }  // namespace
+
+// Host-only view of the two rules above (no HIP call): out4 = {n_main, n_tail, ks_main, ks_tail} of the launches vstab_conv_wgrad makes of a
+// reduction over K pixels into M x cout (nbatch 0 or 1), or -- nbatch 16 -- {cout, 0, ksplit, 0} of the batched launch that
+// vstab_conv3x3_winograd_wgrad makes for M = cin input channels and K = B*TH*TW tiles.
+extern "C" int vstab_host_wgrad_split(int M, int cout, int K, int nbatch, int *out4)
+{
+    if (!out4 || M < 1 || cout < 1 || K < 1 || !(nbatch == 0 || nbatch == 1 || nbatch == 16)) return VSTAB_E_SHAPE;
+    if (nbatch == 16) {
+        WgradParams p; int TH, TW;
+        if (!wino_wgrad_shape(K, 1, 1, M, cout, p, TH, TW)) return VSTAB_E_SHAPE;              // K samples of one tile each: T = K
+        out4[0] = p.Cout; out4[1] = 0; out4[2] = p.ksplit; out4[3] = 0;
+        return VSTAB_OK;
+    }
+    const WgradSplit s = wgrad_split(M, cout, K);
+    out4[0] = s.n_main; out4[1] = s.n_tail; out4[2] = s.ks_main; out4[3] = s.ks_tail;
+    return VSTAB_OK;
+}
 
 extern "C" size_t vstab_conv_wgrad_workspace_bytes(int B, int Ho, int Wo, int k, int cin, int cout)
 {

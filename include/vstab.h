@@ -855,6 +855,12 @@ VSTAB_API long long vstab_host_pack_wdec(int l, const float *W, const double *sc
 /* Positions per workgroup of the stream form of a Winograd stage's 16 GEMMs (csrc/wino_gemm_stream.hip) for B samples of T tiles, cin -> cout
  * channels: 16, 8, 4 or 2, or 0 when the stage does not qualify (the forward then takes the tiled launch). */
 VSTAB_API int vstab_host_wino_stream_positions(int B, int T, int cin, int cout);
+/* How a filter gradient is launched (csrc/wgrad_mfma.hip), without a HIP call: out4 = {n_main, n_tail, ks_main, ks_tail} -- the columns and
+ * the split-K count of the launches vstab_conv_wgrad makes for M = k*k*cin rows, cout columns and a reduction over K = B*Ho*Wo output pixels
+ * (n_tail = ks_tail = 0: one launch).  nbatch = 0 or 1: that plain form; nbatch = 16: {cout, 0, ksplit, 0} of the 16-plane batched launch
+ * vstab_conv3x3_winograd_wgrad makes for M = cin and K = B*ceil(H/2)*ceil(W/2) tiles.  VSTAB_E_SHAPE for anything else, or a shape the
+ * batched form refuses. */
+VSTAB_API int vstab_host_wgrad_split(int M, int cout, int K, int nbatch, int *out4);
 /* The Winograd-domain operand of a 3x3 stride-1 stage as vstab_load_weights packs it: W [3][3][cin][cout], scale (may be NULL = ones) per
  * output channel; 16 positions x [cin/32][cout][32] floats to `wpk`.  Returns the number of floats, or a negative error. */
 VSTAB_API long long vstab_host_pack_winograd(const float *W, const double *scale, int cin, int cout, float *wpk, long long cap);

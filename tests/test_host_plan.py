@@ -370,3 +370,131 @@ def test_winograd_operand_layout_is_the_blocked_layout_per_position():
                                   blocked_pack_np(want[xi].astype(np.float32))), xi
     assert _lib.lib().vstab_host_pack_winograd(Wt.ctypes.data_as(_lib.c_float_p), None, cin, cout, wpk.ctypes.data_as(_lib.c_float_p), n - 1) == -4
     assert _lib.lib().vstab_host_pack_winograd(None, None, cin, cout, wpk.ctypes.data_as(_lib.c_float_p), n) == -1
+
+
+# ---- how a filter gradient is launched (csrc/wgrad_mfma.hip: wgrad_choose_split; csrc/train_api.cpp: wgrad_split, wino_wgrad_shape), as
+# vstab_host_wgrad_split reports it: the cases of tests/test_gpu_wgrad_alone.py, each chosen for what its reduction hits
+def wgrad_split(M, cout, K, nbatch=0):
+    """(n_main, n_tail, ks_main, ks_tail) of the launches of a reduction over K pixels into M x cout"""
+    out = (C.c_int32 * 4)()
+    assert _lib.lib().vstab_host_wgrad_split(M, cout, K, nbatch, out) == 0, (M, cout, K, nbatch)
+    return tuple(out)
+
+
+def wgrad_case_K(case):
+    B, Hi, Wi, _, _, k, s, p = case
+    return B * ((Hi + 2 * p - k) // s + 1) * ((Wi + 2 * p - k) // s + 1)
+
+
+# (B, Hi, Wi, cin, cout, k, s, p), K = B*Ho*Wo (the symmetric-pad output size), (n_main, n_tail, ks_main, ks_tail)
+WGRAD_SPLIT_CASES = [
+    ((1, 1, 1, 4, 4, 3, 1, 1), 1, (4, 0, 1, 0)),              # one pixel, every tap but the centre outside the image, the K-1 clamp
+    ((1, 3, 5, 4, 4, 1, 1, 0), 15, (4, 0, 1, 0)),             # one partial tile, odd K
+    ((1, 4, 8, 8, 8, 1, 1, 0), 32, (8, 0, 1, 0)),             # exactly one tile
+    ((1, 3, 11, 8, 8, 1, 1, 0), 33, (8, 0, 1, 0)),            # the second tile holds one pixel
+    ((3, 5, 7, 8, 2, 3, 1, 1), 105, (2, 0, 1, 0)),            # cout = 2 (4-byte stores), K % 32 = 9, a tile straddles samples
+    ((1, 16, 16, 4, 4, 1, 1, 0), 256, (4, 0, 2, 0)),          # two slabs: the combine's tail loop only
+    ((1, 16, 17, 8, 64, 3, 1, 1), 272, (64, 0, 2, 0)),        # splits of 5 and 4 tiles, the <64> kernel with a full column tile
+    ((1, 24, 32, 4, 4, 1, 1, 0), 768, (4, 0, 6, 0)),          # six slabs: one unrolled group of four and a tail of two
+    ((2, 20, 26, 4, 8, 3, 1, 1), 1040, (8, 0, 7, 0)),         # seven slabs, the last split 3 tiles
+    ((5, 33, 37, 8, 12, 3, 2, 1), 1615, (12, 0, 11, 0)),      # the last split ONE tile; stride 2, odd sizes, K % 32 = 15
+    ((10, 12, 16, 32, 132, 3, 1, 1), 1920, (128, 4, 15, 15)),  # batch 10; the 128-wide part and a 4-column tail
+    ((1, 40, 41, 16, 388, 1, 1, 0), 1640, (384, 4, 13, 13)),  # 384 + 4 columns
+    ((1, 64, 131, 4, 68, 1, 1, 0), 8384, (68, 0, 53, 0)),     # the last split 2 tiles, the <128> kernel with 68 columns
+    ((10, 24, 32, 4, 2, 3, 1, 1), 7680, (2, 0, 60, 0)),       # cout = 2 under split-K: slabs and combine of 2-float rows
+    ((1, 128, 129, 4, 4, 1, 1, 0), 16512, (4, 0, 129, 0)),
+    ((1, 128, 256, 4, 4, 1, 1, 0), 32768, (4, 0, 256, 0)),    # the cap
+    ((10, 6, 8, 128, 256, 4, 2, 1), 120, (256, 0, 1, 0)),     # the deconv's geometry, M = 2048: 16 row tiles
+    ((1, 20, 24, 64, 64, 7, 2, 3), 120, (64, 0, 1, 0)),       # 7x7, M = 3136: a last row tile of 64 rows
+]
+# (B, H, W, cin, cout), T = B*ceil(H/2)*ceil(W/2), ksplit of the 16-plane batched launch
+WINO_WGRAD_SPLIT_CASES = [
+    ((1, 2, 2, 4, 4), 1, 1),                 # one tile
+    ((1, 3, 5, 8, 4), 6, 1),                 # ragged tiles
+    ((3, 9, 8, 32, 64), 60, 1),
+    ((2, 33, 20, 32, 192), 340, 2),          # two column tiles per plane, splits of 6 and 5 K-tiles
+    ((1, 64, 66, 4, 8), 1056, 7),            # 16 x 7 slabs, the last split 3 tiles
+]
+
+
+def wgrad_split_features(cases):
+    """what a table of (case, K, split) rows reaches in wgrad_mfma.hip, by name"""
+    hit = set()
+    for case, K, (n_main, n_tail, ks, ks_tail) in cases:
+        cout, M = case[4], case[5] * case[5] * case[3]
+        ktiles = (K + 31) // 32
+        kts = (ktiles + ks - 1) // ks                        # K-tiles per split (the kernel's own two lines)
+        last = ktiles - (ks - 1) * kts
+        assert 1 <= last <= kts
+        hit.add(f"ks={ks}")
+        if ks > 4:
+            hit.add(f"ks=4n+{ks % 4}")                       # the combine's unrolled groups of four, then a tail of ks % 4
+        if ks > 1 and last == 1:
+            hit.add("one-tile last split")
+        if ks > 1 and 1 < last < kts:
+            hit.add("short last split")
+        hit.add("one tile per split" if kts == 1 else "several tiles per split")
+        hit.add("K=1" if K == 1 else "K<32" if K < 32 else "K=32" if K == 32 else "K=33" if K == 33 else "K>33")
+        if K % 32:
+            hit.add("partial last tile")
+        if K > 33 and K % 2:
+            hit.add("odd K")
+        if cout % 4:
+            hit.add("cout%4 with ks=1" if ks == 1 else "cout%4 with ks>1")
+        if n_tail:
+            hit.add("main part plus tail")
+        hit.add("<64> kernel" if n_main <= 64 else "<128> kernel")
+        if M > 128:
+            hit.add("several row tiles")
+        if M > 128 and M % 128:
+            hit.add("partial last row tile")
+    return hit
+
+
+WGRAD_FEATURES = {"ks=1", "ks=2", "ks=4n+0", "ks=4n+1", "ks=4n+2", "ks=4n+3", "ks=256", "one-tile last split", "short last split",
+                  "one tile per split", "several tiles per split", "K=1", "K<32", "K=32", "K=33", "partial last tile", "odd K",
+                  "cout%4 with ks=1", "cout%4 with ks>1", "main part plus tail", "<64> kernel", "<128> kernel", "several row tiles",
+                  "partial last row tile"}
+
+
+def test_wgrad_split_cases():
+    L = _lib.lib()
+    for case, K, split in WGRAD_SPLIT_CASES:
+        B, Hi, Wi, cin, cout, k, s, p = case
+        assert wgrad_case_K(case) == K, case
+        assert wgrad_split(k * k * cin, cout, K) == split == wgrad_split(k * k * cin, cout, K, 1), case
+        n_main, n_tail, ks, ks_tail = split
+        assert n_main + n_tail == cout and (n_tail == 0) == (ks_tail == 0)
+        # the workspace the entry point asks for holds the larger of the two launches' slabs
+        Ho, Wo = (Hi + 2 * p - k) // s + 1, (Wi + 2 * p - k) // s + 1
+        slabs = max(ks * n_main if ks > 1 else 0, ks_tail * n_tail if ks_tail > 1 else 0) * k * k * cin * 4
+        assert L.vstab_conv_wgrad_workspace_bytes(B, Ho, Wo, k, cin, cout) >= slabs + 256
+    for (B, H, W, cin, cout), T, ks in WINO_WGRAD_SPLIT_CASES:
+        assert B * ((H + 1) // 2) * ((W + 1) // 2) == T
+        assert wgrad_split(cin, cout, T, 16) == (cout, 0, ks, 0), (B, H, W, cin, cout)
+        assert L.vstab_conv3x3_winograd_wgrad_workspace_bytes(B, H, W, cin, cout) >= (16 * ks * cin * cout * 4 if ks > 1 else 0) + 256
+    assert {ks for _, _, ks in WINO_WGRAD_SPLIT_CASES} >= {1, 2} and max(ks for _, _, ks in WINO_WGRAD_SPLIT_CASES) > 4
+
+
+def test_wgrad_split_cases_cover_every_path():
+    """a later change of the rule that moves a row off its purpose fails here (or above), not silently in the GPU file"""
+    hit = wgrad_split_features(WGRAD_SPLIT_CASES)
+    assert hit >= WGRAD_FEATURES, WGRAD_FEATURES - hit
+
+
+def test_wgrad_split_view_refusals_and_rule():
+    L = _lib.lib()
+    out = (C.c_int32 * 4)(7, 7, 7, 7)
+    assert L.vstab_host_wgrad_split(36, 4, 100, 0, None) == -1
+    for bad in ((0, 4, 100, 0), (36, 0, 100, 0), (36, 4, 0, 0), (36, 4, 100, 2), (36, 4, 100, -1), (6, 4, 100, 16), (8, 6, 100, 16)):
+        assert L.vstab_host_wgrad_split(*bad, out) == -1 and tuple(out) == (7, 7, 7, 7), bad
+    # the column rule: a tail of at most 32 columns behind at least one 128-column tile runs as a launch of its own
+    for cout, parts in ((128, (128, 0)), (129, (128, 1)), (160, (128, 32)), (161, (161, 0)), (127, (127, 0)), (388, (384, 4)), (2, (2, 0))):
+        assert wgrad_split(64, cout, 4096)[:2] == parts, cout
+    # every split the view reports is non-empty: (ks - 1) * ceil(ktiles / ks) < ktiles
+    for K in list(range(1, 200)) + [1000, 4095, 4096, 4097, 1 << 20]:
+        for M, cout in ((4, 4), (72, 64), (288, 128), (2048, 256), (4608, 512)):
+            ks = wgrad_split(M, cout, K)[2]
+            ktiles = (K + 31) // 32
+            assert 1 <= ks <= 256 and (ks - 1) * ((ktiles + ks - 1) // ks) < ktiles, (M, cout, K, ks)
+            assert ks == 1 or ktiles // ks >= 1 and ks <= max(ktiles // 4, 1)
