@@ -231,6 +231,40 @@ extern "C" int vstab_get_pixel_value(const float *img, const int32_t *x, const i
     return VSTAB_OK;
 }
 
+// ------------------------------------------------------------------------- backward of tf_warp, get_pixel_value and the flow glue
+extern "C" int vstab_warp_flow_backward(const float *img, const float *flow, const float *dout, int B, int H, int W, int C, float *d_img,
+                                        float *d_flow, int accumulate_img, void *stream)
+{
+    if (!img || !flow || !dout) return fail(nullptr, VSTAB_E_STATE, "warp_flow_backward: NULL buffer");
+    if (!d_img && !d_flow) return fail(nullptr, VSTAB_E_SHAPE, "warp_flow_backward: d_img and d_flow are both NULL");
+    if (B < 1 || H < 1 || W < 1 || C < 1 || (long long)H * W >= (1ll << 31) || (long long)B * H * W >= (1ll << 39))
+        return fail(nullptr, VSTAB_E_SHAPE, "warp_flow_backward: bad shape (H*W < 2^31, B*H*W < 2^39)");
+    if (((uintptr_t)flow | (uintptr_t)d_flow) & 7) return fail(nullptr, VSTAB_E_ALIGN, "warp_flow_backward: flow and d_flow must be 8-byte aligned");
+    TraceRange range("tf_warp backward");
+    HIP_TRY(nullptr, launch_warp_flow_backward(img, flow, dout, B, H, W, C, d_img, d_flow, accumulate_img ? 1 : 0, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_get_pixel_value_backward(const float *dout, const int32_t *x, const int32_t *y, float *d_img, int B, int H, int W, int C,
+                                              int Hi, int Wi, int accumulate, void *stream)
+{
+    if (!dout || !x || !y || !d_img) return fail(nullptr, VSTAB_E_STATE, "get_pixel_value_backward: NULL buffer");
+    if (B < 1 || H < 1 || W < 1 || C < 1 || Hi < 1 || Wi < 1 || (long long)H * W >= (1ll << 31) || (long long)B * H * W >= (1ll << 39))
+        return fail(nullptr, VSTAB_E_SHAPE, "get_pixel_value_backward: bad shape (H*W < 2^31, B*H*W < 2^39)");
+    HIP_TRY(nullptr, launch_get_pixel_value_backward(dout, x, y, d_img, B, H, W, C, Hi, Wi, accumulate ? 1 : 0, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_flow_resize_scale_backward(const float *dout, int B, int oh, int ow, float *d_flow, int h, int w, int net_h, int net_w,
+                                                void *stream)
+{
+    if (!dout || !d_flow) return fail(nullptr, VSTAB_E_STATE, "flow_resize_scale_backward: NULL buffer");
+    if (B < 1 || B > 65535 || h < 1 || w < 1 || oh < 1 || ow < 1 || net_h < 1 || net_w < 1 || (long long)h * w * 2 >= (1ll << 31))
+        return fail(nullptr, VSTAB_E_SHAPE, "flow_resize_scale_backward: bad shape (B <= 65535, h*w*2 < 2^31)");
+    HIP_TRY(nullptr, launch_flow_resize_scale_backward(dout, B, oh, ow, d_flow, h, w, net_h, net_w, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
 // ------------------------------------------------------------------------- secondary samplers
 extern "C" int vstab_st_transform(const float *img, int B, int H, int W, int C, const float *theta, int theta_dim,
                                   float *out, int oh, int ow, void *stream)

@@ -8,6 +8,7 @@
 #include "vstab_internal.h"
 #include "hbm_profile.h"
 #include "tile3.h"
+#include "warp_taps.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -610,29 +611,9 @@ hipError_t launch_resize_bilinear(const float *x, int B, int h, int w, int C, fl
 // zero, all four clipped into the image, weights from the CLIPPED corners (A.6).
 // The saturating v_cvt_i32_f32 keeps NaN/inf flows inside the image (no fault).
 // ---------------------------------------------------------------------------------
-// the four corners (a = (y0,x0), b = (y1,x0), c = (y0,x1), d = (y1,x1)) and weights of the sample point (x, y): the one statement
-// of tf_warp's arithmetic, for the pixel kernel and every tile kernel
-struct WarpTaps { int x0, x1, y0, y1; float wa, wb, wc, wd; };
-__device__ __forceinline__ WarpTaps tf_warp_taps(float x, float y, int H, int W)
-{
-    // Clamp BEFORE the conversion: float->int of an out-of-range value and x0 + 1 at INT_MAX are
-    // undefined in C++ (the optimiser folds the clips below around them and a NaN/inf flow then
-    // indexes out of bounds).  Inside [-2, W] nothing changes; outside, both corners still end
-    // up clipped to the same border pixel exactly as in the reference.
-    int x0 = (int)fminf(fmaxf(x, -2.f), (float)W), y0 = (int)fminf(fmaxf(y, -2.f), (float)H);
-    int x1 = x0 + 1, y1 = y0 + 1;
-    WarpTaps t;
-    t.x0 = min(max(x0, 0), W - 1); t.x1 = min(max(x1, 0), W - 1);
-    t.y0 = min(max(y0, 0), H - 1); t.y1 = min(max(y1, 0), H - 1);
-    const float x0f = (float)t.x0, x1f = (float)t.x1, y0f = (float)t.y0, y1f = (float)t.y1;
-    t.wa = (x1f - x) * (y1f - y); t.wb = (x1f - x) * (y - y0f);
-    t.wc = (x - x0f) * (y1f - y); t.wd = (x - x0f) * (y - y0f);
-    return t;
-}
-__device__ __forceinline__ float tf_warp_blend(const WarpTaps &t, float Ia, float Ib, float Ic, float Id)
-{
-    return ((t.wa * Ia + t.wb * Ib) + t.wc * Ic) + t.wd * Id;      // tf.add_n order
-}
+// The corners (a = (y0,x0), b = (y1,x0), c = (y0,x1), d = (y1,x1)), weights and blend of a sample point are tf_warp_taps /
+// tf_warp_blend of warp_taps.h, the one statement of tf_warp's arithmetic for the pixel kernel, every tile kernel and the backward
+// kernels (warp_flow_grad.hip).
 
 template <int C>
 __global__ __launch_bounds__(256) void warp_flow_kernel(const float *__restrict__ img, const float *__restrict__ flow,

@@ -597,9 +597,11 @@ __device__ __forceinline__ int nearest_ac_t(int i, float scale, int n_in) { retu
 
 // backward of tf.image.resize_images / UpSampling2dLayer (legacy bilinear): out = top + (bot - top) * ty with
 // top = tl + (tr - tl) * tx  =>  d out / d tl = (1-tx)(1-ty), tr: tx(1-ty), bl: (1-tx)ty, br: tx*ty
+// A gather over the output pixels whose taps reach the input element, in a fixed order: no atomics, bit-reproducible.  `gain` scales
+// the even channels and `gain_odd` the odd ones (the flow glue's x and y scalings; the one-gain entry passes the same value twice).
 __global__ __launch_bounds__(256) void resize_bilinear_bwd_kernel(const float *__restrict__ dout, int oh, int ow, int C,
                                                                   float *__restrict__ din, int h, int w, float ry, float rx,
-                                                                  float gain, int accumulate)
+                                                                  float gain, float gain_odd, int accumulate)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)gridDim.y * 0 + (long long)h * w * C;
@@ -623,7 +625,8 @@ __global__ __launch_bounds__(256) void resize_bilinear_bwd_kernel(const float *_
         }
     }
     float *o = din + ((long long)n * h * w) * C + idx;
-    *o = accumulate ? *o + gain * s : gain * s;
+    const float gn = (c & 1) ? gain_odd : gain;
+    *o = accumulate ? *o + gn * s : gn * s;
 }
 
 // F7 of the network: PadLayer(1) then nearest-neighbour resize with align_corners=True to H x W (model.py:795-802, 882-884)
@@ -724,7 +727,22 @@ hipError_t launch_resize_bilinear_backward(const float *dout, int B, int oh, int
 {
     const long long per = (long long)h * w * C;
     resize_bilinear_bwd_kernel<<<dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(
-        dout, oh, ow, C, din, h, w, (float)h / (float)oh, (float)w / (float)ow, gain, accumulate);
+        dout, oh, ow, C, din, h, w, (float)h / (float)oh, (float)w / (float)ow, gain, gain, accumulate);
+    return hipGetLastError();
+}
+
+// The adjoint of launch_flow_resize_scale (flow_ops.hip; main:497-498): out_x = resize(pf_x * net_h / h) * ow / net_w and
+// out_y = resize(pf_y * net_h / h) * oh / net_h are linear in pf, so d pf_c = gain_c * resize^T(dout_c) with one gain per channel,
+// gain_x = (net_h / h)(ow / net_w), gain_y = (net_h / h)(oh / net_h), each evaluated in double and rounded once.  The gather above
+// with two gains: no atomics, bit-reproducible.
+hipError_t launch_flow_resize_scale_backward(const float *dout, int B, int oh, int ow, float *d_flow, int h, int w, int net_h, int net_w,
+                                             hipStream_t stream)
+{
+    const double pre = (double)net_h / (double)h;
+    const float gx = (float)(pre * ((double)ow / (double)net_w)), gy = (float)(pre * ((double)oh / (double)net_h));
+    const long long per = (long long)h * w * 2;
+    resize_bilinear_bwd_kernel<<<dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(
+        dout, oh, ow, 2, d_flow, h, w, (float)h / (float)oh, (float)w / (float)ow, gx, gy, 0);
     return hipGetLastError();
 }
 

@@ -389,6 +389,14 @@ hipError_t launch_scale_shift(const float *x, long long npix, int C, float scale
                               hipStream_t stream);
 hipError_t launch_get_pixel_value(const float *img, const int32_t *x, const int32_t *y, float *out,
                                   int B, int H, int W, int C, int Hi, int Wi, hipStream_t stream);
+// backward of launch_warp_flow (d img by fp32 atomics, zeroed first unless accumulate_img; d flow by plain stores; either nullable)
+// and of launch_get_pixel_value (warp_flow_grad.hip); the adjoint of launch_flow_resize_scale, atomic-free (train_ops.hip)
+hipError_t launch_warp_flow_backward(const float *img, const float *flow, const float *dout, int B, int H, int W, int C, float *d_img,
+                                     float *d_flow, int accumulate_img, hipStream_t stream);
+hipError_t launch_get_pixel_value_backward(const float *dout, const int32_t *x, const int32_t *y, float *d_img, int B, int H, int W, int C,
+                                           int Hi, int Wi, int accumulate, hipStream_t stream);
+hipError_t launch_flow_resize_scale_backward(const float *dout, int B, int oh, int ow, float *d_flow, int h, int w, int net_h, int net_w,
+                                             hipStream_t stream);
 
 // ---------------------------------------------------------------------------------
 // Secondary samplers (sampler_ops.hip): spatial_transformer.py / warp.py rows S1-S3.

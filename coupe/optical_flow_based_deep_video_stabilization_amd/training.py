@@ -492,6 +492,68 @@ def vec2mtrx_backward(p, d_out, warp_type, warp_approx):
     return d_p
 
 
+def warp_flow_backward(img, flow, dout, need_img: bool = True, need_flow: bool = True, d_img=None):
+    """Gradients of warp_flow.tf_warp(img [B,H,W,C], flow [B,H,W,2]) for the output gradient dout [B,H,W,C]: (d img [B,H,W,C] or None,
+    d flow [B,H,W,2] or None) -- what TensorFlow's autodiff yields: the corner indices carry no gradient, the flow enters through the
+    four weights of the clipped corners only.  d_img, need_img as in st_transform_backward; need_flow False skips the flow gradient's
+    work.  d img is summed by float atomics (its last bits may differ between runs); d flow is bit-reproducible."""
+    need_img = need_img or d_img is not None
+    if not need_img and not need_flow:
+        return None, None
+    if not torch.is_tensor(img) or img.dim() != 4:
+        raise ValueError("img must be a float32 CUDA tensor [B,H,W,C]")
+    img, dout, (B, H, W, C, _, _), d_img, acc = _st_backward_args(img, dout, img.shape[1:3], d_img, need_img)
+    if not torch.is_tensor(flow) or flow.device != img.device or flow.dtype != torch.float32 or tuple(flow.shape) != (B, H, W, 2):
+        raise ValueError(f"flow must be a float32 tensor [{B},{H},{W},2] beside img")
+    flow = flow.contiguous()
+    d_flow = torch.empty_like(flow) if need_flow else None
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.lib().vstab_warp_flow_backward(img.data_ptr(), flow.data_ptr(), dout.data_ptr(), B, H, W, C,
+                                                       d_img.data_ptr() if need_img else None, d_flow.data_ptr() if need_flow else None,
+                                                       1 if acc else 0, runtime.stream_ptr()))
+    return (d_img if need_img else None), d_flow
+
+
+def get_pixel_value_backward(dout, x, y, img_hw, d_img=None):
+    """Gradient of warp_flow.get_pixel_value with respect to its image: dout [B,H,W,C] scattered into d img [B,Hi,Wi,C] (img_hw =
+    (Hi, Wi)) at the forward's clipped indices x, y (int32 [B,H,W]).  A given d_img is added into.  Float atomics: where several
+    indices meet, the last bits depend on the arrival order."""
+    if not torch.is_tensor(dout) or not dout.is_cuda or dout.dtype != torch.float32 or dout.dim() != 4:
+        raise ValueError("dout must be a float32 CUDA tensor [B,H,W,C]")
+    dout = dout.contiguous()
+    B, H, W, C = dout.shape
+    if tuple(x.shape) != (B, H, W) or tuple(y.shape) != (B, H, W):
+        raise ValueError(f"x and y must both be [{B},{H},{W}]")
+    x = x.to(device=dout.device, dtype=torch.int32).contiguous()
+    y = y.to(device=dout.device, dtype=torch.int32).contiguous()
+    Hi, Wi = int(img_hw[0]), int(img_hw[1])
+    acc = d_img is not None
+    if acc and (tuple(d_img.shape) != (B, Hi, Wi, C) or d_img.dtype != torch.float32 or d_img.device != dout.device or not d_img.is_contiguous()):
+        raise ValueError(f"d_img must be a contiguous float32 tensor [{B},{Hi},{Wi},{C}] beside dout")
+    if d_img is None:
+        d_img = torch.empty((B, Hi, Wi, C), dtype=torch.float32, device=dout.device)
+    with torch.cuda.device(dout.device):
+        _lib.check(_lib.lib().vstab_get_pixel_value_backward(dout.data_ptr(), x.data_ptr(), y.data_ptr(), d_img.data_ptr(), B, H, W, C, Hi, Wi,
+                                                             1 if acc else 0, runtime.stream_ptr()))
+    return d_img
+
+
+def flow_resize_scale_backward(dout, in_hw, net_h: int, net_w: int):
+    """Gradient of warp_flow.flow_to_output_res with respect to predict_flow2 [B,h,w,2] (in_hw = (h, w)) for the gradient dout
+    [B,oh,ow,2] of the output-resolution flow: (net_h / h) * resize^T(dout * (ow / net_w, oh / net_h)), one gain per channel.  A
+    gather in a fixed order: bit-reproducible."""
+    if not torch.is_tensor(dout) or not dout.is_cuda or dout.dtype != torch.float32 or dout.dim() != 4 or dout.shape[3] != 2:
+        raise ValueError("dout must be a float32 CUDA tensor [B,oh,ow,2]")
+    dout = dout.contiguous()
+    B, oh, ow, _ = dout.shape
+    h, w = int(in_hw[0]), int(in_hw[1])
+    d_flow = torch.empty((B, h, w, 2), dtype=torch.float32, device=dout.device)
+    with torch.cuda.device(dout.device):
+        _lib.check(_lib.lib().vstab_flow_resize_scale_backward(dout.data_ptr(), B, oh, ow, d_flow.data_ptr(), h, w, int(net_h), int(net_w),
+                                                               runtime.stream_ptr()))
+    return d_flow
+
+
 def st_elastic_transform_backward(img, theta, dout, out_size, g, linv_t, need_img: bool = True, need_theta: bool = True, d_img=None,
                                   interp='bilinear'):
     """Gradients of ElasticTransformer.transform (thin-plate spline, sampler `interp`) for the output gradient dout [B,oh,ow,C]:

@@ -168,6 +168,29 @@ VSTAB_API int vstab_stabilise_originalsize(vstab_ctx *ctx, const float *feats, i
 VSTAB_API int vstab_get_pixel_value(const float *img, const int32_t *x, const int32_t *y, float *out, int B,
                           int H, int W, int C, int Hi, int Wi, void *stream);
 
+/* ---- backward of tf_warp, get_pixel_value and the flow glue: what TensorFlow's autodiff yields for them.
+ * vstab_warp_flow_backward: dout [B,H,W,C] is the gradient of vstab_warp_flow's output.  tf_warp's corner indices come from integer
+ * casts and carry no gradient, so the flow enters through the four bilinear weights only:
+ *   d_flow [B,H,W,2]: d_fx = sum_c dout_c [(y1f-y)(Ic-Ia) + (y-y0f)(Id-Ib)]_c, d_fy = sum_c dout_c [(x1f-x)(Ib-Ia) + (x-x0f)(Id-Ic)]_c
+ *     with the CLIPPED corners (exactly 0 along an axis whose corners clip to one border pixel).  Plain stores, one thread per
+ *     pixel: bit-reproducible.
+ *   d_img [B,H,W,C]: the gather's adjoint with the forward's weights, added by fp32 atomics -- its last bits depend on the order
+ *     in which the contributions arrive.  Zeroed first unless accumulate_img.
+ * Either of d_img / d_flow may be NULL (that gradient's work is skipped; d_flow alone needs neither atomics nor the memset).  A NaN,
+ * infinite or huge flow stays in bounds (its taps are border pixels), as in the forward.  flow / d_flow 8-byte aligned.
+ * vstab_get_pixel_value_backward: dout[b,h,w,:] added to d_img[b, clip(y), clip(x), :] (the forward's clipping) by fp32 atomics;
+ * d_img [B,Hi,Wi,C] zeroed first unless `accumulate`.
+ * vstab_flow_resize_scale_backward: the adjoint of vstab_flow_resize_scale, d_flow [B,h,w,2] = gain_c * resize^T(dout [B,oh,ow,2])
+ * with gain_x = (net_h/h)(ow/net_w), gain_y = (net_h/h)(oh/net_h).  A gather in a fixed order, no atomics: bit-reproducible.
+ * VSTAB_E_STATE for a NULL buffer; VSTAB_E_SHAPE for a dimension < 1, H*W >= 2^31 (the glue: B > 65535 or h*w*2 >= 2^31) or
+ * d_img and d_flow both NULL (as the other samplers' backwards answer it); VSTAB_E_ALIGN for a misaligned flow / d_flow. */
+VSTAB_API int vstab_warp_flow_backward(const float *img, const float *flow, const float *dout, int B, int H, int W, int C,
+                                       float *d_img, float *d_flow, int accumulate_img, void *stream);
+VSTAB_API int vstab_get_pixel_value_backward(const float *dout, const int32_t *x, const int32_t *y, float *d_img, int B, int H, int W,
+                                             int C, int Hi, int Wi, int accumulate, void *stream);
+VSTAB_API int vstab_flow_resize_scale_backward(const float *dout, int B, int oh, int ow, float *d_flow, int h, int w, int net_h,
+                                               int net_w, void *stream);
+
 /* ---- secondary samplers named by north_star (never executed by the reference's live scripts) ---- */
 /* AffineTransformer.transform / ProjectiveTransformer.transform / transformer()
  * (spatial_transformer.py:400-452, 539-608, 34-38): theta [B,6] or [B,8] (theta_dim = 6 | 8; the
