@@ -215,6 +215,10 @@ EXPORTS = {
     "vstab_wino_gemm_stream_launch": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
 }
 
+INTERP = {'bilinear': 0, 'bicubic': 1}          # VSTAB_INTERP_*
+INTERP_NAMES = tuple(INTERP)                    # code -> name
+
+
 class LossLevelDesc(C.Structure):
     """vstab_loss_level_desc (include/vstab.h)."""
     _fields_ = [("pf", C.c_void_p), ("grad", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("cs_pf", C.c_int), ("cs_grad", C.c_int),

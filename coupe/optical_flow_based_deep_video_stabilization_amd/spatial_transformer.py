@@ -26,11 +26,10 @@ import ctypes
 
 import numpy as np
 import torch
-from torch.autograd.function import once_differentiable
 
-from . import _lib, runtime
+from . import _autograd, _lib, runtime
 
-_INTERP = {'bilinear': 0, 'bicubic': 1}          # VSTAB_INTERP_*
+_INTERP = _lib.INTERP
 
 
 def _f32_cuda(t, name):
@@ -55,8 +54,8 @@ def _repeat(x, n_repeats):
     return x.reshape(-1, 1).repeat(1, int(n_repeats)).reshape(-1)
 
 
-def _wants_grad(*tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+def _flat(d_theta):
+    return d_theta.reshape(-1) if d_theta is not None else None
 
 
 def _bilinear_interp_call(im, x, y, oh, ow):
@@ -68,23 +67,9 @@ def _bilinear_interp_call(im, x, y, oh, ow):
     return out
 
 
-class _BilinearInterpFn(torch.autograd.Function):
-    """bilinear_interp with its HIP backward (training.st_bilinear_interp_backward)."""
-
-    @staticmethod
-    def forward(ctx, im, x, y, oh, ow):
-        ctx.save_for_backward(im, x, y)
-        ctx.out_size = (oh, ow)
-        return _bilinear_interp_call(im, x, y, oh, ow)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        im, x, y = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        d_im, d_x, d_y = training.st_bilinear_interp_backward(im, x, y, dout, ctx.out_size, need_img=need[0], need_x=need[1], need_y=need[2])
-        return d_im, d_x, d_y, None, None
+def _bilinear_interp_backward(saved, dout, needs, out_size):
+    from . import training
+    return training.st_bilinear_interp_backward(*saved, dout, out_size, need_img=needs[0], need_x=needs[1], need_y=needs[2])
 
 
 def bilinear_interp(im, x, y, out_size):
@@ -99,9 +84,7 @@ def bilinear_interp(im, x, y, out_size):
     npix = oh * ow
     if x.numel() != B * npix or y.numel() != B * npix:
         raise ValueError(f"x/y must have B*out_h*out_w = {B * npix} elements")
-    if _wants_grad(im, x, y):
-        return _BilinearInterpFn.apply(im, x, y, oh, ow)
-    return _bilinear_interp_call(im, x, y, oh, ow)
+    return _autograd.apply(_bilinear_interp_call, _bilinear_interp_backward, (im, x, y), (oh, ow))
 
 
 def _bicubic_interp_call(im, x, y, oh, ow):
@@ -113,23 +96,9 @@ def _bicubic_interp_call(im, x, y, oh, ow):
     return out
 
 
-class _BicubicInterpFn(torch.autograd.Function):
-    """bicubic_interp with its HIP backward (training.st_bicubic_interp_backward)."""
-
-    @staticmethod
-    def forward(ctx, im, x, y, oh, ow):
-        ctx.save_for_backward(im, x, y)
-        ctx.out_size = (oh, ow)
-        return _bicubic_interp_call(im, x, y, oh, ow)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        im, x, y = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        d_im, d_x, d_y = training.st_bicubic_interp_backward(im, x, y, dout, ctx.out_size, need_img=need[0], need_x=need[1], need_y=need[2])
-        return d_im, d_x, d_y, None, None
+def _bicubic_interp_backward(saved, dout, needs, out_size):
+    from . import training
+    return training.st_bicubic_interp_backward(*saved, dout, out_size, need_img=needs[0], need_x=needs[1], need_y=needs[2])
 
 
 def bicubic_interp(im, x, y, out_size, differentiable=False):
@@ -145,9 +114,7 @@ def bicubic_interp(im, x, y, out_size, differentiable=False):
     npix = oh * ow
     if x.numel() != B * npix or y.numel() != B * npix:
         raise ValueError(f"x/y must have B*out_h*out_w = {B * npix} elements")
-    if differentiable and _wants_grad(im, x, y):
-        return _BicubicInterpFn.apply(im, x, y, oh, ow)
-    return _bicubic_interp_call(im, x, y, oh, ow)
+    return _autograd.apply(_bicubic_interp_call, _bicubic_interp_backward, (im, x, y), (oh, ow), differentiable)
 
 
 def _interpolate(im, x, y, out_size, method):
@@ -177,23 +144,12 @@ def _theta_transform_call(inp, theta, param_dim, oh, ow, interp):
     return out
 
 
-class _ThetaTransformFn(torch.autograd.Function):
-    """Affine / ProjectiveTransformer.transform with its HIP backward (training.st_transform_backward); theta flat, method the sampler."""
-
-    @staticmethod
-    def forward(ctx, inp, theta, param_dim, oh, ow, method='bilinear'):
-        ctx.save_for_backward(inp, theta)
-        ctx.out_size, ctx.method = (oh, ow), method
-        return _theta_transform_call(inp, theta, param_dim, oh, ow, _INTERP[method])
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        inp, theta = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        d_inp, d_theta = training.st_transform_backward(inp, theta, dout, ctx.out_size, need_img=need[0], need_theta=need[1], interp=ctx.method)
-        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None
+def _theta_transform_backward(saved, dout, needs, statics):
+    from . import training
+    _, oh, ow, interp = statics
+    d_inp, d_theta = training.st_transform_backward(*saved, dout, (oh, ow), need_img=needs[0], need_theta=needs[1],
+                                                    interp=_lib.INTERP_NAMES[interp])
+    return d_inp, _flat(d_theta)
 
 
 class _ThetaTransformer(object):
@@ -219,10 +175,8 @@ class _ThetaTransformer(object):
         theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
         if theta.numel() != B * self.param_dim:
             raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
-        oh, ow = self.out_size
-        if (interp == 0 or self.differentiable) and _wants_grad(inp, theta):
-            return _ThetaTransformFn.apply(inp, theta, self.param_dim, oh, ow, self.interp_method)
-        return _theta_transform_call(inp, theta, self.param_dim, oh, ow, interp)
+        return _autograd.apply(_theta_transform_call, _theta_transform_backward, (inp, theta), (self.param_dim, *self.out_size, interp),
+                               interp == 0 or self.differentiable)
 
 
 class AffineTransformer(_ThetaTransformer):
@@ -253,24 +207,12 @@ def _symmetry_transform_call(inp, theta, kind, oh, ow, interp):
     return out
 
 
-class _SymmetryTransformFn(torch.autograd.Function):
-    """The symmetric-pad transformers' transform with its HIP backward (training.st_symmetry_transform_backward); theta flat."""
-
-    @staticmethod
-    def forward(ctx, inp, theta, kind, oh, ow, method='bilinear'):
-        ctx.save_for_backward(inp, theta)
-        ctx.kind, ctx.out_size, ctx.method = kind, (oh, ow), method
-        return _symmetry_transform_call(inp, theta, kind, oh, ow, _INTERP[method])
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        inp, theta = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        d_inp, d_theta = training.st_symmetry_transform_backward(inp, theta, dout, ctx.out_size, ctx.kind, need_img=need[0], need_theta=need[1],
-                                                                 interp=ctx.method)
-        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None
+def _symmetry_transform_backward(saved, dout, needs, statics):
+    from . import training
+    kind, oh, ow, interp = statics
+    d_inp, d_theta = training.st_symmetry_transform_backward(*saved, dout, (oh, ow), kind, need_img=needs[0], need_theta=needs[1],
+                                                             interp=_lib.INTERP_NAMES[interp])
+    return d_inp, _flat(d_theta)
 
 
 class _SymmetryTransformer(object):
@@ -302,10 +244,8 @@ class _SymmetryTransformer(object):
         if H < 100 or W < 100:
             raise ValueError(f"{type(self).__name__}: the 100-pixel symmetric pad needs H, W >= 100, got {H}x{W}")
         theta = self._theta(theta, B)
-        oh, ow = self.out_size
-        if (interp == 0 or self.differentiable) and _wants_grad(inp, theta):
-            return _SymmetryTransformFn.apply(inp, theta, self.kind, oh, ow, self.interp_method)
-        return _symmetry_transform_call(inp, theta, self.kind, oh, ow, interp)
+        return _autograd.apply(_symmetry_transform_call, _symmetry_transform_backward, (inp, theta), (self.kind, *self.out_size, interp),
+                               interp == 0 or self.differentiable)
 
     def matrix(self, theta):
         """theta [B, param_dim] -> [B,3,3]: the pre-mapped matrices `transform` multiplies the grid by (affine kinds: last row 0 0 1),
@@ -382,7 +322,7 @@ def _tps_linv(g):
     return buf
 
 
-def _elastic_transform_call(inp, theta, g, linv_t, oh, ow, interp):
+def _elastic_transform_call(inp, theta, linv_t, g, oh, ow, interp):
     B, H, W, Cc = inp.shape
     out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
     with torch.cuda.device(inp.device):
@@ -391,24 +331,13 @@ def _elastic_transform_call(inp, theta, g, linv_t, oh, ow, interp):
     return out
 
 
-class _ElasticTransformFn(torch.autograd.Function):
-    """ElasticTransformer.transform with its HIP backward (training.st_elastic_transform_backward); theta flat."""
-
-    @staticmethod
-    def forward(ctx, inp, theta, g, linv_t, oh, ow, method='bilinear'):
-        ctx.save_for_backward(inp, theta, linv_t)
-        ctx.g, ctx.out_size, ctx.method = g, (oh, ow), method
-        return _elastic_transform_call(inp, theta, g, linv_t, oh, ow, _INTERP[method])
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        inp, theta, linv_t = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        d_inp, d_theta = training.st_elastic_transform_backward(inp, theta, dout, ctx.out_size, ctx.g, linv_t, need_img=need[0], need_theta=need[1],
-                                                                interp=ctx.method)
-        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None, None, None, None, None
+def _elastic_transform_backward(saved, dout, needs, statics):
+    from . import training
+    inp, theta, linv_t = saved
+    g, oh, ow, interp = statics
+    d_inp, d_theta = training.st_elastic_transform_backward(inp, theta, dout, (oh, ow), g, linv_t, need_img=needs[0], need_theta=needs[1],
+                                                            interp=_lib.INTERP_NAMES[interp])
+    return d_inp, _flat(d_theta), None
 
 
 class ElasticTransformer(object):
@@ -451,10 +380,8 @@ class ElasticTransformer(object):
         theta = self._theta(theta, B)
         if theta.device != inp.device:
             raise ValueError("theta must be on inp's device")
-        oh, ow = self.out_size
-        if (interp == 0 or self.differentiable) and _wants_grad(inp, theta):
-            return _ElasticTransformFn.apply(inp, theta, self.grid_size, self.L_inv, oh, ow, self.interp_method)
-        return _elastic_transform_call(inp, theta, self.grid_size, self.L_inv, oh, ow, interp)
+        return _autograd.apply(_elastic_transform_call, _elastic_transform_backward, (inp, theta, self.L_inv),
+                               (self.grid_size, *self.out_size, interp), interp == 0 or self.differentiable)
 
     def transform_coords(self, theta):
         """theta [B, 2*g*g] -> (x_s, y_s), each flat [B*oh*ow]: the normalised source coordinates `transform` samples at (the
@@ -506,24 +433,11 @@ def _bilinear_interp3d_call(vol, x, y, z, out_size, edge_size):
     return out
 
 
-class _BilinearInterp3dFn(torch.autograd.Function):
-    """bilinear_interp3d with its HIP backward (training.st3d_bilinear_interp_backward)."""
-
-    @staticmethod
-    def forward(ctx, vol, x, y, z, out_size, edge_size):
-        ctx.save_for_backward(vol, x, y, z)
-        ctx.out_size, ctx.edge_size = out_size, edge_size
-        return _bilinear_interp3d_call(vol, x, y, z, out_size, edge_size)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        vol, x, y, z = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        grads = training.st3d_bilinear_interp_backward(vol, x, y, z, dout, ctx.out_size, edge_size=ctx.edge_size, need_vol=need[0],
-                                                       need_x=need[1], need_y=need[2], need_z=need[3])
-        return (*grads, None, None)
+def _bilinear_interp3d_backward(saved, dout, needs, statics):
+    from . import training
+    out_size, edge_size = statics
+    return training.st3d_bilinear_interp_backward(*saved, dout, out_size, edge_size=edge_size, need_vol=needs[0], need_x=needs[1],
+                                                  need_y=needs[2], need_z=needs[3])
 
 
 def bilinear_interp3d(vol, x, y, z, out_size, edge_size=1):
@@ -540,9 +454,7 @@ def bilinear_interp3d(vol, x, y, z, out_size, edge_size=1):
     x, y, z = (_f32_cuda(t.to(torch.float32), n).reshape(-1) for t, n in ((x, "x"), (y, "y"), (z, "z")))
     if x.numel() != nvox or y.numel() != nvox or z.numel() != nvox:
         raise ValueError(f"x/y/z must have B*out_d*out_h*out_w = {nvox} elements")
-    if _wants_grad(vol, x, y, z):
-        return _BilinearInterp3dFn.apply(vol, x, y, z, out_size, edge_size)
-    return _bilinear_interp3d_call(vol, x, y, z, out_size, edge_size)
+    return _autograd.apply(_bilinear_interp3d_call, _bilinear_interp3d_backward, (vol, x, y, z), (out_size, edge_size))
 
 
 def _interpolate3d(vol, x, y, z, out_size, method='bilinear'):
@@ -559,23 +471,11 @@ def _volume_transform_call(inp, theta, out_size):
     return out
 
 
-class _VolumeTransformFn(torch.autograd.Function):
-    """AffineVolumeTransformer.transform with its HIP backward (training.st3d_transform_backward); theta flat."""
-
-    @staticmethod
-    def forward(ctx, inp, theta, out_size):
-        ctx.save_for_backward(inp, theta)
-        ctx.out_size = out_size
-        return _volume_transform_call(inp, theta, out_size)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        inp, theta = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        d_inp, d_theta = training.st3d_transform_backward(inp, theta, dout, ctx.out_size, need_vol=need[0], need_theta=need[1])
-        return d_inp, (d_theta.reshape(-1) if d_theta is not None else None), None
+def _volume_transform_backward(saved, dout, needs, statics):
+    from . import training
+    (out_size,) = statics
+    d_inp, d_theta = training.st3d_transform_backward(*saved, dout, out_size, need_vol=needs[0], need_theta=needs[1])
+    return d_inp, _flat(d_theta)
 
 
 class AffineVolumeTransformer(object):
@@ -602,9 +502,7 @@ class AffineVolumeTransformer(object):
         theta = _f32_cuda(theta.to(torch.float32), "theta").reshape(-1)
         if theta.numel() != B * self.param_dim:
             raise ValueError(f"theta must have shape [{B}, {self.param_dim}]")
-        if _wants_grad(inp, theta):
-            return _VolumeTransformFn.apply(inp, theta, self.out_size)
-        return _volume_transform_call(inp, theta, self.out_size)
+        return _autograd.apply(_volume_transform_call, _volume_transform_backward, (inp, theta), (self.out_size,))
 
 
 def transformer(inp, theta, out_size, name='SpatialTransformer', **kwargs):

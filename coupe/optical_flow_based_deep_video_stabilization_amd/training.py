@@ -349,29 +349,45 @@ def resize_bilinear_backward(dout, in_hw, gain: float = 1.0, din=None):
     return din
 
 
-def _st_backward_args(img, dout, out_hw, d_img, need_img):
-    if not torch.is_tensor(img) or not img.is_cuda or img.dtype != torch.float32 or img.dim() != 4:
-        raise ValueError("img must be a float32 CUDA tensor [B,H,W,C]")
-    img = img.contiguous()
-    B, H, W, C = img.shape
-    oh, ow = int(out_hw[0]), int(out_hw[1])
-    if not torch.is_tensor(dout) or dout.device != img.device or dout.dtype != torch.float32 or dout.numel() != B * oh * ow * C:
-        raise ValueError(f"dout must be a float32 tensor of {B}*{oh}*{ow}*{C} elements beside img")
-    acc = d_img is not None
-    if acc and (d_img.shape != img.shape or d_img.dtype != torch.float32 or d_img.device != img.device or not d_img.is_contiguous()):
-        raise ValueError("d_img must be a contiguous float32 tensor of img's shape beside it")
-    if d_img is None and need_img:
-        d_img = torch.empty_like(img)
-    return img, dout.contiguous(), (B, H, W, C, oh, ow), d_img, acc
+def _st_backward_args(src, dout, out_size, d_src, need_src, rank=4):
+    """The checks every sampler backward makes of its input (rank 4: img [B,H,W,C], out_size (oh, ow); rank 5: vol [B,D,H,W,C],
+    out_size (od, oh, ow)), of dout and of a given gradient to add into -> (src, dout, src's shape + out_size, d_src, accumulate)."""
+    name, layout = ("img", "[B,H,W,C]") if rank == 4 else ("vol", "[B,D,H,W,C]")
+    if not torch.is_tensor(src) or not src.is_cuda or src.dtype != torch.float32 or src.dim() != rank:
+        raise ValueError(f"{name} must be a float32 CUDA tensor {layout}")
+    src = src.contiguous()
+    out = tuple(int(out_size[i]) for i in range(rank - 2))
+    counts = (src.shape[0], *out, src.shape[-1])
+    if not torch.is_tensor(dout) or dout.device != src.device or dout.dtype != torch.float32 or dout.numel() != math.prod(counts):
+        raise ValueError(f"dout must be a float32 tensor of {'*'.join(map(str, counts))} elements beside {name}")
+    acc = d_src is not None
+    if acc and (d_src.shape != src.shape or d_src.dtype != torch.float32 or d_src.device != src.device or not d_src.is_contiguous()):
+        raise ValueError(f"d_{name} must be a contiguous float32 tensor of {name}'s shape beside it")
+    if d_src is None and need_src:
+        d_src = torch.empty_like(src)
+    return src, dout.contiguous(), (*src.shape, *out), d_src, acc
 
 
-_ST_INTERP = {'bilinear': 0, 'bicubic': 1}          # VSTAB_INTERP_*
+def _backward_with_param_grad(entry, head, dout, out_size, d_src, acc, need_src, need_par, par_shape, ws_query, ws_args):
+    """The call every sampler backward with a parameter gradient makes: entry(*head, dout, *out_size, d_src, accumulate, d_par,
+    workspace, workspace_bytes, stream) -> (d_src or None, d_par or None).  entry and ws_query are the library's functions.  The
+    parameter gradient [par_shape] and the workspace the library asks for (ws_query(*ws_args) bytes; never an empty allocation)
+    exist only when need_par."""
+    d_par, ws, n = None, None, 0
+    if need_par:
+        d_par = torch.empty(par_shape, dtype=torch.float32, device=dout.device)
+        n = int(ws_query(*ws_args))
+        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=dout.device)
+    with torch.cuda.device(dout.device):
+        _lib.check(entry(*head, dout.data_ptr(), *out_size, d_src.data_ptr() if need_src else None, 1 if acc else 0,
+                                     d_par.data_ptr() if need_par else None, ws.data_ptr() if need_par else None, n, runtime.stream_ptr()))
+    return (d_src if need_src else None), d_par
 
 
 def _st_interp(interp):
-    if interp not in _ST_INTERP:
+    if interp not in _lib.INTERP:
         raise ValueError("interp must be 'bilinear' or 'bicubic'")
-    return _ST_INTERP[interp]
+    return _lib.INTERP[interp]
 
 
 def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, need_theta: bool = True, d_img=None, interp='bilinear'):
@@ -387,20 +403,10 @@ def st_transform_backward(img, theta, dout, out_size, need_img: bool = True, nee
     if not theta.is_cuda or theta.dtype != torch.float32 or theta.numel() not in (6 * B, 8 * B):
         raise ValueError("theta must be a float32 CUDA tensor [B,6] or [B,8]")
     tdim = theta.numel() // B
-    L = _lib.lib()
-    d_theta, ws, n = None, None, 0
-    if need_theta:
-        d_theta = torch.empty((B, tdim), dtype=torch.float32, device=img.device)
-        n = int(L.vstab_st_transform_backward_workspace_bytes(B, H, W, C, oh, ow))
-        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
-    with torch.cuda.device(img.device):
-        tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_theta.data_ptr() if need_theta else None,
-                ws.data_ptr() if need_theta else None, n, runtime.stream_ptr())
-        if ip == 0:
-            _lib.check(L.vstab_st_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), tdim, *tail))
-        else:
-            _lib.check(L.vstab_st_transform_interp_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), tdim, ip, *tail))
-    return (d_img if need_img else None), d_theta
+    L, head = _lib.lib(), (img.data_ptr(), B, H, W, C, theta.data_ptr(), tdim)
+    entry, head = (L.vstab_st_transform_backward, head) if ip == 0 else (L.vstab_st_transform_interp_backward, (*head, ip))
+    return _backward_with_param_grad(entry, head, dout, (oh, ow), d_img, acc, need_img, need_theta, (B, tdim),
+                                     L.vstab_st_transform_backward_workspace_bytes, (B, H, W, C, oh, ow))
 
 
 _SYM_THETA_DIM = {0: 6, 1: 8, 2: 4}          # VSTAB_SYM_AFFINE, _PROJECTIVE, _SIMILARITY
@@ -426,20 +432,10 @@ def st_symmetry_transform_backward(img, theta, dout, out_size, kind, need_img: b
     theta = theta.contiguous()
     if not theta.is_cuda or theta.dtype != torch.float32 or theta.numel() != tdim * B:
         raise ValueError(f"theta must be a float32 CUDA tensor [B,{tdim}]")
-    L = _lib.lib()
-    d_theta, ws, n = None, None, 0
-    if need_theta:
-        d_theta = torch.empty((B, tdim), dtype=torch.float32, device=img.device)
-        n = int(L.vstab_st_symmetry_transform_backward_workspace_bytes(B, H, W, C, oh, ow))
-        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
-    with torch.cuda.device(img.device):
-        tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_theta.data_ptr() if need_theta else None,
-                ws.data_ptr() if need_theta else None, n, runtime.stream_ptr())
-        if ip == 0:
-            _lib.check(L.vstab_st_symmetry_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), kind, *tail))
-        else:
-            _lib.check(L.vstab_st_symmetry_transform_interp_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), kind, ip, *tail))
-    return (d_img if need_img else None), d_theta
+    L, head = _lib.lib(), (img.data_ptr(), B, H, W, C, theta.data_ptr(), kind)
+    entry, head = (L.vstab_st_symmetry_transform_backward, head) if ip == 0 else (L.vstab_st_symmetry_transform_interp_backward, (*head, ip))
+    return _backward_with_param_grad(entry, head, dout, (oh, ow), d_img, acc, need_img, need_theta, (B, tdim),
+                                     L.vstab_st_symmetry_transform_backward_workspace_bytes, (B, H, W, C, oh, ow))
 
 
 def homography_warp_backward(img, M, dout, out_size, need_img: bool = True, need_M: bool = True, d_img=None, ref=None):
@@ -453,24 +449,16 @@ def homography_warp_backward(img, M, dout, out_size, need_img: bool = True, need
     if not torch.is_tensor(M) or M.device != img.device or M.dtype != torch.float32 or M.numel() != 9 * B:
         raise ValueError("M must be a float32 tensor [B,9] or [B,3,3] beside img")
     M = M.contiguous()
-    if ref is not None:
+    L = _lib.lib()
+    if ref is None:
+        entry, head = L.vstab_homography_warp_backward, (img.data_ptr(), B, H, W, C, M.data_ptr())
+    else:
         if not torch.is_tensor(ref) or ref.device != img.device or ref.dtype != torch.float32 or ref.numel() != 9:
             raise ValueError("ref must be a float32 tensor of 9 elements beside img")
         ref = ref.contiguous()
-    L = _lib.lib()
-    d_M, ws, n = None, None, 0
-    if need_M:
-        d_M = torch.empty((B, 3, 3), dtype=torch.float32, device=img.device)
-        n = int(L.vstab_homography_warp_backward_workspace_bytes(B, H, W, C, oh, ow))
-        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
-    tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_M.data_ptr() if need_M else None,
-            ws.data_ptr() if need_M else None, n, runtime.stream_ptr())
-    with torch.cuda.device(img.device):
-        if ref is None:
-            _lib.check(L.vstab_homography_warp_backward(img.data_ptr(), B, H, W, C, M.data_ptr(), *tail))
-        else:
-            _lib.check(L.vstab_transform_image_backward(img.data_ptr(), B, H, W, C, ref.data_ptr(), M.data_ptr(), *tail))
-    return (d_img if need_img else None), d_M
+        entry, head = L.vstab_transform_image_backward, (img.data_ptr(), B, H, W, C, ref.data_ptr(), M.data_ptr())
+    return _backward_with_param_grad(entry, head, dout, (oh, ow), d_img, acc, need_img, need_M, (B, 3, 3),
+                                     L.vstab_homography_warp_backward_workspace_bytes, (B, H, W, C, oh, ow))
 
 
 def vec2mtrx_backward(p, d_out, warp_type, warp_approx):
@@ -571,20 +559,10 @@ def st_elastic_transform_backward(img, theta, dout, out_size, g, linv_t, need_im
     if not torch.is_tensor(linv_t) or linv_t.device != img.device or linv_t.dtype != torch.float32 or linv_t.numel() != K * (K + 3):
         raise ValueError(f"linv_t must be a float32 tensor [{K}, {K + 3}] beside img")
     linv_t = linv_t.contiguous()
-    L = _lib.lib()
-    d_theta, ws, n = None, None, 0
-    if need_theta:
-        d_theta = torch.empty((B, 2 * K), dtype=torch.float32, device=img.device)
-        n = int(L.vstab_st_elastic_transform_backward_workspace_bytes(B, H, W, C, g, oh, ow))
-        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=img.device)
-    with torch.cuda.device(img.device):
-        tail = (dout.data_ptr(), oh, ow, d_img.data_ptr() if need_img else None, 1 if acc else 0, d_theta.data_ptr() if need_theta else None,
-                ws.data_ptr() if need_theta else None, n, runtime.stream_ptr())
-        if ip == 0:
-            _lib.check(L.vstab_st_elastic_transform_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), g, linv_t.data_ptr(), *tail))
-        else:
-            _lib.check(L.vstab_st_elastic_transform_interp_backward(img.data_ptr(), B, H, W, C, theta.data_ptr(), g, linv_t.data_ptr(), ip, *tail))
-    return (d_img if need_img else None), d_theta
+    L, head = _lib.lib(), (img.data_ptr(), B, H, W, C, theta.data_ptr(), g, linv_t.data_ptr())
+    entry, head = (L.vstab_st_elastic_transform_backward, head) if ip == 0 else (L.vstab_st_elastic_transform_interp_backward, (*head, ip))
+    return _backward_with_param_grad(entry, head, dout, (oh, ow), d_img, acc, need_img, need_theta, (B, 2 * K),
+                                     L.vstab_st_elastic_transform_backward_workspace_bytes, (B, H, W, C, g, oh, ow))
 
 
 def st_bilinear_interp_backward(img, x, y, dout, out_size, need_img: bool = True, need_x: bool = True, need_y: bool = True, d_img=None):
@@ -615,44 +593,20 @@ def _st_interp_backward(entry, img, x, y, dout, out_size, need_img, need_x, need
     return (d_img if need_img else None), d_x, d_y
 
 
-def _st3d_backward_args(vol, dout, out_size, d_vol, need_vol):
-    if not torch.is_tensor(vol) or not vol.is_cuda or vol.dtype != torch.float32 or vol.dim() != 5:
-        raise ValueError("vol must be a float32 CUDA tensor [B,D,H,W,C]")
-    vol = vol.contiguous()
-    B, D, H, W, C = vol.shape
-    od, oh, ow = int(out_size[0]), int(out_size[1]), int(out_size[2])
-    if not torch.is_tensor(dout) or dout.device != vol.device or dout.dtype != torch.float32 or dout.numel() != B * od * oh * ow * C:
-        raise ValueError(f"dout must be a float32 tensor of {B}*{od}*{oh}*{ow}*{C} elements beside vol")
-    acc = d_vol is not None
-    if acc and (d_vol.shape != vol.shape or d_vol.dtype != torch.float32 or d_vol.device != vol.device or not d_vol.is_contiguous()):
-        raise ValueError("d_vol must be a contiguous float32 tensor of vol's shape beside it")
-    if d_vol is None and need_vol:
-        d_vol = torch.empty_like(vol)
-    return vol, dout.contiguous(), (B, D, H, W, C, od, oh, ow), d_vol, acc
-
-
 def st3d_transform_backward(vol, theta, dout, out_size, need_vol: bool = True, need_theta: bool = True, d_vol=None):
     """Gradients of AffineVolumeTransformer.transform for the output gradient dout [B,od,oh,ow,C]: (d vol [B,D,H,W,C] or None,
     d theta [B,12] or None).  A given d_vol is added into, otherwise it is allocated and overwritten; need_vol / need_theta False
     skips that gradient's work.  d vol is summed by float atomics (its last bits may differ between runs); d theta is
     bit-reproducible."""
     need_vol = need_vol or d_vol is not None
-    vol, dout, (B, D, H, W, C, od, oh, ow), d_vol, acc = _st3d_backward_args(vol, dout, out_size, d_vol, need_vol)
+    vol, dout, (B, D, H, W, C, od, oh, ow), d_vol, acc = _st_backward_args(vol, dout, out_size, d_vol, need_vol, rank=5)
     theta = theta.contiguous()
     if not theta.is_cuda or theta.dtype != torch.float32 or theta.numel() != 12 * B:
         raise ValueError("theta must be a float32 CUDA tensor [B,12]")
     L = _lib.lib()
-    d_theta, ws, n = None, None, 0
-    if need_theta:
-        d_theta = torch.empty((B, 12), dtype=torch.float32, device=vol.device)
-        n = int(L.vstab_st3d_transform_backward_workspace_bytes(B, D, H, W, C, od, oh, ow))
-        ws = torch.empty(max(n, 8), dtype=torch.uint8, device=vol.device)
-    with torch.cuda.device(vol.device):
-        _lib.check(L.vstab_st3d_transform_backward(vol.data_ptr(), B, D, H, W, C, theta.data_ptr(), dout.data_ptr(), od, oh, ow,
-                                                   d_vol.data_ptr() if need_vol else None, 1 if acc else 0,
-                                                   d_theta.data_ptr() if need_theta else None, ws.data_ptr() if need_theta else None, n,
-                                                   runtime.stream_ptr()))
-    return (d_vol if need_vol else None), d_theta
+    return _backward_with_param_grad(L.vstab_st3d_transform_backward, (vol.data_ptr(), B, D, H, W, C, theta.data_ptr()), dout, (od, oh, ow),
+                                     d_vol, acc, need_vol, need_theta, (B, 12), L.vstab_st3d_transform_backward_workspace_bytes,
+                                     (B, D, H, W, C, od, oh, ow))
 
 
 def st3d_bilinear_interp_backward(vol, x, y, z, dout, out_size, edge_size: int = 1, need_vol: bool = True, need_x: bool = True,
@@ -660,7 +614,7 @@ def st3d_bilinear_interp_backward(vol, x, y, z, dout, out_size, edge_size: int =
     """Gradients of bilinear_interp3d(vol, x, y, z, out_size, edge_size) for dout [B*od*oh*ow, C]: (d vol or None, d x [B*od*oh*ow]
     or None, d y or None, d z or None); d_vol as in st3d_transform_backward."""
     need_vol = need_vol or d_vol is not None
-    vol, dout, (B, D, H, W, C, od, oh, ow), d_vol, acc = _st3d_backward_args(vol, dout, out_size, d_vol, need_vol)
+    vol, dout, (B, D, H, W, C, od, oh, ow), d_vol, acc = _st_backward_args(vol, dout, out_size, d_vol, need_vol, rank=5)
     x, y, z = x.contiguous().reshape(-1), y.contiguous().reshape(-1), z.contiguous().reshape(-1)
     for t in (x, y, z):
         if not t.is_cuda or t.dtype != torch.float32 or t.numel() != B * od * oh * ow:

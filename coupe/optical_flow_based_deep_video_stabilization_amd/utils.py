@@ -22,6 +22,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, runtime
+from ._autograd import wants_grad as _wants_grad
 
 _MAX_SIZE = 11
 
@@ -58,10 +59,6 @@ def _pair(img1, img2, size, sigma):
     if a.shape[0] < 1 or a.shape[1] < size or a.shape[2] < size:
         raise ValueError(f"images of {a.shape[1]}x{a.shape[2]} are smaller than the {size}x{size} window")
     return a, b, size, float(sigma)
-
-
-def _wants_grad(*tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
 
 
 def _ssim_call(a, b, size, sigma, want_map, want_means):

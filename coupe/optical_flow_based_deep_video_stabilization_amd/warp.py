@@ -14,9 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 import torch
-from torch.autograd.function import once_differentiable
 
-from . import _lib, runtime
+from . import _autograd, _lib, runtime
 
 
 def fit(Xsrc, Xdst):
@@ -49,11 +48,7 @@ def _f32_cuda(t, name):
     return t.to(torch.float32).contiguous()
 
 
-def _wants_grad(*tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
-
-
-def _vec2mtrx_call(p, dim, approx):
+def _vec2mtrx_call(p, warp_type, dim, approx):
     B = p.shape[0]
     out = torch.empty((B, 3, 3), dtype=torch.float32, device=p.device)
     with torch.cuda.device(p.device):
@@ -61,21 +56,10 @@ def _vec2mtrx_call(p, dim, approx):
     return out
 
 
-class _Vec2MtrxFn(torch.autograd.Function):
-    """vec2mtrx with its HIP backward (training.vec2mtrx_backward)."""
-
-    @staticmethod
-    def forward(ctx, p, warp_type, dim, approx):
-        ctx.save_for_backward(p)
-        ctx.warp_type, ctx.approx = warp_type, approx
-        return _vec2mtrx_call(p, dim, approx)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d_out):
-        from . import training
-        (p,) = ctx.saved_tensors
-        return training.vec2mtrx_backward(p, d_out, ctx.warp_type, ctx.approx), None, None, None
+def _vec2mtrx_backward(saved, d_out, needs, statics):
+    from . import training
+    warp_type, _, approx = statics
+    return (training.vec2mtrx_backward(saved[0], d_out, warp_type, approx),)
 
 
 def vec2mtrx(config, p):
@@ -90,9 +74,7 @@ def vec2mtrx(config, p):
         raise AssertionError("warpType must be 'homography' or 'affine'")
     if p.shape[1] != dim:
         raise ValueError(f"p must be [B,{dim}] for warpType={config.warpType}")
-    if _wants_grad(p):
-        return _Vec2MtrxFn.apply(p, config.warpType, dim, int(config.warpApprox))
-    return _vec2mtrx_call(p, dim, int(config.warpApprox))
+    return _autograd.apply(_vec2mtrx_call, _vec2mtrx_backward, (p,), (config.warpType, dim, int(config.warpApprox)))
 
 
 def _warp_call(image, mat, ref, oh, ow):
@@ -110,29 +92,17 @@ def _warp_call(image, mat, ref, oh, ow):
     return out
 
 
-class _WarpFn(torch.autograd.Function):
-    """The homography warp with its HIP backward (training.homography_warp_backward): d image and d M, or with ref d pMtrx."""
-
-    @staticmethod
-    def forward(ctx, image, mat, ref, oh, ow):
-        ctx.save_for_backward(image, mat)
-        ctx.ref, ctx.out_size = ref, (oh, ow)
-        return _warp_call(image, mat, ref, oh, ow)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        image, mat = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        d_img, d_mat = training.homography_warp_backward(image, mat, dout, ctx.out_size, need_img=need[0], need_M=need[1], ref=ctx.ref)
-        return d_img, (d_mat.reshape(mat.shape) if d_mat is not None else None), None, None, None
+def _warp_backward(saved, dout, needs, statics):
+    """d image and d M, or with ref d pMtrx."""
+    from . import training
+    image, mat = saved
+    ref, oh, ow = statics
+    d_img, d_mat = training.homography_warp_backward(image, mat, dout, (oh, ow), need_img=needs[0], need_M=needs[1], ref=ref)
+    return d_img, (d_mat.reshape(mat.shape) if d_mat is not None else None)
 
 
 def _warp(image, mat, ref, oh, ow):
-    if _wants_grad(image, mat):
-        return _WarpFn.apply(image, mat, ref, oh, ow)
-    return _warp_call(image, mat, ref, oh, ow)
+    return _autograd.apply(_warp_call, _warp_backward, (image, mat), (ref, oh, ow))
 
 
 def warpImage(image, M, oh, ow):

@@ -16,17 +16,14 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib, runtime
+from . import _autograd, _lib, runtime
+from ._autograd import wants_grad as _wants_grad
 
 
 def _f32_cuda(t, name):
     if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
         raise ValueError(f"{name} must be a float32 CUDA tensor")
     return t.contiguous()
-
-
-def _wants_grad(*tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
 
 
 def _tf_warp_call(img, flow):
@@ -38,21 +35,10 @@ def _tf_warp_call(img, flow):
     return out
 
 
-class _TfWarpFn(torch.autograd.Function):
-    """tf_warp with its HIP backward (training.warp_flow_backward): d img and / or d flow, whichever is needed."""
-
-    @staticmethod
-    def forward(ctx, img, flow):
-        ctx.save_for_backward(img, flow)
-        return _tf_warp_call(img, flow)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dout):
-        from . import training
-        img, flow = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        return training.warp_flow_backward(img, flow, dout, need_img=need[0], need_flow=need[1])
+def _tf_warp_backward(saved, dout, needs, statics):
+    """d img and / or d flow, whichever is needed."""
+    from . import training
+    return training.warp_flow_backward(*saved, dout, need_img=needs[0], need_flow=needs[1])
 
 
 def tf_warp(img, flow, H, W):
@@ -62,9 +48,7 @@ def tf_warp(img, flow, H, W):
     B, h, w, Cc = img.shape
     if (h, w) != (H, W) or tuple(flow.shape) != (B, H, W, 2):
         raise ValueError(f"tf_warp: img {tuple(img.shape)} / flow {tuple(flow.shape)} do not match H={H}, W={W}")
-    if _wants_grad(img, flow):
-        return _TfWarpFn.apply(img, flow)
-    return _tf_warp_call(img, flow)
+    return _autograd.apply(_tf_warp_call, _tf_warp_backward, (img, flow))
 
 
 def _get_pixel_value_call(img, x, y):

@@ -1,6 +1,6 @@
 """ElasticTransformer (thin-plate spline) on the GPU: its coordinate entry point (vstab_st_elastic_coords /
 ElasticTransformer.transform_coords), the gradients of its bilinear sampler (vstab_st_elastic_transform_backward,
-training.st_elastic_transform_backward, spatial_transformer._ElasticTransformFn) and the C ABI's argument checks, against
+training.st_elastic_transform_backward, the shared _autograd.SamplerFn) and the C ABI's argument checks, against
 tests/st_tps_grad_ref.py.  The reference is fed transform_coords' output -- the coordinates the forward samples at, which the first
 tests establish -- so every floor and clip decision is shared and every element is compared.
 
