@@ -209,6 +209,7 @@ EXPORTS = {
     "vstab_host_pack_wdec": (C.c_longlong, [C.c_int, c_float_p, C.POINTER(C.c_double), c_float_p, C.c_longlong]),
     "vstab_host_wino_stream_positions": (C.c_int, [C.c_int] * 4),
     "vstab_host_wgrad_split": (C.c_int, [C.c_int] * 4 + [c_int32_p]),
+    "vstab_host_train_conv_plan": (C.c_int, [C.c_int] * 15 + [c_int32_p, C.c_int, c_int32_p, C.c_longlong]),
     "vstab_host_pack_winograd": (C.c_longlong, [c_float_p, C.POINTER(C.c_double), C.c_int, C.c_int, c_float_p, C.c_longlong]),
     "vstab_wino_domain_gemm_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "vstab_wino_domain_gemm": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -1,6 +1,6 @@
 // C ABI of libvstab_hip.so (include/vstab.h): context, errors, roctx ranges and the thin wrappers around single launches (glue, flow
 // warps and their backward, clip-driver pieces, post-filters).  The FlowNetS pyramid lives in flownet_plan.cpp / flownet_forward.cpp,
-// the VGG16 trunk in vgg_api.cpp, the NLDF head in nldf_api.cpp, the training blocks in train_api.cpp, the samplers in sampler_api.cpp.
+// the VGG16 trunk in vgg_api.cpp, the NLDF head in nldf_api.cpp, the training blocks in loss_api.cpp, train_conv_api.cpp and train_api.cpp, the samplers in sampler_api.cpp.
 #include <cstdlib>
 #include <new>
 

@@ -1,5 +1,5 @@
 // Shared between the translation units that implement the C ABI (api.cpp, sampler_api.cpp, flownet_plan.cpp, flownet_forward.cpp, vgg_api.cpp,
-// nldf_api.cpp, train_api.cpp): the context object, error plumbing and the helpers that turn a plain convolution into a launch plan.
+// nldf_api.cpp, loss_api.cpp, train_conv_api.cpp, train_api.cpp): the context object, error plumbing and the helpers that turn a plain convolution into a launch plan.
 #pragma once
 #include <cstdarg>
 #include <cstdio>

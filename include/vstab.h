@@ -884,6 +884,21 @@ VSTAB_API int vstab_host_wino_stream_positions(int B, int T, int cin, int cout);
  * vstab_conv3x3_winograd_wgrad makes for M = cin and K = B*ceil(H/2)*ceil(W/2) tiles.  VSTAB_E_SHAPE for anything else, or a shape the
  * batched form refuses. */
 VSTAB_API int vstab_host_wgrad_split(int M, int cout, int K, int nbatch, int *out4);
+/* The launches vstab_conv_forward (dgrad = 0) or vstab_conv_dgrad (dgrad = 1) makes for a geometry, without a HIP call.  x is the image
+ * side (the forward's input, the input gradient's dx: Hi x Wi, cin of cs_x channels), y the output side (the forward's y, gout: Ho x Wo,
+ * cout of cs_y channels; the forward takes Ho = Wo = 0 as the symmetric-pad size); c_off = channel offset of the tensor the launches
+ * WRITE (the offset on the side they read only moves a pointer); act = the forward's epilogue / the input gradient's accumulate flag.
+ * Writes 7 ints
+ *   launches packed_floats part_floats blocked_K tbl_nfast workspace_bytes/256 table_entries
+ * then per launch 8 ints
+ *   nphase tile vec4 ksplit Mmax N Npad operand_offset(floats)
+ * each followed by 12 per phase
+ *   Hg Wg M off_y off_x o_y o_x KH NSEG SEG SEGP SEG_STRIDE
+ * and, when `table` is not NULL, the gather table (table_entries ints: 0 = a zero, i > 0 = element i - 1 of the filter) that the
+ * operand is packed through every call (none when blocked_K > 0).  Returns the ints written to `out`, or the entry point's own
+ * refusal of the geometry (VSTAB_E_NOMEM: `cap` / `table_cap` too small) with both buffers untouched. */
+VSTAB_API int vstab_host_train_conv_plan(int dgrad, int B, int Hi, int Wi, int cs_x, int cin, int k, int stride, int pad, int Ho, int Wo,
+                                         int cs_y, int cout, int c_off, int act, int32_t *out, int cap, int32_t *table, long long table_cap);
 /* The Winograd-domain operand of a 3x3 stride-1 stage as vstab_load_weights packs it: W [3][3][cin][cout], scale (may be NULL = ones) per
  * output channel; 16 positions x [cin/32][cout][32] floats to `wpk`.  Returns the number of floats, or a negative error. */
 VSTAB_API long long vstab_host_pack_winograd(const float *W, const double *scale, int cin, int cout, float *wpk, long long cap);

@@ -372,7 +372,7 @@ def test_winograd_operand_layout_is_the_blocked_layout_per_position():
     assert _lib.lib().vstab_host_pack_winograd(None, None, cin, cout, wpk.ctypes.data_as(_lib.c_float_p), n) == -1
 
 
-# ---- how a filter gradient is launched (csrc/wgrad_mfma.hip: wgrad_choose_split; csrc/train_api.cpp: wgrad_split, wino_wgrad_shape), as
+# ---- how a filter gradient is launched (csrc/wgrad_mfma.hip: wgrad_choose_split; csrc/train_conv_api.cpp: wgrad_split, wino_wgrad_shape), as
 # vstab_host_wgrad_split reports it: the cases of tests/test_gpu_wgrad_alone.py, each chosen for what its reduction hits
 def wgrad_split(M, cout, K, nbatch=0):
     """(n_main, n_tail, ks_main, ks_tail) of the launches of a reduction over K pixels into M x cout"""
@@ -498,3 +498,149 @@ def test_wgrad_split_view_refusals_and_rule():
             ktiles = (K + 31) // 32
             assert 1 <= ks <= 256 and (ks - 1) * ((ktiles + ks - 1) // ks) < ktiles, (M, cout, K, ks)
             assert ks == 1 or ktiles // ks >= 1 and ks <= max(ktiles // 4, 1)
+
+
+# ---- the training step's forward and input gradient as GEMMs on raw weights (csrc/train_conv_api.cpp: plan_forward, plan_dgrad), as
+# vstab_host_train_conv_plan reports them: the launches, the workspace and the gather table the operand is packed through
+from tests import train_conv_ref as tcr  # noqa: E402
+
+LAUNCH_FIELDS = "nphase tile vec4 ksplit Mmax N Npad w_off".split()
+PHASE_K_FIELDS = PH_FIELDS + "KH NSEG SEG SEGP SEG_STRIDE".split()
+TILE_COLS = {0: 128, 1: 64, 2: 32, 3: 128}
+SENTINEL = -77
+
+
+def train_conv_plan_raw(dgrad, B, Hi, Wi, cs_x, cin, k, s, p, out_hw, cs_y, cout, c_off=0, act=0, cap=96, table_cap=None):
+    """(return code, the int buffer, the table buffer or None); both buffers start as SENTINEL"""
+    buf = (C.c_int32 * 96)(*([SENTINEL] * 96))
+    tbl = None if table_cap is None else np.full(table_cap, SENTINEL, np.int32)
+    rc = _lib.lib().vstab_host_train_conv_plan(dgrad, B, Hi, Wi, cs_x, cin, k, s, p, out_hw[0], out_hw[1], cs_y, cout, c_off, act, buf, cap,
+                                               None if tbl is None else tbl.ctypes.data_as(C.POINTER(C.c_int32)), 0 if tbl is None else len(tbl))
+    return rc, list(buf), tbl
+
+
+def train_conv_plan(*args, **kw):
+    """the plan as a dict (launches: list of dicts with their phases) and its gather table (length 0 for a blocked operand)"""
+    rc, buf, _ = train_conv_plan_raw(*args, **kw)
+    assert rc > 0, (args, kw, _lib.lib().vstab_last_error(None))
+    d = dict(zip("launches packed_floats part_floats blocked_K tbl_nfast ws256 table_entries".split(), buf[:7]))
+    at, d["launch"] = 7, []
+    for _ in range(d["launches"]):
+        la = dict(zip(LAUNCH_FIELDS, buf[at:at + 8]))
+        la["ph"] = [dict(zip(PHASE_K_FIELDS, buf[at + 8 + 12 * f:at + 20 + 12 * f])) for f in range(la["nphase"])]
+        at += 8 + 12 * la["nphase"]
+        d["launch"].append(la)
+    assert at == rc and all(v == SENTINEL for v in buf[rc:])
+    rc2, buf2, tbl = train_conv_plan_raw(*args, **kw, table_cap=d["table_entries"])
+    assert rc2 == rc and buf2 == buf
+    return d, tbl
+
+
+def plan_tiles(d):
+    """128-row tiles of every phase of every launch, in column tiles of the launch's own width"""
+    return sum(-(-ph["M"] // 128) * (la["Npad"] // TILE_COLS[la["tile"]]) for la in d["launch"] for ph in la["ph"])
+
+
+@pytest.mark.parametrize("i", range(len(tcr.PHASE_CASES)))
+def test_odd_k_stride2_dgrad_plan_is_the_one_the_case_names(i):
+    """what tests/test_gpu_train_conv_edges.py section B assumes: 'merged' rows run as ONE launch of all parity phases, the others as
+    one launch per non-empty parity phase, and the tile count that decides it is the recorded one"""
+    B, Hi, Wi, cin, cout, k, p, _, tiles, per_phase = tcr.PHASE_CASES[i]
+    hw = tcr.phase_out_hw(tcr.PHASE_CASES[i])
+    for sliced in (False, True):            # the plain call, and the accumulating call into a slice (cg_off moves a pointer only)
+        d, _ = train_conv_plan(1, B, Hi, Wi, cin + 8 * sliced, cin, k, 2, p, hw, cout + 8 * sliced, cout, c_off=4 * sliced, act=int(sliced))
+        nonempty = sum(1 for py in range(2) for px in range(2)
+                       if min((Hi - py + 1) // 2, (Wi - px + 1) // 2, (k - ((py + p) & 1) + 1) // 2, (k - ((px + p) & 1) + 1) // 2) >= 1)
+        assert d["launches"] == (nonempty if per_phase else 1)
+        assert [la["nphase"] for la in d["launch"]] == ([1] * nonempty if per_phase else [nonempty])
+        assert plan_tiles(d) == tcr.dgrad_plan_tiles(B, Hi, Wi, cin, k, p) == tiles
+        assert (tiles > tcr.PHASE_THRESHOLD) == per_phase
+        if not per_phase:                   # split-K sized for the phases together: 512 / tiles, at most a quarter of the shortest reduction
+            kt_min = min(ph["KH"] * ph["NSEG"] * ph["SEGP"] // 32 for ph in d["launch"][0]["ph"])
+            assert d["launch"][0]["ksplit"] == max(1, min(512 // tiles, max(1, kt_min // 4)))
+
+
+def _train_conv_geometries():
+    """(dgrad, B, Hi, Wi, cs_x, cin, k, s, p, out_hw, cs_y, cout, c_off, act): sections A and B of the GPU test, as it calls them (contiguous
+    tensors; slices of wider pixels on both sides with the accumulating epilogue), for the forward and the input gradient"""
+    geo = [(c, tcr.extra_out_hw(c, d)) for c in tcr.EXTRA_CASES for d in tcr.EXTRA_DELTAS]
+    geo += [((c[0], c[1], c[2], c[3], c[4], c[5], 2, c[6]), tcr.phase_out_hw(c)) for c in tcr.PHASE_CASES]
+    out = []
+    for (B, Hi, Wi, cin, cout, k, s, p), hw in geo:
+        for dgrad in (0, 1):
+            out.append((dgrad, B, Hi, Wi, cin, cin, k, s, p, hw, cout, cout, 0, 0))
+            out.append((dgrad, B, Hi, Wi, cin + 8, cin, k, s, p, hw, cout + 12, cout, 4, 3 if not dgrad else 1))
+    return out
+
+
+def test_train_conv_plans_tables_and_workspace():
+    r256 = lambda n: (n + 255) // 256 * 256
+    seen = set()
+    for g in _train_conv_geometries():
+        dgrad, B, Hi, Wi, cs_x, cin, k, s, p, hw, cs_y, cout, c_off, act = g
+        d, tbl = train_conv_plan(*g[:12], c_off=c_off, act=act)
+        numel = k * k * cin * cout
+        la0 = d["launch"][0]
+        assert all(la["N"] == (cin if dgrad else cout) and la["Npad"] == la0["Npad"] for la in d["launch"])
+        # the packed operand is the phases' operands one after the other
+        sizes = [ph["KH"] * ph["NSEG"] * (ph["SEGP"] // 32) * la["Npad"] * 32 for la in d["launch"] for ph in la["ph"]]
+        assert sum(sizes) == d["packed_floats"]
+        assert [la["w_off"] for la in d["launch"]] == [sum(sizes[:n]) for n in range(d["launches"])] or d["launches"] == 1
+        # workspace: operand, bias vector of Npad floats, split-K slabs, each rounded to 256 bytes, and 256 for the caller's alignment
+        assert d["ws256"] * 256 == r256(4 * d["packed_floats"]) + r256(4 * la0["Npad"]) + r256(4 * d["part_floats"]) + 256
+        slabs = [la["nphase"] * la["ksplit"] * la["Mmax"] * la["Npad"] if la["ksplit"] > 1 else 0 for la in d["launch"]]
+        assert d["part_floats"] == max(slabs)
+        if d["blocked_K"] > 0:
+            assert not dgrad and d["blocked_K"] == k * k * cin and d["table_entries"] == 0 and len(tbl) == 0 and not d["tbl_nfast"]
+            seen.add("blocked")
+            continue
+        assert d["table_entries"] == d["packed_floats"] == len(tbl)
+        assert tbl.min() >= 0 and tbl.max() <= numel
+        # every filter element is gathered exactly once: over the parity phases together, each tap belongs to one of them
+        assert np.array_equal(np.bincount(tbl, minlength=numel + 1)[1:], np.ones(numel, np.int64)), g
+        seen.add(("dgrad" if dgrad else "forward", "table"))
+        if dgrad:
+            assert not d["tbl_nfast"]
+            continue
+        # forward: logical reduction index kk of column n is tap (t, kx), channel ci of the USED channels, wherever the K layout puts it
+        ph = la0["ph"][0]
+        KT, Np = ph["KH"] * ph["NSEG"] * ph["SEGP"] // 32, la0["Npad"]
+        t3 = tbl.reshape(KT, Np, 32)
+        unsw = np.array([[swz32(n, q) for q in range(32)] for n in range(Np)])
+        logical = np.take_along_axis(t3, np.broadcast_to(unsw, t3.shape), axis=2).transpose(0, 2, 1).reshape(KT * 32, Np)
+        kk = np.arange(KT * 32)
+        t, sg, q = kk // (ph["NSEG"] * ph["SEGP"]), kk // ph["SEGP"] % ph["NSEG"], kk % ph["SEGP"]
+        kx, ci = (q // cin, q % cin) if ph["NSEG"] == 1 else (sg, q)
+        assert ph["SEG"] == (k * cin if ph["NSEG"] == 1 else cin) and (ph["NSEG"] == 1) == (cs_x == cin)
+        want = 1 + (((t * k + kx) * cin + ci) * cout)[:, None] + np.arange(Np)[None, :]
+        want = np.where((q < ph["SEG"])[:, None] & (np.arange(Np) < cout)[None, :], want, 0)
+        assert np.array_equal(logical, want), g
+        seen.add("tap mode" if cs_x > cin else "run mode")
+    assert seen >= {"blocked", ("dgrad", "table"), ("forward", "table"), "tap mode", "run mode"}, seen
+
+
+def test_train_conv_plan_refusals_leave_the_output_untouched():
+    E_SHAPE, E_NOMEM = -1, -4
+    B, Hi, Wi, cin, cout, k, s, p = tcr.EXTRA_CASES[0]
+    hw = tcr.extra_out_hw(tcr.EXTRA_CASES[0], (0, 0))
+    ok = (B, Hi, Wi, cin, cin, k, s, p, hw, cout, cout)
+    n_tbl = train_conv_plan(1, *ok)[0]["table_entries"]
+    bad = [
+        ((1, B, Hi, Wi, cin, cin, k, 3, p, (tcr.min_out(Hi, k, 3, p), tcr.min_out(Wi, k, 3, p)), cout, cout), E_SHAPE),   # stride 3 in the input gradient
+        ((1, B, Hi, Wi, cin, cin, k, s, p, (hw[0] + 2, hw[1]), cout, cout), E_SHAPE),                 # two extra rows
+        ((0, B, Hi, Wi, cin, cin, k, s, p, (hw[0] + 2, hw[1]), cout, cout), E_SHAPE),
+        ((0, B, Hi, Wi, cin, cin, k, s, p, (hw[0], hw[1] + 2), cout, cout), E_SHAPE),
+        ((1, 1, 9, 11, 8, 8, 3, 1, 1, (10, 11), 8, 8), E_SHAPE),                                     # stride 1 takes no extra row in the input gradient
+        ((1, 1, 4096, 4096, 32, 32, 3, 2, 1, (2048, 2048), 32, 32), E_SHAPE),                         # dx at exactly 2 GiB
+        ((0, 1, 4096, 4096, 32, 32, 3, 2, 1, (2048, 2048), 32, 32), E_SHAPE),                         # x at exactly 2 GiB
+        ((0, 1, 2048, 2048, 32, 32, 3, 1, 1, (2048, 2049), 128, 32), E_SHAPE),                        # y reaches 2 GiB through its extra column only
+    ]
+    for args, code in bad:
+        rc, buf, tbl = train_conv_plan_raw(*args, table_cap=64)
+        assert rc == code and all(v == SENTINEL for v in buf) and (tbl == SENTINEL).all(), args
+    assert 4096 * 4096 * 32 * 4 == 1 << 31 and 2048 * 2048 * 128 * 4 == 1 << 31
+    assert train_conv_plan_raw(1, 1, 4096, 4095, 32, 32, 3, 2, 1, (2048, 2048), 32, 32)[0] > 0        # one column less fits
+    for kw in (dict(cap=7 + 8 + 4 * 12 - 1), dict(table_cap=n_tbl - 1)):
+        rc, buf, tbl = train_conv_plan_raw(1, *ok, **kw)
+        assert rc == E_NOMEM and all(v == SENTINEL for v in buf) and (tbl is None or (tbl == SENTINEL).all())
+    assert _lib.lib().vstab_host_train_conv_plan(1, *ok[:8], hw[0], hw[1], cout, cout, 0, 0, None, 96, None, 0) == -6       # VSTAB_E_STATE, as every NULL buffer

@@ -117,7 +117,7 @@ def phase_out_hw(case):
 
 
 def dgrad_plan_tiles(B, Hi, Wi, cin, k, p):
-    """The 128-row tiles that dgrad_plan (csrc/train_api.cpp) counts for an odd-k stride-2 input gradient: the output pixels of
+    """The 128-row tiles that plan_dgrad (csrc/train_conv_api.cpp) counts for an odd-k stride-2 input gradient: the output pixels of
     parity (py, px) form one GEMM of B*Hg*Wg rows and cin columns (padded to the column tile: 128 from 128 columns up, 64 above 32,
     else 32).  More than PHASE_THRESHOLD of them run as one launch per parity."""
     assert k & 1
