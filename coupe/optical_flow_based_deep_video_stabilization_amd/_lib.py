@@ -20,6 +20,13 @@ class VstabWsEntry(C.Structure):
                 ("w", C.c_int32), ("c", C.c_int32), ("c_stride", C.c_int32)]
 
 
+class PredictUpArgs(C.Structure):
+    """vstab_predict_up_args (include/vstab.h): vstab_predict_up's arguments without the batch and the stream."""
+    _fields_ = [("taps", C.c_void_p), ("ks", C.c_int), ("slab_stride", C.c_longlong), ("h", C.c_int), ("w", C.c_int), ("bias2", C.c_void_p),
+                ("prev", C.c_void_p), ("ph", C.c_int), ("pw", C.c_int), ("out", C.c_void_p), ("up_w", c_float_p), ("up_b", c_float_p),
+                ("concat", C.c_void_p), ("oh", C.c_int), ("ow", C.c_int), ("Cs", C.c_int), ("c_off", C.c_int)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "vstab_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
@@ -214,6 +221,12 @@ EXPORTS = {
     "vstab_wino_domain_gemm_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "vstab_wino_domain_gemm": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "vstab_wino_gemm_stream_launch": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "vstab_host_pack_wdec_shape": (C.c_longlong, [c_float_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, c_float_p, C.c_longlong]),
+    "vstab_predict_up": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                   c_float_p, c_float_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "vstab_deconv4x4_winograd_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "vstab_deconv4x4_winograd": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6 +
+                                 [C.POINTER(PredictUpArgs), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 INTERP = {'bilinear': 0, 'bicubic': 1}          # VSTAB_INTERP_*

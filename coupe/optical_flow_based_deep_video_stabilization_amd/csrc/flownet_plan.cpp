@@ -466,13 +466,7 @@ extern "C" long long vstab_host_pack_wdec(int l, const float *W, const double *s
 {
     if (!W || !wpk || l < 0 || l > 3) return fail(nullptr, VSTAB_E_SHAPE, "pack_wdec: bad arguments");
     const Layer &d = dec_layer(l);
-    const int co = d.cout, cs = in_buf(d).cs;
-    const long long n = 9LL * klayout_run(1, 1, cs).ktiles() * 4 * co * 32;
-    if (cap < n) return fail(nullptr, VSTAB_E_NOMEM, "pack_wdec: need %lld floats", n);
-    std::vector<double> ones;
-    if (!scale) { ones.assign(co, 1.0); scale = ones.data(); }
-    pack_wdec(W, scale, d.cin, cs, co, wpk);
-    return n;
+    return vstab_host_pack_wdec_shape(W, scale, d.cin, in_buf(d).cs, d.cout, wpk, cap);
 }
 
 extern "C" long long vstab_host_pack_layer(int Cin, int layer, const float *W, const double *scale, float *wpk,

@@ -874,6 +874,45 @@ VSTAB_API long long vstab_host_pack_layer(int Cin, int layer, const float *W, co
  * builds them (W = the reference-layout filter [4][4][Cout][Cin]; 9 positions x [KT][4 Cout][32]). */
 VSTAB_API int vstab_host_wdec_plan(int B, int H, int W, int Cin, int l, int32_t *out, int cap);
 VSTAB_API long long vstab_host_pack_wdec(int l, const float *W, const double *scale, float *wpk, long long cap);
+/* The same operands for arbitrary channel counts: W [4][4][cout][cin], input pixels of cs_in >= cin floats (rows cin .. cs_in of every
+ * position are zeros); 9 positions x [round_up(cs_in, 32) / 32][4 cout][32] floats.  vstab_host_pack_wdec(l, ...) is this call with level
+ * l's channel counts. */
+VSTAB_API long long vstab_host_pack_wdec_shape(const float *W, const double *scale, int cin, int cs_in, int cout, float *wpk, long long cap);
+
+/* A refinement level's flow head by itself (csrc/flow_ops.hip: predict_flowN + upsample_flowN in one launch; the forward's launch_predict_up
+ * without a combine or an inverse transform riding along).  taps: the tap table T [B][h][w][32] (T[.., 2 tap + o], tap = 3 dy + dx; columns
+ * 18..31 are not read) or its `ks` split-K slabs `slab_stride` floats apart (even; at least one table when ks > 1), summed in slab order.
+ * out [B][h][w][2] = bias2[o] + the in-image taps T[y+dy-1, x+dx-1, 2 tap + o] in (dy, dx) order, then, with prev [B][ph][pw][2] != NULL,
+ * (.. + u) + u with u the legacy-bilinear sample of prev.  Then the 4x4 stride-2 SAME transposed convolution 2 -> 2 of `out` with the HOST
+ * arrays up_w [4][4][co][ci] (64 floats) and up_b (2 floats), cropped to oh x ow (oh <= 2 h, ow <= 2 w), written as (u, v, 0, 0) into the four
+ * floats at c_off of concat [B][oh][ow][Cs]; the other floats of a pixel are not touched.  bias2 is a device pointer.  VSTAB_E_SHAPE for
+ * Cs % 4, c_off % 4, c_off + 4 > Cs, ks < 1, oh > 2 h, ow > 2 w or a tensor of 2 GiB; VSTAB_E_STATE for a NULL buffer (prev may be NULL);
+ * VSTAB_E_ALIGN unless taps, prev and out are 8-byte and concat 16-byte aligned.  A refused call launches nothing. */
+VSTAB_API int vstab_predict_up(const float *taps, int ks, long long slab_stride, int B, int h, int w, const float *bias2, const float *prev, int ph,
+                               int pw, float *out, const float *up_w, const float *up_b, float *concat, int oh, int ow, int Cs, int c_off,
+                               void *stream);
+/* vstab_predict_up's arguments without the batch and the stream, for vstab_deconv4x4_winograd's `head` */
+typedef struct vstab_predict_up_args {
+    const float *taps; int ks; long long slab_stride; int h, w; const float *bias2; const float *prev; int ph, pw; float *out;
+    const float *up_w; const float *up_b; float *concat; int oh, ow, Cs, c_off;
+} vstab_predict_up_args;
+
+/* A 4x4 stride-2 SAME transposed convolution in Winograd F(2x2,2x2) form by itself (csrc/winograd_ops.hip documents the algebra), through
+ * the forward's launchers: the input transform, the 9-position GEMM on the 128x128 (tile = 0) or 64x128 (tile = 1) tile with a zero bias,
+ * the inverse transform + bias + activation (act 0 = none, 1 = leaky relu 0.1).  x [B][Hi][Wi][cs_in]; wpk = a device copy of
+ * vstab_host_pack_wdec_shape's operands; bias [cout]; the result goes to channels c_off .. c_off + cout of out [B][Ho][Wo][cs_out], the
+ * other channels are not touched.  head == NULL: the inverse transform is a launch of its own; otherwise it rides in the flow head's launch
+ * (the forward's wdec_output_predict_up_kernel) with *head's arguments and this call's B.  workspace:
+ * vstab_deconv4x4_winograd_workspace_bytes() bytes, 256-byte aligned (the transformed tiles V [B][9][NTy][NTx][cs_in] at its start, the
+ * GEMM's result M [B][9][NTy][NTx][4 cout] at the next multiple of 256 bytes, then the zero bias; NT = Ho / 4 + 1 per axis; tiles a
+ * position does not need are left as they were; the query returns 0 for a shape the call refuses).  VSTAB_E_SHAPE for cs_in % 4, 4 cout not a multiple of 128 or above 2048, Ho not in {2 Hi - 1, 2 Hi} (Wo
+ * likewise), cs_out % 4, c_off % 4, c_off + cout > cs_out, tile or act not 0 / 1, a tensor of 2 GiB, or a head vstab_predict_up refuses;
+ * VSTAB_E_STATE for a NULL buffer; VSTAB_E_ALIGN unless every tensor is 16-byte aligned; VSTAB_E_NOMEM for a short workspace.  A refused
+ * call launches nothing. */
+VSTAB_API size_t vstab_deconv4x4_winograd_workspace_bytes(int B, int Hi, int Wi, int cs_in, int Ho, int Wo, int cout);
+VSTAB_API int vstab_deconv4x4_winograd(const float *x, int B, int Hi, int Wi, int cs_in, const float *wpk, const float *bias, int act, float *out,
+                                       int Ho, int Wo, int cs_out, int c_off, int cout, int tile, const vstab_predict_up_args *head,
+                                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* Positions per workgroup of the stream form of a Winograd stage's 16 GEMMs (csrc/wino_gemm_stream.hip) for B samples of T tiles, cin -> cout
  * channels: 16, 8, 4 or 2, or 0 when the stage does not qualify (the forward then takes the tiled launch). */

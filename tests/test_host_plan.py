@@ -372,6 +372,68 @@ def test_winograd_operand_layout_is_the_blocked_layout_per_position():
     assert _lib.lib().vstab_host_pack_winograd(None, None, cin, cout, wpk.ctypes.data_as(_lib.c_float_p), n) == -1
 
 
+def wdec_operand_np(Wt, scale, cs_in):
+    """U[pos = 3 i + j][ci][ph * cout + co] = (G g G^T)[i][j] * scale[co] in float64, g[a][b] = W[3 - py - 2 a][3 - px - 2 b][co][ci] the
+    2 x 2 taps of output phase ph = 2 py + px, G = [1 0; 1 1; 0 1]; rows cin .. round_up(cs_in, 32) are zeros (pack.cpp: pack_wdec)"""
+    cout, cin = Wt.shape[2], Wt.shape[3]
+    G = np.array([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0]])
+    U = np.zeros((9, -(-cs_in // 32) * 32, 4 * cout))
+    for py in range(2):
+        for px in range(2):
+            g = Wt.astype(np.float64)[3 - py::-2, 3 - px::-2]                # [a][b][co][ci]
+            u = np.einsum("ia,jb,aboc->ijco", G, G, g).reshape(9, cin, cout)
+            ph = 2 * py + px
+            U[:, :cin, ph * cout:(ph + 1) * cout] = u if scale is None else u * scale
+    return U
+
+
+def pack_wdec_shape(Wt, scale, cin, cs_in, cout, cap=None, slack=32):
+    n = 9 * -(-cs_in // 32) * 4 * cout * 32
+    wpk = np.full(n + slack, np.nan, np.float32)
+    got = _lib.lib().vstab_host_pack_wdec_shape(Wt.ctypes.data_as(_lib.c_float_p),
+                                                None if scale is None else scale.ctypes.data_as(C.POINTER(C.c_double)), cin, cs_in, cout,
+                                                wpk.ctypes.data_as(_lib.c_float_p), n if cap is None else cap)
+    return got, n, wpk
+
+
+@pytest.mark.parametrize("cin,cs_in,cout", [(64, 64, 32), (34, 36, 64)])
+def test_wdec_operand_for_arbitrary_channel_counts_vs_fp64_transform(cin, cs_in, cout):
+    # integer filters: G g G^T is exact, so the comparison is bit for bit; the scale is folded in double and rounded once on both sides
+    rng = np.random.default_rng(cin + cout)
+    Wt = rng.integers(-4, 5, (4, 4, cout, cin)).astype(np.float32)
+    scale = rng.uniform(0.5, 1.5, cout)
+    for sc in (None, scale):
+        got, n, wpk = pack_wdec_shape(Wt, sc, cin, cs_in, cout)
+        assert got == n and np.isnan(wpk[n:]).all()
+        want = wdec_operand_np(Wt, sc, cs_in).astype(np.float32)
+        packed = wpk[:n].reshape(9, -1, 4 * cout, 32)
+        for pos in range(9):
+            assert np.array_equal(packed[pos], blocked_pack_np(want[pos])), pos
+        # the rows of the pad channels and of the K-tile's tail are zeros at every position (they meet whatever the pixel holds there)
+        unsw = np.array([[swz32(c, k) for k in range(32)] for c in range(4 * cout)])
+        logical = np.take_along_axis(packed, np.broadcast_to(unsw, packed.shape), axis=3)          # [9][KT][4 cout][k]
+        rows = logical.transpose(0, 1, 3, 2).reshape(9, -1, 4 * cout)
+        assert rows.shape[1] == -(-cs_in // 32) * 32 and not rows[:, cin:].any() and rows[:, :cin].any()
+    L = _lib.lib()
+    assert pack_wdec_shape(Wt, None, cin, cs_in, cout, cap=n - 1)[0] == -4
+    assert pack_wdec_shape(Wt, None, cin, cin - 2, cout)[0] == -1 and pack_wdec_shape(Wt, None, 0, cs_in, cout)[0] == -1
+    assert L.vstab_host_pack_wdec_shape(None, None, cin, cs_in, cout, wpk.ctypes.data_as(_lib.c_float_p), n) == -1
+
+
+@pytest.mark.parametrize("l", [0, 1, 2, 3])
+def test_wdec_level_operand_is_the_shape_form(l):
+    cin, cs, cout = ((1024, 1024, 512), (1026, 1028, 256), (770, 772, 128), (386, 388, 64))[l]
+    rng = np.random.default_rng(40 + l)
+    Wt = rng.standard_normal((4, 4, cout, cin)).astype(np.float32)
+    scale = rng.uniform(0.5, 1.5, cout)
+    got, n, want = pack_wdec_shape(Wt, scale, cin, cs, cout, slack=0)
+    assert got == n
+    wpk = np.full(n, np.nan, np.float32)
+    assert _lib.lib().vstab_host_pack_wdec(l, Wt.ctypes.data_as(_lib.c_float_p), scale.ctypes.data_as(C.POINTER(C.c_double)),
+                                           wpk.ctypes.data_as(_lib.c_float_p), n) == n
+    assert np.array_equal(wpk, want)
+
+
 # ---- how a filter gradient is launched (csrc/wgrad_mfma.hip: wgrad_choose_split; csrc/train_conv_api.cpp: wgrad_split, wino_wgrad_shape), as
 # vstab_host_wgrad_split reports it: the cases of tests/test_gpu_wgrad_alone.py, each chosen for what its reduction hits
 def wgrad_split(M, cout, K, nbatch=0):
