@@ -317,6 +317,35 @@ extern "C" int vstab_assemble_input_resized(const uint8_t *const *slots8, const 
     return VSTAB_OK;
 }
 
+extern "C" int vstab_assemble_train_batch_launch_samples(void) { return TRAIN_BATCH_LAUNCH_SAMPLES; }
+
+extern "C" int vstab_assemble_train_batch(const uint8_t *stab, const uint8_t *unstab, int N, int sh, int sw, const int *rows, const int *frame_idx, int n,
+                                          float *feats, float *gtstab, float *unstab_out, int B, int H, int W, void *stream)
+{
+    if (!stab || !unstab || !rows || !frame_idx || !feats || !gtstab || !unstab_out)
+        return fail(nullptr, VSTAB_E_STATE, "assemble_train_batch: NULL buffer");
+    if (N < 1 || sh < 1 || sw < 1 || n < 1 || B < 1 || H < 1 || W < 1)
+        return fail(nullptr, VSTAB_E_SHAPE, "assemble_train_batch: bad shape (N %d, source %dx%d, n %d, B %d, output %dx%d)", N, sh, sw, n, B, H, W);
+    if ((long long)H * W > (1ll << 30) || (long long)sh * sw > (1ll << 30))
+        return fail(nullptr, VSTAB_E_SHAPE, "assemble_train_batch: a frame of more than 2^30 pixels");
+    if ((uintptr_t)feats & 15) return fail(nullptr, VSTAB_E_SHAPE, "assemble_train_batch: feats must be 16-byte aligned");
+    if (((uintptr_t)gtstab | (uintptr_t)unstab_out) & 3) return fail(nullptr, VSTAB_E_SHAPE, "assemble_train_batch: gtstab / unstab_out must be 4-byte aligned");
+    std::vector<char> seen((size_t)B, 0);
+    for (int i = 0; i < n; ++i) {
+        const int r = rows[i];
+        if (r < 0 || r >= B) return fail(nullptr, VSTAB_E_SHAPE, "assemble_train_batch: rows[%d] = %d is outside [0, %d)", i, r, B);
+        if (seen[(size_t)r]) return fail(nullptr, VSTAB_E_SHAPE, "assemble_train_batch: row %d is written twice (rows[%d])", r, i);
+        seen[(size_t)r] = 1;
+        for (int j = 0; j < 9; ++j) {
+            const int f = frame_idx[(size_t)i * 9 + j];
+            if (f < 0 || f >= N) return fail(nullptr, VSTAB_E_SHAPE, "assemble_train_batch: frame_idx[%d][%d] = %d is outside [0, %d)", i, j, f, N);
+        }
+    }
+    TraceRange range("assemble_train_batch");
+    HIP_TRY(nullptr, launch_assemble_train_batch(stab, unstab, sh, sw, rows, frame_idx, n, feats, gtstab, unstab_out, H, W, (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
 extern "C" int vstab_flow_glue_warp_u8(const float *flow, int B, int h, int w, const uint8_t *frame, float *outflow, uint8_t *out, int oh, int ow,
                                        int net_h, int net_w, void *stream)
 {

@@ -480,6 +480,12 @@ hipError_t launch_flow_glue_warp_u8(const float *flow, int B, int h, int w, cons
 hipError_t launch_frame_to_float(const unsigned char *f, long long npix, float *out, hipStream_t stream);
 hipError_t launch_quantise_output(const float *warped, long long npix, unsigned char *out, hipStream_t stream);
 
+// the training loader's batch assembly (train_batch_ops.hip): the samples of one clip, rows / frame_idx [n][9] HOST arrays, already
+// validated; they reach the kernel by value, TRAIN_BATCH_LAUNCH_SAMPLES samples per launch
+constexpr int TRAIN_BATCH_LAUNCH_SAMPLES = 8;
+hipError_t launch_assemble_train_batch(const unsigned char *stab, const unsigned char *unstab, int sh, int sw, const int *rows, const int *frame_idx,
+                                       int n, float *feats, float *gtstab, float *unstab_out, int H, int W, hipStream_t stream);
+
 hipError_t launch_flow_box_blur(const float *flow, int B, int h, int w, int k, float *tmp, float *out, hipStream_t stream);
 hipError_t launch_axpby(const float *x, float a, const float *y, float b, float *out, long long n, hipStream_t stream);
 hipError_t launch_flow_mean_fill(const float *flow, int B, int h, int w, float *out, hipStream_t stream);

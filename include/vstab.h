@@ -468,6 +468,19 @@ VSTAB_API int vstab_flow_glue_warp_u8(const float *flow, int B, int h, int w, co
 VSTAB_API int vstab_clip_step(vstab_ctx *ctx, const uint8_t *const *slots8, const uint8_t *frame, int n, int net_h, int net_w, int oh, int ow,
                               float *feats, float *pf6, float *pf5, float *pf4, float *pf3, float *pf2, float *outflow, uint8_t *out,
                               uint8_t *ring_slot, void *workspace, size_t workspace_bytes, void *stream);
+/* ---- the training loader's batch (data_loader.py: _read_frame :203-206, read_dataset :132-169; main:179-184) ----
+ * stab / unstab: one clip's two frame pools, uint8 [N,sh,sw,3] in RGB order (the loader's cvtColor(BGR2RGB) already applied), device
+ * memory.  rows [n] and frame_idx [n][9] are HOST arrays: sample i fills output row rows[i] with
+ *   feats[rows[i],:,:,3j+c] = resize(stab[frame_idx[i][j]] / 255.) for j < 8,
+ *   feats[rows[i],:,:,24+c] = unstab_out[rows[i]] = resize(unstab[frame_idx[i][8]] / 255.),   gtstab[rows[i]] = resize(stab[frame_idx[i][8]] / 255.),
+ * resize = cv2.resize(., (W, H)), INTER_LINEAR on the float64 image (restated, see train_batch_ops.hip), rounded to fp32 once.
+ * feats [B,H,W,27] (16-byte aligned), gtstab / unstab_out [B,H,W,3]; rows not named are left untouched.  One call serves the samples of
+ * one clip; a batch spanning clips is one call per clip.  The indices travel in the kernel arguments
+ * (vstab_assemble_train_batch_launch_samples() samples per launch): no copy, no synchronisation, capturable.
+ * VSTAB_E_SHAPE: a size < 1, frame_idx outside [0,N), rows outside [0,B) or not distinct, feats not 16-byte aligned. */
+VSTAB_API int vstab_assemble_train_batch(const uint8_t *stab, const uint8_t *unstab, int N, int sh, int sw, const int *rows, const int *frame_idx,
+                                         int n, float *feats, float *gtstab, float *unstab_out, int B, int H, int W, void *stream);
+VSTAB_API int vstab_assemble_train_batch_launch_samples(void);
 /* resizedInput (main:568): swap(frame)/255 -> float [npix,3]. */
 VSTAB_API int vstab_frame_to_float(const uint8_t *frame, long long npix, float *out, void *stream);
 /* np.uint8(swap(warped*255)) (main:625,630,556): float [npix,3] -> u8, truncating, saturating outside [0,255]. */
