@@ -174,6 +174,11 @@ EXPORTS = {
     "vstab_loss_main_multi_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vstab_loss_main_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_int32_p, c_float_p, C.c_void_p] + [C.c_int] * 3 +
                               [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_loss_report_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vstab_loss_report": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, c_int32_p, c_float_p, C.c_void_p] + [C.c_int] * 3 +
+                          [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "vstab_bn_lrelu_inference_forward": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_float, C.c_void_p]),
     "vstab_resize_f32_to_u8": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vstab_homography_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "vstab_homography_fit": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_uint, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -1,4 +1,5 @@
-// C ABI of the training objective (train_ops.hip): the per-level and the whole-pyramid loss, for one target and for many.
+// C ABI of the training objective (train_ops.hip): the per-level and the whole-pyramid loss, for one target and for many, and the test
+// pass's report of it (no gradient; the scalars per level, the warped frames).
 // vstab_loss_level / vstab_loss_main are the _multi entry points at one 3-channel target tensor, channel offset 0, weight 1: the
 // same checks in the same order, the same kernels.
 #include <cstdint>
@@ -61,9 +62,12 @@ size_t loss_main_bytes(const vstab_loss_level_desc *levels, int n_levels, int B,
     return loss_main_workspace_bytes(B, reinterpret_cast<const LossLevel *>(levels), n_levels, Ct, T);
 }
 
+// what vstab_loss_report adds to a loss_main call: the levels' previews and their type
+struct LossReportArgs { void *const *previews; int preview_dtype; };
+
 int loss_main(const char *who, const vstab_loss_level_desc *levels, int n_levels, const float *targets, int Ct, int T, const int *c_off,
               const float *weights, const float *unstab, int B, int H, int W, double *loss_out, bool per_target, void *workspace,
-              size_t workspace_bytes, void *stream)
+              size_t workspace_bytes, void *stream, const LossReportArgs *report = nullptr)
 {
     int c = loss_main_check(levels, n_levels, B, Ct, T);
     if (c != VSTAB_OK)
@@ -78,9 +82,31 @@ int loss_main(const char *who, const vstab_loss_level_desc *levels, int n_levels
     const LossLevel *lv = reinterpret_cast<const LossLevel *>(levels);
     if (workspace_bytes < loss_main_workspace_bytes(B, lv, n_levels, Ct, T)) return fail(nullptr, VSTAB_E_NOMEM, "%s: workspace too small", who);
     void *ws = (void *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    if (report) {
+        if (report->preview_dtype != 0 && report->preview_dtype != 1)
+            return fail(nullptr, VSTAB_E_SHAPE, "%s: preview_dtype must be 0 (float32) or 1 (uint8)", who);
+        for (int l = 0; report->previews && report->preview_dtype == 0 && l < n_levels; ++l)
+            if ((uintptr_t)report->previews[l] & 3) return fail(nullptr, VSTAB_E_ALIGN, "%s: a float32 preview must be 4-byte aligned", who);
+        HIP_TRY(nullptr, launch_loss_report(lv, n_levels, targets, Ct, T, c_off, weights, unstab, B, H, W, report->previews,
+                                            report->preview_dtype == 1, loss_out, ws, (hipStream_t)stream));
+        return VSTAB_OK;
+    }
     HIP_TRY(nullptr, launch_loss_main(lv, n_levels, targets, Ct, T, c_off, weights, unstab, B, H, W, loss_out, per_target, ws, (hipStream_t)stream));
     return VSTAB_OK;
 }
+
+// The report writes no gradient and ignores levels[l].grad: the descriptors as loss_main's checks should see them, grad NULL.  An
+// array or count the checks refuse anyway is handed through as it is.
+struct GradlessLevels {
+    vstab_loss_level_desc copy[8];
+    const vstab_loss_level_desc *lv;
+    GradlessLevels(const vstab_loss_level_desc *levels, int n) : lv(levels)
+    {
+        if (!levels || n < 1 || n > 8) return;
+        for (int l = 0; l < n; ++l) { copy[l] = levels[l]; copy[l].grad = nullptr; copy[l].cs_grad = 0; }
+        lv = copy;
+    }
+};
 }  // namespace
 
 extern "C" int vstab_loss_level(const float *pf, const float *gt, const float *unstab, int B, int h, int w, double *sums,
@@ -120,4 +146,20 @@ extern "C" int vstab_loss_main_multi(const vstab_loss_level_desc *levels, int n_
 {
     return loss_main("loss_main_multi", levels, n_levels, targets, Ct, T, c_off, weights, unstab, B, H, W, loss_out, true, workspace,
                      workspace_bytes, stream);
+}
+
+// ---- the test pass's loss report (main:277-326, 346-372): loss_main_multi's checks in its order, then the previews'
+extern "C" size_t vstab_loss_report_workspace_bytes(const vstab_loss_level_desc *levels, int n_levels, int B, int Ct, int T)
+{
+    return loss_main_bytes(GradlessLevels(levels, n_levels).lv, n_levels, B, Ct, T);
+}
+
+// out: 1 + T + 2 * n_levels doubles
+extern "C" int vstab_loss_report(const vstab_loss_level_desc *levels, int n_levels, const float *targets, int Ct, int T, const int *c_off,
+                                 const float *weights, const float *unstab, int B, int H, int W, void *const *previews, int preview_dtype,
+                                 double *out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const LossReportArgs report = {previews, preview_dtype};
+    return loss_main("loss_report", GradlessLevels(levels, n_levels).lv, n_levels, targets, Ct, T, c_off, weights, unstab, B, H, W, out, true,
+                     workspace, workspace_bytes, stream, &report);
 }

@@ -9,7 +9,7 @@
 
 using namespace vstab;
 
-// ------------------------------------------------------------------------- BatchNorm (training mode) + leaky relu
+// ------------------------------------------------------------------------- BatchNorm (training and inference mode) + leaky relu
 extern "C" size_t vstab_bn_scratch_bytes(long long rows, int C)
 {
     if (rows < 1 || C < 1) return 0;
@@ -28,6 +28,18 @@ extern "C" int vstab_bn_lrelu_train_forward(float *zy, long long rows, int cs, i
     if (scratch_bytes < vstab_bn_scratch_bytes(rows, C)) return fail(nullptr, VSTAB_E_NOMEM, "bn_lrelu_train_forward: scratch too small");
     HIP_TRY(nullptr, launch_bn_lrelu_train_forward(zy, rows, cs, c_off, C, beta, moving_mean, moving_var, decay, eps, save_mean, save_rstd,
                                                    reinterpret_cast<float *>(scratch), (hipStream_t)stream));
+    return VSTAB_OK;
+}
+
+extern "C" int vstab_bn_lrelu_inference_forward(float *zy, long long rows, int cs, int c_off, int C, const float *beta, const float *moving_mean,
+                                                const float *moving_var, float eps, void *stream)
+{
+    if (!zy || !beta || !moving_mean || !moving_var) return fail(nullptr, VSTAB_E_STATE, "bn_lrelu_inference_forward: NULL buffer");
+    if (rows < 1 || C < 1 || c_off < 0 || c_off + C > cs) return fail(nullptr, VSTAB_E_SHAPE, "bn_lrelu_inference_forward: bad shape");
+    if ((C & 3) || (cs & 3) || (c_off & 3) || (reinterpret_cast<uintptr_t>(zy) & 15) || (reinterpret_cast<uintptr_t>(beta) & 15) ||
+        (reinterpret_cast<uintptr_t>(moving_mean) & 15) || (reinterpret_cast<uintptr_t>(moving_var) & 15))
+        return fail(nullptr, VSTAB_E_ALIGN, "bn_lrelu_inference_forward: channels multiples of 4, 16-byte aligned buffers");
+    HIP_TRY(nullptr, launch_bn_lrelu_inference_forward(zy, rows, cs, c_off, C, beta, moving_mean, moving_var, eps, (hipStream_t)stream));
     return VSTAB_OK;
 }
 

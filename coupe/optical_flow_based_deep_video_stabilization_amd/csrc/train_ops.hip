@@ -114,9 +114,10 @@ static LossTargets loss_one_target()
 // LOSS_PPT * 256 pixels, so a full-resolution level issues ~64 atomics per sample and sum instead of ~1000 (they serialise on one
 // address).
 constexpr int LOSS_PPT = 16;
-template <int T>
-__global__ __launch_bounds__(256) void loss_sums_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G, LossTargets tg,
-                                                        const float *__restrict__ U, int h, int w, double *__restrict__ sums)
+// `warped(idx, P)` is handed every pixel's three warped values P (the reference's `warpedimg`, before the mask) as they are formed.
+template <int T, class Warped>
+__device__ __forceinline__ void loss_sums_block(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G, const LossTargets &tg,
+                                                const float *__restrict__ U, int h, int w, double *__restrict__ sums, Warped warped)
 {
     const int n = blockIdx.y;
     double num[T], den = 0.0, tv = 0.0;
@@ -132,9 +133,12 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(const float *__restrict_
         const LossPixel p = loss_pixel(xx, yy, f, ub, h, w);
         const float M = p.M;
         const float *g = G + ((long long)n * h * w + idx) * tg.Ct;
-        float PM[3];
+        float P[3], PM[3];
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) PM[ch] = (((p.wa * p.Ia[ch] + p.wb * p.Ib[ch]) + p.wc * p.Ic[ch]) + p.wd * p.Id[ch]) * M;
+        for (int ch = 0; ch < 3; ++ch) P[ch] = ((p.wa * p.Ia[ch] + p.wb * p.Ib[ch]) + p.wc * p.Ic[ch]) + p.wd * p.Id[ch];
+        warped(idx, P);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) PM[ch] = P[ch] * M;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const float *gt = g + tg.c_off[t];
@@ -162,6 +166,33 @@ __global__ __launch_bounds__(256) void loss_sums_kernel(const float *__restrict_
         const double s = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
         atomicAdd(&sums[(T + 2) * n + threadIdx.x], s);
     }
+}
+
+template <int T>
+__global__ __launch_bounds__(256) void loss_sums_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G, LossTargets tg,
+                                                        const float *__restrict__ U, int h, int w, double *__restrict__ sums)
+{
+    loss_sums_block<T>(pf, cs_pf, G, tg, U, h, w, sums, [](int, const float *) {});
+}
+
+// utils.fix_image_tf(P, 1) (utils.py:434): tf.cast(P / 1 * 255., tf.uint8), truncation toward zero.  TF's cast is undefined outside
+// 0..255 (a tiny negative P occurs where clamped corners make the weights cancel), so the product saturates first.
+__device__ __forceinline__ void preview_store(float *o, const float *P) { o[0] = P[0]; o[1] = P[1]; o[2] = P[2]; }
+__device__ __forceinline__ void preview_store(unsigned char *o, const float *P)
+{
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) o[ch] = (unsigned char)(int)fminf(fmaxf(P[ch] * 255.f, 0.f), 255.f);
+}
+
+// pass 1 of the loss report: the same sums from the same flow read and gather, and the level's warped frame P (not P * M) into
+// preview [B,h,w,3], float32 or uint8 fix_image_tf(P, 1) by the type O
+template <int T, class O>
+__global__ __launch_bounds__(256) void loss_sums_preview_kernel(const float *__restrict__ pf, int cs_pf, const float *__restrict__ G,
+                                                                LossTargets tg, const float *__restrict__ U, int h, int w,
+                                                                double *__restrict__ sums, O *__restrict__ preview)
+{
+    O *pv = preview + (long long)blockIdx.y * h * w * 3;
+    loss_sums_block<T>(pf, cs_pf, G, tg, U, h, w, sums, [pv](int idx, const float *P) { preview_store(pv + idx * 3, P); });
 }
 
 // pass 2: grad[b,y,x,0:2] = d( scale_mse * sum_t c_t * mean_b(num_t,b/den_b) + scale_tv * TV ) / d pf[b,y,x,:]   (grad: [B,h,w,cs_g] pixels)
@@ -207,7 +238,9 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float *__restrict_
 
 // out[0] = sum over levels of [ sum_t c_t * mean_b(num_t/den) + tv_weight * sum_b TV ]  (main:213-217, 269-275 for T = 1, c = 1);
 // per_target: out[1 + t] = sum over levels of mean_b(num_t/den), target t's unweighted share
-struct LossTotalArgs { float tvw[8]; float c[LOSS_MAX_TARGETS]; int n, T, per_target; };
+// per_level (the loss report; after the T shares): out[1 + T + l] = mse_l = sum_t c_t * mean_b(num_t/den) of level l and
+// out[1 + T + n + l] = var_l = tv_weight_l * sum_b TV -- the two addends of `total`, so total is what it is without them
+struct LossTotalArgs { float tvw[8]; float c[LOSS_MAX_TARGETS]; int n, T, per_target, per_level; };
 __global__ void loss_total_kernel(const double *__restrict__ sums, int B, LossTotalArgs a, double *__restrict__ out)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -225,20 +258,30 @@ __global__ void loss_total_kernel(const double *__restrict__ sums, int B, LossTo
             per[t] += mse;
             lvl = t == 0 ? (double)a.c[0] * mse : lvl + (double)a.c[t] * mse;
         }
-        total += lvl + (double)a.tvw[l] * tv;
+        const double var = (double)a.tvw[l] * tv;
+        total += lvl + var;
+        if (a.per_level) { out[1 + a.T + l] = lvl; out[1 + a.T + a.n + l] = var; }
     }
     out[0] = total;
     if (a.per_target)
         for (int t = 0; t < a.T; ++t) out[1 + t] = per[t];
 }
 
+// a level's warped frame for the loss report: out [B,h,w,3] of float (u8 false) or unsigned char (u8 true); out NULL: none
+struct LossPreview { void *out; bool u8; };
+
 template <int T>
 static hipError_t loss_level_kernels(const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B, int h, int w,
-                                     double *sums, float scale_mse, float scale_tv, float *grad, int cs_g, hipStream_t stream)
+                                     double *sums, float scale_mse, float scale_tv, float *grad, int cs_g, LossPreview pv, hipStream_t stream)
 {
     const int npix = h * w;
-    loss_sums_kernel<T><<<dim3((unsigned)((npix + 256 * LOSS_PPT - 1) / (256 * LOSS_PPT)), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U,
-                                                                                                                             h, w, sums);
+    const dim3 grid((unsigned)((npix + 256 * LOSS_PPT - 1) / (256 * LOSS_PPT)), (unsigned)B);
+    if (!pv.out)
+        loss_sums_kernel<T><<<grid, dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U, h, w, sums);
+    else if (pv.u8)
+        loss_sums_preview_kernel<T><<<grid, dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U, h, w, sums, static_cast<unsigned char *>(pv.out));
+    else
+        loss_sums_preview_kernel<T><<<grid, dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U, h, w, sums, static_cast<float *>(pv.out));
     if (grad)
         loss_grad_kernel<T><<<dim3((unsigned)((npix + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(pf, cs_pf, G, tg, U, B, h, w, sums,
                                                                                                        scale_mse, scale_tv, grad, cs_g);
@@ -246,10 +289,11 @@ static hipError_t loss_level_kernels(const float *pf, int cs_pf, const float *G,
 }
 
 static hipError_t loss_level_dispatch(int T, const float *pf, int cs_pf, const float *G, const LossTargets &tg, const float *U, int B, int h,
-                                      int w, double *sums, float scale_mse, float scale_tv, float *grad, int cs_g, hipStream_t stream)
+                                      int w, double *sums, float scale_mse, float scale_tv, float *grad, int cs_g, LossPreview pv,
+                                      hipStream_t stream)
 {
     switch (T) {
-#define VSTAB_LOSS_T(N) case N: return loss_level_kernels<N>(pf, cs_pf, G, tg, U, B, h, w, sums, scale_mse, scale_tv, grad, cs_g, stream)
+#define VSTAB_LOSS_T(N) case N: return loss_level_kernels<N>(pf, cs_pf, G, tg, U, B, h, w, sums, scale_mse, scale_tv, grad, cs_g, pv, stream)
         VSTAB_LOSS_T(1); VSTAB_LOSS_T(2); VSTAB_LOSS_T(3); VSTAB_LOSS_T(4); VSTAB_LOSS_T(5); VSTAB_LOSS_T(6); VSTAB_LOSS_T(7); VSTAB_LOSS_T(8);
 #undef VSTAB_LOSS_T
     }
@@ -269,7 +313,8 @@ hipError_t launch_loss_level(const float *pf, const float *G, int Ct, int T, con
 {
     hipError_t e = hipMemsetAsync(sums, 0, sizeof(double) * (size_t)(T + 2) * B, stream);
     if (e != hipSuccess) return e;
-    return loss_level_dispatch(T, pf, 2, G, loss_targets(Ct, T, c_off, weights), U, B, h, w, sums, scale_mse, scale_tv, grad, 2, stream);
+    return loss_level_dispatch(T, pf, 2, G, loss_targets(Ct, T, c_off, weights), U, B, h, w, sums, scale_mse, scale_tv, grad, 2, LossPreview{},
+                               stream);
 }
 
 // workspace: the sums of every level, then the resized targets [B,h,w,Ct] and the resized unstable frame [B,h,w,3] of the largest level
@@ -295,8 +340,11 @@ size_t loss_main_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int 
 // ONE target of weight 1 has nothing to share: its levels resize the target's three channels alone (read in place from the Ct-channel
 // tensor) and hand the kernels that 3-channel G.  A level the slice resize does not take (same size inside wider pixels, or too large
 // for the tile kernel) resizes all Ct channels; the kernels then read the slice at c_off[0], which gives the same bits.
-hipError_t launch_loss_main(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
-                            const float *unstab, int B, int H, int W, double *loss_out, bool per_target, void *workspace, hipStream_t stream)
+// report (the loss report: per_target and per_level scalars): no gradient is written whatever lv[l].grad holds, and a level with a
+// preview [B,h,w,3] (previews NULL or previews[l] NULL: none) runs the pass-1 kernel that also stores its warped frame.
+static hipError_t loss_main_levels(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                                   const float *unstab, int B, int H, int W, double *loss_out, bool per_target, bool report,
+                                   void *const *previews, bool preview_u8, void *workspace, hipStream_t stream)
 {
     size_t sbytes, gbytes, ubytes;
     loss_main_layout(B, lv, n, Ct, T, sbytes, gbytes, ubytes);
@@ -311,6 +359,7 @@ hipError_t launch_loss_main(const LossLevel *lv, int n, const float *targets, in
     a.n = n;
     a.T = T;
     a.per_target = per_target ? 1 : 0;
+    a.per_level = report ? 1 : 0;
     for (int t = 0; t < T; ++t) a.c[t] = weights[t];
     const bool single = T == 1 && weights[0] == 1.0f;
     for (int l = 0; l < n; ++l) {
@@ -327,11 +376,28 @@ hipError_t launch_loss_main(const LossLevel *lv, int n, const float *targets, in
         if (!sliced && (e = launch_resize_bilinear(targets, B, H, W, Ct, G, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
         if ((e = launch_resize_bilinear(unstab, B, H, W, 3, U, lv[l].h, lv[l].w, stream)) != hipSuccess) return e;
         if ((e = loss_level_dispatch(T, lv[l].pf, lv[l].cs_pf, G, sliced ? loss_one_target() : tg, U, B, lv[l].h, lv[l].w, sums + (size_t)l * S * B,
-                                     1.0f, lv[l].tv_weight, lv[l].grad, lv[l].cs_grad, stream)) != hipSuccess)
+                                     1.0f, lv[l].tv_weight, report ? nullptr : lv[l].grad, lv[l].cs_grad,
+                                     LossPreview{previews ? previews[l] : nullptr, preview_u8}, stream)) != hipSuccess)
             return e;
     }
     loss_total_kernel<<<1, 64, 0, stream>>>(sums, B, a, loss_out);
     return hipGetLastError();
+}
+
+hipError_t launch_loss_main(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                            const float *unstab, int B, int H, int W, double *loss_out, bool per_target, void *workspace, hipStream_t stream)
+{
+    return loss_main_levels(lv, n, targets, Ct, T, c_off, weights, unstab, B, H, W, loss_out, per_target, false, nullptr, false, workspace,
+                            stream);
+}
+
+// The loss report of the test pass (main:277-326, 346-372): launch_loss_main's resizes and pass 1 with no gradient pass, the scalars
+// per level, and on request every level's warped frame.  out: 1 + T + 2 n doubles; workspace as launch_loss_main's.
+hipError_t launch_loss_report(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                              const float *unstab, int B, int H, int W, void *const *previews, bool preview_u8, double *out, void *workspace,
+                              hipStream_t stream)
+{
+    return loss_main_levels(lv, n, targets, Ct, T, c_off, weights, unstab, B, H, W, out, true, true, previews, preview_u8, workspace, stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -477,6 +543,42 @@ __global__ __launch_bounds__(256) void bn_lrelu_apply_kernel(float *__restrict__
     *reinterpret_cast<f32x4v *>(p) = v;
 }
 
+// BatchNormLayer(act = lrelu 0.1, is_train = False): the apply pass above on the MOVING statistics, rstd formed from moving_var as
+// bn_moments_final_kernel forms it from the batch variance.  A thread keeps one channel quad for BN_INF_ROWS rows, so the four double
+// divisions and square roots are paid once per 8 rows; the rows' loads are all issued before the first is used.
+constexpr int BN_INF_ROWS = 8;
+__global__ __launch_bounds__(256) void bn_lrelu_inference_kernel(float *__restrict__ zy, int cs, int c_off, int C4, long long rows,
+                                                                 const float *__restrict__ mov_mean, const float *__restrict__ mov_var,
+                                                                 const float *__restrict__ beta, float eps)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long groups = (rows + BN_INF_ROWS - 1) / BN_INF_ROWS;
+    if (idx >= groups * C4) return;
+    const long long rg = idx / C4;
+    const int c = (int)(idx - rg * C4) * 4;
+    const f32x4v m = *reinterpret_cast<const f32x4v *>(mov_mean + c), var = *reinterpret_cast<const f32x4v *>(mov_var + c);
+    const f32x4v b = *reinterpret_cast<const f32x4v *>(beta + c);
+    f32x4v s;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[e] = (float)(1.0 / sqrt((double)var[e] + (double)eps));
+    const long long r0 = rg * BN_INF_ROWS;
+    float *p = zy + r0 * cs + c_off + c;
+    f32x4v v[BN_INF_ROWS];
+#pragma unroll
+    for (int u = 0; u < BN_INF_ROWS; ++u)
+        if (r0 + u < rows) v[u] = *reinterpret_cast<const f32x4v *>(p + (long long)u * cs);
+#pragma unroll
+    for (int u = 0; u < BN_INF_ROWS; ++u) {
+        if (r0 + u >= rows) break;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float y = (v[u][e] - m[e]) * s[e] + b[e];
+            v[u][e] = fmaxf(y, 0.1f * y);
+        }
+        *reinterpret_cast<f32x4v *>(p + (long long)u * cs) = v[u];
+    }
+}
+
 // backward sums: sums[c] = sum g, sums[C + c] = sum g * xhat (chunks added in order); dbeta = sum g
 __global__ __launch_bounds__(1024) void bn_bwd_final_kernel(const float *__restrict__ part, int chunks, int C, float *__restrict__ sums,
                                                             float *__restrict__ dbeta, int accumulate)
@@ -549,6 +651,16 @@ hipError_t launch_bn_lrelu_train_forward(float *zy, long long rows, int cs, int 
                                                                                        save_mean, save_rstd, mov_mean, mov_var);
     const long long n4 = rows * (C / 4);
     bn_lrelu_apply_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream>>>(zy, cs, c_off, C / 4, rows, save_mean, save_rstd, beta);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_lrelu_inference_forward(float *zy, long long rows, int cs, int c_off, int C, const float *beta, const float *mov_mean,
+                                             const float *mov_var, float eps, hipStream_t stream)
+{
+    if ((C & 3) || (cs & 3) || (c_off & 3)) return hipErrorInvalidValue;
+    const long long n = (rows + BN_INF_ROWS - 1) / BN_INF_ROWS * (C / 4);
+    bn_lrelu_inference_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(zy, cs, c_off, C / 4, rows, mov_mean, mov_var, beta,
+                                                                                          eps);
     return hipGetLastError();
 }
 

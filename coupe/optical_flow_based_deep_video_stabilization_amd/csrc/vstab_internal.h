@@ -546,6 +546,11 @@ size_t loss_main_workspace_bytes(int B, const LossLevel *lv, int n, int Ct, int 
 // all levels in one call; loss_out: the objective, and with per_target the T unweighted per-target shares after it
 hipError_t launch_loss_main(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
                             const float *unstab, int B, int H, int W, double *loss_out, bool per_target, void *workspace, hipStream_t stream);
+// the test pass's report: the same sums with no gradient (lv[l].grad is ignored); out = total, T per-target shares, then mse_l and var_l of
+// the n levels; previews (nullable, n nullable entries): each level's warped frame [B,h,w,3], float32 or uint8 fix_image_tf(P, 1)
+hipError_t launch_loss_report(const LossLevel *lv, int n, const float *targets, int Ct, int T, const int *c_off, const float *weights,
+                              const float *unstab, int B, int H, int W, void *const *previews, bool preview_u8, double *out, void *workspace,
+                              hipStream_t stream);
 hipError_t launch_flow_medfilt(const float *flow, int B, int h, int w, int kh, int kw, int kc, float *out, hipStream_t stream);
 
 // SSIM structure term, its gradient and the 2x2 SAME average pool (ssim_ops.hip; utils.py:74-166).  win: the 1-D vector whose outer
@@ -665,6 +670,9 @@ int bn_chunks(long long rows, int C);
 hipError_t launch_bn_lrelu_train_forward(float *zy, long long rows, int cs, int c_off, int C, const float *beta, float *mov_mean,
                                          float *mov_var, float decay, float eps, float *save_mean, float *save_rstd, float *scratch,
                                          hipStream_t stream);
+// the same layer with is_train = False: the moving statistics normalise and are not written; no scratch
+hipError_t launch_bn_lrelu_inference_forward(float *zy, long long rows, int cs, int c_off, int C, const float *beta, const float *mov_mean,
+                                             const float *mov_var, float eps, hipStream_t stream);
 hipError_t launch_bn_lrelu_train_backward(const float *y, int cs_y, int cy_off, float *dy, int cs_g, int cg_off, int C, long long rows,
                                           const float *beta, const float *save_rstd, float *dbeta, int accumulate, float *scratch,
                                           hipStream_t stream);

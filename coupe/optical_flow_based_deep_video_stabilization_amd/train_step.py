@@ -105,6 +105,7 @@ class Trainer:
         self.overlap_single_rank = False      # tests: run the overlapped exchange even when the process group has one rank
         self.wino_min_flops = 3.0e9           # a 3x3 stride-1 stage runs in Winograd form once its GEMM issues this much
         self._ws = torch.empty(1 << 20, dtype=torch.uint8, device=self.dev)
+        self._test_activations = False        # True from forward_test until the next forward: no backward pass from those activations
         self._alloc_buffers()
 
     # ------------------------------------------------------------------ parameters
@@ -298,6 +299,13 @@ class Trainer:
                                                         BN_DECAY, BN_EPS, mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), ws.numel(), self.st))
         self.save[name] = (mean, rstd)
 
+    def _bn_test(self, name, buf, c_off, C):
+        """The layer with is_train=False: the moving statistics normalise and stay as they are; nothing is saved for a backward."""
+        rows = buf.shape[0] * buf.shape[1] * buf.shape[2]
+        self._check(self.L.vstab_bn_lrelu_inference_forward(buf.data_ptr(), rows, buf.shape[3], c_off, C, self.p[f"{name}/beta"].data_ptr(),
+                                                            self.p[f"{name}/moving_mean"].data_ptr(),
+                                                            self.p[f"{name}/moving_variance"].data_ptr(), BN_EPS, self.st))
+
     def _bn_bwd(self, name, y, G, c_off, C):
         rows = y.shape[0] * y.shape[1] * y.shape[2]
         ws = self._workspace(self.L.vstab_bn_scratch_bytes(rows, C))
@@ -330,11 +338,23 @@ class Trainer:
     def _axpby(self, a, x, b, y, out):
         self._check(self.L.vstab_axpby(x.data_ptr(), float(a), y.data_ptr(), float(b), out.data_ptr(), x.numel(), self.st))
 
-    # ------------------------------------------------------------------ forward (is_train=True)
+    # ------------------------------------------------------------------ forward (is_train=True), forward_test (is_train=False)
     def forward(self, feats: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return self._forward(feats, test=False)
+
+    def forward_test(self, feats: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """`flownetS_pyramid(..., is_train=False, reuse=True)` (main:185) on the training graph's own variables: `forward` with every
+        BatchNorm on its moving statistics -- the same buffers, convolution plans and heads, no copy of the weights.  Parameters,
+        moving statistics, gradients and Adam state are left as they are.  The activations ARE overwritten, and no batch statistics
+        are saved: a backward pass needs a fresh `forward` first (loss_and_backward / backward_from_flow_grads raise until then)."""
+        return self._forward(feats, test=True)
+
+    def _forward(self, feats, test: bool):
         if tuple(feats.shape) != (self.B, self.H, self.W, 27) or feats.dtype != torch.float32 or not feats.is_cuda:
             raise ValueError(f"feats must be a float32 CUDA tensor {(self.B, self.H, self.W, 27)}")
         self.st = runtime.stream_ptr()
+        self._test_activations = test
+        bn = self._bn_test if test else self._bn_fwd
         a, p = self.a, self.p
         a["x0"][..., :27].copy_(feats)              # the 28-channel copy the first layer's filter gradient reads
         for name, k, s, pad, cout in ENC:                                                # model.py:807-844
@@ -344,7 +364,7 @@ class Trainer:
                 pass                                 # the first layer on the inference path's row-window kernel, straight from the 27-channel input
             elif not (k == 3 and s == 1 and self._wino(a[ib], ioff, p[f"{name}/W_conv2d"], False, p[f"{name}/b_conv2d"], a[ob], ooff, 0)):
                 self._conv_fwd(a[ib], ioff, cin, p[f"{name}/W_conv2d"], p[f"{name}/b_conv2d"], k, s, pad, a[ob], ooff, cout)
-            self._bn_fwd(name, a[ob], ooff, cout)
+            bn(name, a[ob], ooff, cout)
         prev = None
         for dname, ib, _cin, ob, ooff, cout, pname, uname, foff in DEC:                   # model.py:847-880
             level = "predict_flow" + pname[-1]
@@ -360,7 +380,7 @@ class Trainer:
             # upsample_flowN into the next concat's flow channels, deconvN + BatchNorm into its middle slice
             self._convT(self.pf[level], 0, 4, p[f"{uname}/W_deconv2d"], p[f"{uname}/b_deconv2d"], 4, 2, 1, a[ob], foff, 4, False)
             self._convT(a[ib], 0, a[ib].shape[3], p[f"{dname}/W_deconv2d"], p[f"{dname}/b_deconv2d"], 4, 2, 1, a[ob], ooff, cout, False)
-            self._bn_fwd(f"{dname}_bn", a[ob], ooff, cout)
+            bn(f"{dname}_bn", a[ob], ooff, cout)
             prev = level
         # full-resolution head (model.py:882-887) through its tap table, as in the inference path: the padded, nearest-upsampled
         # concat2 (1.6 GB at B=8 512x512) never exists.  T[s][tap*2+o] = sum_c concat2[s][c] W[tap][c][o] is a 1x1 conv.
@@ -423,6 +443,7 @@ class Trainer:
         """loss_main (main:213-217, 269-275; with an objective: main_flownetS_pyramid.py:200-250) and d loss_main / d every trainable
         tensor (into self.g)."""
         from .training import loss_main_fused, loss_main_multi
+        self._need_train_activations()
         self._zero_grads()
         if self.objective is None:
             total = loss_main_fused(self.pf, gtstab, unstab, self.dpf)    # all five levels, gradients straight into dpf[..., :2]
@@ -434,10 +455,35 @@ class Trainer:
     def backward_from_flow_grads(self, dflows: Dict[str, torch.Tensor]):
         """Vector-Jacobian product of the network alone: given d L / d predict_flowN [B,h,w,2] for the five flows, fills
         self.g with d L / d every trainable tensor (what tf.gradients(flows, vars, grad_ys=dflows) returns)."""
+        self._need_train_activations()
         self._zero_grads()
         for level in LOSS_LEVELS:
             self.dpf[level][..., :2].copy_(dflows[level])
         self._backward()
+
+    def _need_train_activations(self):
+        if self._test_activations:
+            raise RuntimeError("the activations are those of forward_test (BatchNorm on its moving statistics, nothing saved): run "
+                               "forward before a backward pass")
+
+    # ------------------------------------------------------------------ the test pass (main:277-326, 431-441)
+    def evaluate(self, feats, gtstab, unstab, previews: str = None):
+        """`sess.run(loss_sum_test_main)` and, with previews ('uint8' as the image log, or 'float32'), `image_sum`'s warpedimg2..6
+        (main:279-283, 326, 365-371): forward_test, then the Trainer's objective on the test-mode flows as a `training.LossReport`.
+        With an objective, gtstab is the multi-channel stable tensor, as in `step`.  Nothing is synchronised."""
+        from .training import loss_report
+        with torch.cuda.device(self.dev):
+            self.forward_test(feats)
+            return loss_report(self.pf, gtstab, unstab, self.objective, previews)
+
+    def test_epoch(self, batches):
+        """The test loop of main:431-441 over an iterable of (feats, gtstab, unstab) CUDA batches or a `Data_Loader`: `evaluate` on
+        every full batch -- a short one is skipped (main:438) -- and the totals `loss_main_test` as host floats, synchronising once
+        at the end.  A `Data_Loader` yields the 3-channel gtstab and so serves the default objective only (as in `train_epoch`); a
+        Trainer with an `Objective` takes an iterable whose second element is the multi-channel stable tensor, e.g.
+        `(feed['feats'], feed['stab_image'], feed['unstab_image'])` of `feed_the_network()`."""
+        totals = [self.evaluate(f, g, u).total for f, g, u in batches if f.shape[0] == self.B]
+        return [float(v) for v in torch.stack(totals).cpu()] if totals else []
 
     def _zero_grads(self):
         # the activation gradients are NOT cleared: the first gradient written into each buffer in _backward covers all of its

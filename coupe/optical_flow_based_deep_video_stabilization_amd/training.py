@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -219,6 +219,68 @@ def loss_main_multi(flows: Dict[str, torch.Tensor], stab_image, unstab_image, ob
     return out[0], out[1:]
 
 
+# ----------------------------------------------------------------------------- the test pass's report of the objective
+@dataclass
+class LossReport:
+    """What the reference logs of loss_main on a batch (main:346-372), float64 CUDA tensors: `total` (0-dim; `loss_main_test`), `mse` and
+    `tv` [5] in LOSS_LEVELS order (the summary scalars loss6..loss2 and var6..var2; total = mse.sum() + tv.sum() up to the last bit),
+    `per_target` [T] (unweighted, summed over the levels, as loss_main_multi returns them) and `warped`: {level: warpedimgN [B,h,w,3]},
+    float32 or the uint8 `fix_image_tf(warpedimgN, 1)` of the image log, or None when no previews were asked for."""
+    total: torch.Tensor
+    mse: torch.Tensor
+    tv: torch.Tensor
+    per_target: torch.Tensor
+    warped: Optional[Dict[str, torch.Tensor]]
+
+
+_PREVIEW_DTYPES = {"float32": (0, torch.float32), "uint8": (1, torch.uint8)}
+
+
+def loss_report(flows: Dict[str, torch.Tensor], stab_image, unstab_image, objective: Objective = None, previews: str = None, *,
+                preview_levels=None) -> LossReport:
+    """loss_main of `objective` with its terms level by level and, on request, lossterm's second return value `warpedimg` of every
+    level, through ONE library call without a gradient pass (`vstab_loss_report`): what the reference's test pass and summaries read
+    (main:277-326, 346-372).  flows as loss_main_fused takes them (the Trainer's 4-channel pixels included).  objective None:
+    OBJECTIVE_NOPREV on a 3-channel stab_image; otherwise stab_image is the multi-channel stable tensor of loss_main_multi.
+    previews: None, 'uint8' (`utils.fix_image_tf(warpedimg, 1)`) or 'float32'; preview_levels: the LOSS_LEVELS names to store (all when
+    None) -- a level left out runs the kernel without the store.  `total` and `per_target` are what loss_main_fused / loss_main_multi
+    return on the same inputs.  Nothing is synchronised."""
+    import ctypes as C
+    unstab = _f32(unstab_image, "unstab_image", 3)
+    if objective is None:
+        objective, stab = OBJECTIVE_NOPREV, _f32(stab_image, "stab_image", 3)
+    else:
+        stab = _f32c(stab_image, "stab_image")
+    B, H, W, Ct = stab.shape
+    if unstab.shape[:3] != stab.shape[:3]:
+        raise ValueError("stab_image / unstab_image must have the same batch and frame size")
+    if previews is not None and previews not in _PREVIEW_DTYPES:
+        raise ValueError("previews must be None, 'uint8' or 'float32'")
+    T, offs, wts, _w = _targets(objective.target_channels, objective.target_weights, Ct)
+    desc = _level_descs(flows, None, objective.tv_weights, B)
+    nl = len(LOSS_LEVELS)
+    warped, ptrs, code = None, None, 0
+    if previews is not None:
+        code, dtype = _PREVIEW_DTYPES[previews]
+        names = LOSS_LEVELS if preview_levels is None else tuple(preview_levels)
+        if not set(names) <= set(LOSS_LEVELS):
+            raise ValueError(f"preview_levels must be among {LOSS_LEVELS}")
+        warped = {k: torch.empty((B, flows[k].shape[1], flows[k].shape[2], 3), dtype=dtype, device=stab.device) for k in LOSS_LEVELS if k in names}
+        ptrs = (C.c_void_p * nl)(*[warped[k].data_ptr() if k in warped else None for k in LOSS_LEVELS])
+    L = _lib.lib()
+    n = L.vstab_loss_report_workspace_bytes(C.addressof(desc), nl, B, Ct, T)
+    if n == 0:
+        raise ValueError("loss_report: the library rejects the level descriptors (even channel counts >= 2, 8-byte aligned flows, level "
+                         "sizes below 2^31 / 3 pixels, B <= 65535)")
+    ws = torch.empty(n, dtype=torch.uint8, device=stab.device)
+    out = torch.empty(1 + T + 2 * nl, dtype=torch.float64, device=stab.device)
+    with torch.cuda.device(stab.device):
+        _lib.check(L.vstab_loss_report(C.addressof(desc), nl, stab.data_ptr(), Ct, T, offs, wts, unstab.data_ptr(), B, H, W,
+                                       C.addressof(ptrs) if ptrs is not None else None, code, out.data_ptr(), ws.data_ptr(), n,
+                                       runtime.stream_ptr()))
+    return LossReport(out[0], out[1 + T:1 + T + nl], out[1 + T + nl:], out[1:1 + T], warped)
+
+
 # ----------------------------------------------------------------------------- backward building blocks
 def conv_wgrad(x, gout, k: int, stride: int, pad: int, cx_off: int = 0, cin: int = None, cg_off: int = 0, cout: int = None,
                dW=None, db=None, accumulate: bool = False, want_db: bool = True):
@@ -306,6 +368,16 @@ def bn_lrelu_train_forward(z, beta, moving_mean=None, moving_var=None, decay: fl
                                                   moving_var.data_ptr() if moving_var is not None else None, float(decay), float(eps),
                                                   mean.data_ptr(), rstd.data_ptr(), sc.data_ptr(), sc.numel(), runtime.stream_ptr()))
     return z, mean, rstd
+
+
+def bn_lrelu_inference_forward(z, beta, moving_mean, moving_var, eps: float = 1e-5, c_off: int = 0, C: int = None):
+    """BatchNormLayer(act=lrelu 0.1, is_train=False, gamma_init=None) IN PLACE on channels c_off..+C of z: y = lrelu((z - moving_mean)
+    * rsqrt(moving_var + eps) + beta).  The moving statistics are read only.  Returns y (= z)."""
+    rows, cs, C = _rows_view(z, c_off, C)
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.lib().vstab_bn_lrelu_inference_forward(z.data_ptr(), rows, cs, c_off, C, beta.data_ptr(), moving_mean.data_ptr(),
+                                                               moving_var.data_ptr(), float(eps), runtime.stream_ptr()))
+    return z
 
 
 def bn_lrelu_train_backward(y, dy, beta, save_rstd, cy_off: int = 0, cg_off: int = 0, C: int = None, dbeta=None, accumulate: bool = False):

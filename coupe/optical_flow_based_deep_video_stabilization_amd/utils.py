@@ -15,7 +15,9 @@ Two things are kept or changed on purpose:
     pow(c, 0) is 0 * c^-1, which is NaN wherever a window is flat (sqrt(0)) or fp32 cancellation leaves a variance slightly
     negative; here the gradient is that of s alone and is finite there.
 The autograd path is taken only when gradients are enabled and an image requires grad.  Values and gradients are summed without
-atomics in a fixed order: two runs give the same bits."""
+atomics in a fixed order: two runs give the same bits.
+
+`fix_image_tf` (:434), the image log's float -> uint8 conversion, is here too."""
 from __future__ import annotations
 
 import torch
@@ -200,3 +202,13 @@ def tf_ms_ssim(img1, img2, batch_size, mean_metric=True, level=5):
             a, b = avg_pool_2x2_same(a), avg_pool_2x2_same(b)
     value = torch.prod(torch.stack(mcs, dim=0)).expand(int(batch_size))
     return value.mean() if mean_metric else value
+
+
+def fix_image_tf(image, norm_value):
+    """utils.py:434: tf.cast(image / norm_value * 255., tf.uint8) on a float tensor, for the image log (main:365-371).  The quotient
+    and the product are rounded in the image's type, the result is saturated to 0..255 and then truncated toward zero: TensorFlow's
+    cast is undefined outside the range, and a warped frame holds tiny negative values where clamped corners make the bilinear
+    weights cancel.  The same rule as the uint8 previews of `training.loss_report` (norm_value 1).  Plain torch, no kernel."""
+    if not torch.is_tensor(image) or not image.is_floating_point():
+        raise ValueError("image must be a float tensor")
+    return (image / norm_value * 255.0).clamp(0.0, 255.0).to(torch.uint8)

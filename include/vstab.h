@@ -546,6 +546,22 @@ VSTAB_API size_t vstab_loss_main_multi_workspace_bytes(const vstab_loss_level_de
 VSTAB_API int vstab_loss_main_multi(const vstab_loss_level_desc *levels, int n_levels, const float *targets, int Ct, int T, const int *c_off,
                                     const float *weights, const float *unstab, int B, int H, int W, double *loss_out, void *workspace,
                                     size_t workspace_bytes, void *stream);
+/* The loss report of the test pass (main:277-326, 346-372): vstab_loss_main_multi's value from the same sums, without the gradient
+ * pass (levels[l].grad and cs_grad are ignored, nothing is written there), with the scalars the reference logs per level and, on
+ * request, each level's warped frame.
+ *   out: device double[1 + T + 2 * n_levels] = total (what vstab_loss_main[_multi] returns from the same sums: the same double
+ *        arithmetic in the same order), the T unweighted per-target shares, then mse_l = sum_t weights[t] * mean_b(masked_MSE_t) of
+ *        every level (loss6..loss2) and var_l = tv_weight_l * sum_b TV of every level (var6..var2).
+ *   previews: NULL, or HOST array of n_levels device pointers, each NULL or [B,h,w,3] of that level's size: tf_warp(unstab resized,
+ *        flow) -- lossterm's second return value `warpedimg`, before the mask -- as float32 (preview_dtype 0) or as uint8
+ *        utils.fix_image_tf(warpedimg, 1) (preview_dtype 1): warpedimg * 255 saturated to 0..255, then truncated toward zero.  The
+ *        preview is stored by the kernel that forms the sums: one flow read and one gather per pixel serve both.
+ * Workspace, limits and errors as vstab_loss_main_multi, judged in its order; then VSTAB_E_SHAPE for preview_dtype outside {0, 1} and
+ * VSTAB_E_ALIGN for a float32 preview that is not 4-byte aligned.  A refused call allocates and launches nothing. */
+VSTAB_API size_t vstab_loss_report_workspace_bytes(const vstab_loss_level_desc *levels, int n_levels, int B, int Ct, int T);
+VSTAB_API int vstab_loss_report(const vstab_loss_level_desc *levels, int n_levels, const float *targets, int Ct, int T, const int *c_off,
+                                const float *weights, const float *unstab, int B, int H, int W, void *const *previews, int preview_dtype,
+                                double *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- image similarity: tf_ssim / tf_ms_ssim of the reference's utils.py (:74-166) --------------------------------------------
  * img1, img2: [B,H,W] (one channel).  With the size x size window of _tf_fspecial_gauss(size, sigma) (:74-89; offsets
@@ -740,7 +756,14 @@ VSTAB_API size_t vstab_bn_scratch_bytes(long long rows, int C);
 VSTAB_API int vstab_bn_lrelu_train_forward(float *zy, long long rows, int cs, int c_off, int C, const float *beta, float *moving_mean,
                                            float *moving_var, float decay, float eps, float *save_mean, float *save_rstd, void *scratch,
                                            size_t scratch_bytes, void *stream);
-/* Its backward: dy (gradient w.r.t. y, channels cg_off..+C of a [rows, cs_g] tensor) is overwritten by the gradient w.r.t.
+/* The same layer with is_train=False (outputs_test, main:185), IN PLACE on the same slice: y = lrelu((z - moving_mean) * rstd + beta)
+ * with rstd = (float)(1 / sqrt((double)moving_var + (double)eps)).  Writes nothing but the slice -- the moving statistics are only
+ * read -- and needs no scratch.  As for the training entry: VSTAB_E_STATE for a NULL buffer; VSTAB_E_SHAPE for rows < 1, C < 1,
+ * c_off < 0 or c_off + C > cs; VSTAB_E_ALIGN unless C, cs and c_off are multiples of 4 and zy, beta, moving_mean and moving_var are
+ * 16-byte aligned. */
+VSTAB_API int vstab_bn_lrelu_inference_forward(float *zy, long long rows, int cs, int c_off, int C, const float *beta,
+                                               const float *moving_mean, const float *moving_var, float eps, void *stream);
+/* The training-mode layer's backward: dy (gradient w.r.t. y, channels cg_off..+C of a [rows, cs_g] tensor) is overwritten by the gradient w.r.t.
  * the layer's input z; dbeta [C] = sum dy*lrelu'(y) (may be NULL).  y: the forward's output (xhat is recovered from it). */
 VSTAB_API int vstab_bn_lrelu_train_backward(const float *y, int cs_y, int cy_off, float *dy, int cs_g, int cg_off, int C, long long rows,
                                             const float *beta, const float *save_rstd, float *dbeta, int accumulate, void *scratch,
