@@ -11,4 +11,5 @@ from .warp_flow import tf_warp, get_pixel_value, resize_images, resize_images_sl
 from .pipeline import stabilise_originalsize, stabilise_native, OriginalSizeStabiliser  # noqa: F401
 from .utils import _tf_fspecial_gauss, tf_ssim, tf_ms_ssim, fix_image_tf  # noqa: F401
 from .cell import ConvLSTMCell, ConvGRUCell, LSTMStateTuple, run_sequence  # noqa: F401
-from . import spatial_transformer, warp, vgg16, NLDF, clip_driver, postfilters, training, train_step, utils, cell, data_loader  # noqa: F401,E402  (secondary samplers)
+from .flow_vis import flow_to_image, compute_color, make_color_wheel  # noqa: F401
+from . import spatial_transformer, warp, vgg16, NLDF, clip_driver, postfilters, training, train_step, utils, cell, data_loader, flow_vis  # noqa: F401,E402  (secondary samplers)

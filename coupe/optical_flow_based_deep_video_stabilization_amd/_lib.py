@@ -190,6 +190,8 @@ EXPORTS = {
     "vstab_ssim_backward": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "vstab_avgpool2x2_same": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "vstab_avgpool2x2_same_backward": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "vstab_flow_to_image_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "vstab_flow_to_image": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "vstab_convlstm_gates_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "vstab_convlstm_gates": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_int] * 3 +
                              [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -566,6 +566,14 @@ hipError_t launch_ssim_backward(const float *img1, const float *img2, int B, int
 hipError_t launch_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, hipStream_t stream);
 hipError_t launch_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, hipStream_t stream);
 
+// Middlebury colour code of a flow field (flow_vis_ops.hip; flow_to_image, main_flownetS_pyramid.py:824-957).  Without maxrad_in a
+// first launch leaves flow_vis_partials(H, W) floats per sample in partial (one workgroup per FLOW_VIS_SLICE pixels, at most
+// FLOW_VIS_MAX_PARTIALS); flow 8-byte aligned, B <= 65535, B*H*W < 2^31 (the entry point checks).
+constexpr int FLOW_VIS_SLICE = 2048, FLOW_VIS_MAX_PARTIALS = 128;
+int flow_vis_partials(int H, int W);
+hipError_t launch_flow_to_image(const float *flow, int B, int H, int W, const float *maxrad_in, unsigned char *img, unsigned char *anglemap,
+                                float *maxrad_out, float *partial, hipStream_t stream);
+
 // What follows the convolution in a ConvLSTMCell / ConvGRUCell step (cell_ops.hip; cell.py:5-136).  y: the convolution's output
 // [B, HW, ys]; states [B, HW*F] contiguous or slices of a wider NHWC buffer (pointer to the first channel of pixel 0 + pixel stride);
 // act 0 tanh, 1 relu, 2 identity.  A workgroup reduces CELL_CHUNK elements of one sample; workspace sizes are 0 without normalize.

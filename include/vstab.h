@@ -592,6 +592,29 @@ VSTAB_API int vstab_ssim_backward(const float *img1, const float *img2, int B, i
 VSTAB_API int vstab_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, void *stream);
 VSTAB_API int vstab_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, void *stream);
 
+/* ---- flow visualisation: flow_to_image / compute_color / make_color_wheel of the reference's main scripts
+ * (main_flownetS_pyramid.py:824-957), the Middlebury colour code ------------------------------------------------------------------
+ * flow: [B,H,W,2] float32, dense, read only (the reference zeroes unknown pixels in the caller's array; this does not).
+ * img: [B,H,W,3] uint8.  anglemap (may be NULL): [B,H,W,3] uint8, the angle as a gray value in all three channels.
+ * maxrad_in: NULL, or [B] device floats, the radius each sample's flow is divided by (a video wants one value for all frames).
+ * With NULL each sample's own largest radius is found first: a pixel with |u| > 1e7 or |v| > 1e7 is unknown and counts as (0,0), a
+ * pixel with a NaN component is left out (in the reference it makes the maximum come out as -1, an accident of argument order),
+ * and the radius is sqrt(max(u*u + v*v)) in float32.  maxrad_out (may be NULL): [B] receives the radii used, given or found.
+ * Per pixel, with d = maxrad > 0 ? maxrad : 2^-52 and un = u / d, vn = v / d in float32 (the reference adds float64 eps to the
+ * float32 maximum and divides a float32 array by the sum, which under the NumPy of its day is a float32 division by the maximum):
+ *   rad = sqrtf(un*un + vn*vn);  a = atan2f(-vn, -un) / pi;  fk = (a + 1) / 2 * 54 + 1;  k0 = floor(fk), k1 = k0 + 1 (56 -> 1)
+ *   col = (1 - f) wheel[k0-1]/255 + f wheel[k1-1]/255 with f = fk - k0, in float64 from here;
+ *   col = rad <= 1 ? 1 - rad (1 - col) : 0.75 col;  img byte = floor(255 col);  anglemap byte = trunc(a * 127 + 128) in float32.
+ * Unknown and NaN pixels are black in img and 1 (the angle of (+0,+0)) in anglemap.  Everything is stream-ordered, nothing
+ * synchronises with the host, and no atomics are used: two calls give the same bytes.
+ * workspace: vstab_flow_to_image_workspace_bytes() bytes, 4-byte aligned, needed only without maxrad_in.
+ * VSTAB_E_STATE for a NULL flow or img, or a NULL workspace without maxrad_in (checked first); VSTAB_E_SHAPE unless
+ * 1 <= B <= 65535, H, W >= 1 and B*H*W < 2^31 (the workspace query returns 0 for such arguments); VSTAB_E_ALIGN unless flow is
+ * 8-byte and the radii are 4-byte aligned; VSTAB_E_NOMEM when the workspace is too small. */
+VSTAB_API size_t vstab_flow_to_image_workspace_bytes(int B, int H, int W);
+VSTAB_API int vstab_flow_to_image(const float *flow, int B, int H, int W, const float *maxrad_in, unsigned char *img, unsigned char *anglemap,
+                                  float *maxrad_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The recurrent cells of cell.py (ConvLSTMCell :5-76, ConvGRUCell :78-136), forward (backward: next block): what follows each cell's SAME convolution
  * over concat([x, h]) -- that convolution is vstab_conv_forward on the caller's concat buffer.  y: the convolution's output
  * [B,H,W,ys] (ys >= the gate channels; rows may be padded); states [B,H,W,F] contiguous, or slices of a wider NHWC buffer given as
