@@ -31,7 +31,7 @@ current values (the padded device copies are rebuilt once per call, not per step
 grad mode is on and x, the state or a parameter requires grad, the results hang on one torch.autograd.Function per `call` /
 `run_sequence` (the whole sequence: back-propagation through time inside it); gradients flow to the inputs, the initial state and every
 parameter, `needs_input_grad` decides what is computed, forward values are bit-equal to the default path's.  Backward of a step: the
-gate-stage backward kernels of csrc/cell_ops.hip (`training.convlstm_gates_backward`, `convgru_update_backward`,
+gate-stage backward kernels of csrc/cell_ops.hip (`cell_grad.convlstm_gates_backward`, `convgru_update_backward`,
 `convgru_gates_backward`), then `training.conv_wgrad` and `training.conv_dgrad` on the concat buffer.  First derivatives only.
 
 Not built: data_format='channels_first' (the reference passes 'NC' with feature axis 0 for it, which is wrong for a
@@ -45,7 +45,8 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib, runtime
+from . import _lib, runtime, training
+from .runtime import _up4
 
 LSTMStateTuple = collections.namedtuple("LSTMStateTuple", ("c", "h"))
 
@@ -63,10 +64,6 @@ def _act_code(activation) -> int:
     if activation is torch.relu:
         return 1
     raise NotImplementedError(f"activation {activation!r}: 'tanh', 'relu' or 'identity' (torch.tanh, torch.relu, None)")
-
-
-def _up4(n: int) -> int:
-    return (n + 3) // 4 * 4
 
 
 def _as_f32(value, name, shape):
@@ -540,7 +537,6 @@ class _LstmSequence(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out, g_c):
-        from . import training
         cell, dev, steps = ctx.cell, ctx.dev, _saved_steps(ctx)
         T, F, cx, hoff, k, m = len(steps), cell._filters, cell._cx, cell._hoff, cell._k, 4 * cell._filters
         need_in, need_c0, need_h0 = ctx.needs_input_grad[1:4]
@@ -601,7 +597,6 @@ class _GruSequence(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_out):
-        from . import training
         cell, dev, steps = ctx.cell, ctx.dev, _saved_steps(ctx)
         T, F, cx, hoff, k = len(steps), cell._filters, cell._cx, cell._hoff, cell._k
         need_in, need_h0 = ctx.needs_input_grad[1:3]

@@ -43,8 +43,7 @@ def resize_u8(src: torch.Tensor, size_hw, out: Optional[torch.Tensor] = None) ->
     if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (n, dh, dw, 3) or not out.is_contiguous() or out.device != src.device):
         raise ValueError("out must be a contiguous uint8 tensor [n, h, w, 3] on src's device")
     dst = out if out is not None else torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.lib().vstab_resize_u8(src.data_ptr(), n, sh, sw, dst.data_ptr(), dh, dw, runtime.stream_ptr()))
+    runtime.call(src.device, "vstab_resize_u8", src.data_ptr(), n, sh, sw, dst.data_ptr(), dh, dw)
     return dst
 
 
@@ -153,9 +152,7 @@ class ClipStabiliser:
                                                   runtime.stream_ptr()))                                   # main:568
             flows, outflow, warped = stabilise_originalsize(self.feats, self.frame_f, scope=self.scope, flow_filter=self.flow_filter)    # main:569
             out = torch.empty_like(f)
-            with torch.cuda.device(self.device):
-                _lib.check(L.vstab_quantise_output(warped.data_ptr(), self.n * self.out_h * self.out_w, out.data_ptr(),
-                                                   runtime.stream_ptr()))                                  # main:625,630
+            runtime.call(self.device, "vstab_quantise_output", warped.data_ptr(), self.n * self.out_h * self.out_w, out.data_ptr())    # main:625,630
             resize_u8(out, (self.net_h, self.net_w), out=self.ring[i % RING])    # what later frames read back (main:556), written in place
         self.last_flows, self.last_outflow = flows, outflow
         self.i += 1
@@ -204,14 +201,12 @@ class NativeClipStabiliser:
         f = _u8(frame_bgr_u8, "frame")
         if f.shape[0] != self.n:
             raise ValueError(f"frame must hold {self.n} clips, got {f.shape[0]}")
-        L = _lib.lib()
         i = self.i
         cur_small = resize_u8(f, (self.net_h, self.net_w))                       # main:842-843
         slots = [cur_small if i == 0 else self.ring[max(i - lag, 0) % RING] for lag in self.LAGS]      # main:845-849
         slots.append(cur_small)
         ptrs = (C.c_void_p * 9)(*[s.data_ptr() for s in slots])
-        with torch.cuda.device(self.device):
-            _lib.check(L.vstab_assemble_input(ptrs, self.n, self.net_h, self.net_w, self.feats.data_ptr(), runtime.stream_ptr()))
+        runtime.call(self.device, "vstab_assemble_input", ptrs, self.n, self.net_h, self.net_w, self.feats.data_ptr())
         flows = flownetS_pyramid(self.feats, self.n, is_train=False, scope=self.scope)                  # main:804
         of = flows['predict_flow2']
         flow = self.flow_filter(of) if self.flow_filter is not None else of
@@ -219,9 +214,7 @@ class NativeClipStabiliser:
         unstab = resize_images_slice3(self.feats, 24, (fh, fw))                                          # main:806
         warped = tf_warp(unstab, flow, fh, fw)                                                          # main:807
         out = torch.empty((self.n, self.net_h, self.net_w, 3), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(L.vstab_resize_f32_to_u8(warped.data_ptr(), self.n, fh, fw, out.data_ptr(), self.net_h, self.net_w,
-                                                runtime.stream_ptr()))                                   # main:861, 863
+        runtime.call(self.device, "vstab_resize_f32_to_u8", warped.data_ptr(), self.n, fh, fw, out.data_ptr(), self.net_h, self.net_w)    # main:861, 863
         self.ring[i % RING].copy_(out)
         self.last_flows = flows
         self.i += 1

@@ -31,7 +31,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib, runtime
+from . import runtime
 
 _SEGMENTS = (15, 6, 4, 11, 13, 6)                   # RY, YG, GC, CB, BM, MR
 
@@ -54,7 +54,6 @@ def make_color_wheel():
 def _run(flow: torch.Tensor, maxrad, want_anglemap: bool):
     """flow [B,H,W,2] float32 CUDA, contiguous; maxrad None or a [B] float32 CUDA tensor -> img, anglemap or None, radii [B]"""
     B, H, W, _ = flow.shape
-    L = _lib.lib()
     dev = flow.device
     if B * H * W == 0:
         raise ValueError(f"flow_to_image: empty flow {tuple(flow.shape)}")
@@ -63,14 +62,9 @@ def _run(flow: torch.Tensor, maxrad, want_anglemap: bool):
     img = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
     ang = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) if want_anglemap else None
     used = torch.empty((B,), dtype=torch.float32, device=dev)
-    ws, n = None, 0
-    if maxrad is None:
-        n = int(L.vstab_flow_to_image_workspace_bytes(B, H, W))
-        ws = torch.empty(max(n, 4), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.vstab_flow_to_image(flow.data_ptr(), B, H, W, None if maxrad is None else maxrad.data_ptr(), img.data_ptr(),
-                                         ang.data_ptr() if want_anglemap else None, used.data_ptr(),
-                                         None if ws is None else ws.data_ptr(), n, runtime.stream_ptr()))
+    ws = runtime.workspace(dev, "vstab_flow_to_image_workspace_bytes", B, H, W) if maxrad is None else None
+    runtime.call(dev, "vstab_flow_to_image", flow.data_ptr(), B, H, W, runtime.ptr(maxrad), img.data_ptr(), runtime.ptr(ang), used.data_ptr(),
+                 runtime.ptr(ws), 0 if ws is None else ws.numel())
     return img, ang, used
 
 

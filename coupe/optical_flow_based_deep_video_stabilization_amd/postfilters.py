@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, runtime
+from . import runtime
 
 
 def _flow(t, name="flow"):
@@ -22,9 +22,7 @@ def box_blur_flow(flow, k: int = 75):
     f = _flow(flow)
     B, h, w, _ = f.shape
     tmp, out = torch.empty_like(f), torch.empty_like(f)
-    with torch.cuda.device(f.device):
-        _lib.check(_lib.lib().vstab_flow_box_blur(f.data_ptr(), B, h, w, int(k), tmp.data_ptr(), out.data_ptr(),
-                                                  runtime.stream_ptr()))
+    runtime.call(f.device, "vstab_flow_box_blur", f.data_ptr(), B, h, w, int(k), tmp.data_ptr(), out.data_ptr())
     return out
 
 
@@ -34,9 +32,7 @@ def axpby(a: float, x, b: float, y):
     if x.shape != y.shape or x.dtype != torch.float32 or not x.is_cuda or not y.is_cuda:
         raise ValueError("x and y must be equally shaped float32 CUDA tensors")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().vstab_axpby(x.data_ptr(), float(a), y.data_ptr(), float(b), out.data_ptr(), x.numel(),
-                                          runtime.stream_ptr()))
+    runtime.call(x.device, "vstab_axpby", x.data_ptr(), float(a), y.data_ptr(), float(b), out.data_ptr(), x.numel())
     return out
 
 
@@ -51,9 +47,7 @@ def medfilt_flow(flow, kernel_size=5):
     if len(ks) != 3:
         raise ValueError("kernel_size must be a scalar or (kh, kw, kc)")
     out = torch.empty_like(f)
-    with torch.cuda.device(f.device):
-        _lib.check(_lib.lib().vstab_flow_medfilt(f.data_ptr(), B, h, w, ks[0], ks[1], ks[2], out.data_ptr(),
-                                                 runtime.stream_ptr()))
+    runtime.call(f.device, "vstab_flow_medfilt", f.data_ptr(), B, h, w, ks[0], ks[1], ks[2], out.data_ptr())
     return out
 
 
@@ -62,8 +56,7 @@ def mean_flow(flow):
     f = _flow(flow)
     B, h, w, _ = f.shape
     out = torch.empty_like(f)
-    with torch.cuda.device(f.device):
-        _lib.check(_lib.lib().vstab_flow_mean_fill(f.data_ptr(), B, h, w, out.data_ptr(), runtime.stream_ptr()))
+    runtime.call(f.device, "vstab_flow_mean_fill", f.data_ptr(), B, h, w, out.data_ptr())
     return out
 
 
@@ -74,16 +67,11 @@ def find_homography(flow, K: int = 256, seed: int = 0, thresh: float = 3.0, refi
     4-point hypotheses, 3 px consensus (cv2's default threshold), `refine` least-squares refits on the inliers."""
     f = _flow(flow)
     B, h, w, _ = f.shape
-    L = _lib.lib()
-    n = L.vstab_homography_workspace_bytes(B, h, w, int(K))
-    if n == 0:
-        raise ValueError("find_homography: need 1 <= K <= 512")
-    ws = torch.empty(n, dtype=torch.uint8, device=f.device)
+    ws = runtime.workspace(f.device, "vstab_homography_workspace_bytes", B, h, w, int(K), refused="find_homography: need 1 <= K <= 512")
     Hm = torch.empty((B, 3, 3), dtype=torch.float64, device=f.device)
     inl = torch.empty((B,), dtype=torch.int32, device=f.device)
-    with torch.cuda.device(f.device):
-        _lib.check(L.vstab_homography_fit(f.data_ptr(), B, h, w, int(K), int(seed) & 0xffffffff, float(thresh), int(refine),
-                                          int(stride), Hm.data_ptr(), inl.data_ptr(), ws.data_ptr(), n, runtime.stream_ptr()))
+    runtime.call(f.device, "vstab_homography_fit", f.data_ptr(), B, h, w, int(K), int(seed) & 0xffffffff, float(thresh), int(refine),
+                 int(stride), Hm.data_ptr(), inl.data_ptr(), ws.data_ptr(), ws.numel())
     return Hm, inl
 
 
@@ -98,9 +86,7 @@ def warp_perspective_u8(frames, Hm, size_hw=None):
         raise ValueError("Hm must be a float64 tensor [B,3,3] on the frames' device")
     oh, ow = (sh, sw) if size_hw is None else (int(size_hw[0]), int(size_hw[1]))
     dst = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.lib().vstab_warp_perspective_u8(src.data_ptr(), B, sh, sw, Hm.contiguous().data_ptr(), dst.data_ptr(),
-                                                        oh, ow, runtime.stream_ptr()))
+    runtime.call(src.device, "vstab_warp_perspective_u8", src.data_ptr(), B, sh, sw, Hm.contiguous().data_ptr(), dst.data_ptr(), oh, ow)
     return dst
 
 

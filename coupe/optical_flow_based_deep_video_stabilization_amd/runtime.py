@@ -20,6 +20,42 @@ def stream_ptr() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def call(device, name, *args, ctx=None):
+    """The library's entry point `name`(*args, stream) on `device`'s current stream; an error code raises (_lib.check, with `ctx`'s
+    message when the entry point takes a context).  Entry points without a trailing stream (vstab_host_*, the *_workspace_bytes
+    queries) are called on _lib.lib() directly."""
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), name)(*args, stream_ptr()), ctx)
+
+
+def f32_cuda(t, name, rank=None, last=None, layout=""):
+    """t, contiguous, when it is a float32 CUDA tensor of `rank` dimensions whose last one has `last` elements (None: any);
+    otherwise ValueError("<name> must be a float32 CUDA tensor <layout>")."""
+    if (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or (rank is not None and t.dim() != rank)
+            or (last is not None and t.shape[-1] != last)):
+        raise ValueError(f"{name} must be a float32 CUDA tensor {layout}".rstrip())
+    return t.contiguous()
+
+
+def workspace(device, query, *args, refused=None) -> torch.Tensor:
+    """uint8 device memory of the size the library's `query`(*args) asks for, never an empty allocation; pass its numel() as the
+    byte count.  A query answers 0 for a shape its entry point refuses: that raises ValueError(refused) where a message is given."""
+    n = int(getattr(_lib.lib(), query)(*args))
+    if n == 0 and refused is not None:
+        raise ValueError(refused)
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
+
+
+def ptr(t):
+    """The address of an optional tensor (None -> NULL)."""
+    return t.data_ptr() if t is not None else None
+
+
+def _up4(n: int) -> int:
+    """n rounded up to the NHWC buffers' channel granule of 4 floats"""
+    return (n + 3) // 4 * 4
+
+
 def trace_ranges(on: bool):
     """roctx ranges per layer (rocprofv3 --marker-trace); raises if no roctx library is installed."""
     _lib.check(_lib.lib().vstab_trace_ranges(int(bool(on))))
@@ -118,9 +154,7 @@ class Context:
         if self.cin is None:
             raise RuntimeError("vstab: weights have not been loaded (initialize_global_variables / "
                                "load_and_assign_npz_dict)")
-        if feats.dim() != 4 or feats.dtype != torch.float32 or not feats.is_cuda:
-            raise ValueError("feats must be a float32 CUDA tensor [B,H,W,C]")
-        feats = feats.contiguous()
+        feats = f32_cuda(feats, "feats", 4, layout="[B,H,W,C]")
         B, H, W, Cin = feats.shape
         sz = netspec.sizes_for(H, W)
         ws = self.workspace(B, H, W, Cin)
@@ -128,10 +162,8 @@ class Context:
         dev = feats.device
         flows = [torch.empty((B, lv[k][0], lv[k][1], 2), dtype=torch.float32, device=dev) for k in (6, 5, 4, 3)]
         flows.append(torch.empty((B, H - 2, W - 2, 2), dtype=torch.float32, device=dev))
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().vstab_flownets_forward(
-                self._h, feats.data_ptr(), B, H, W, Cin, *[f.data_ptr() for f in flows],
-                ws.data_ptr(), ws.numel(), stream_ptr()), self._h)
+        call(dev, "vstab_flownets_forward", self._h, feats.data_ptr(), B, H, W, Cin, *[f.data_ptr() for f in flows], ws.data_ptr(), ws.numel(),
+             ctx=self._h)
         return flows
 
     LAUNCH_SLOTS = ("conv1", "conv2", "conv3", "conv3_1", "conv4", "conv4_1", "conv5", "conv5_1", "conv6", "conv6_1",

@@ -22,20 +22,13 @@ the keyword changes nothing.  NOT differentiable: `ElasticTransformer.transform_
 The homography samplers of the reference's `warp.py` (`warp.transformImage` and its kin) are differentiable too: see `warp.py`."""
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
-from . import _autograd, _lib, runtime
+from . import _autograd, _lib, runtime, training          # the backward wrappers under their public names (sampler_grad's, re-exported)
+from .runtime import f32_cuda as _f32_cuda
 
 _INTERP = _lib.INTERP
-
-
-def _f32_cuda(t, name):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be a float32 CUDA tensor")
-    return t.contiguous()
 
 
 def _meshgrid(out_size, device=None):
@@ -44,8 +37,7 @@ def _meshgrid(out_size, device=None):
     oh, ow = int(out_size[0]), int(out_size[1])
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     out = torch.empty(3 * oh * ow, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().vstab_st_meshgrid(out.data_ptr(), oh, ow, runtime.stream_ptr()))
+    runtime.call(dev, "vstab_st_meshgrid", out.data_ptr(), oh, ow)
     return out
 
 
@@ -61,14 +53,11 @@ def _flat(d_theta):
 def _bilinear_interp_call(im, x, y, oh, ow):
     B, H, W, Cc = im.shape
     out = torch.empty((B * oh * ow, Cc), dtype=torch.float32, device=im.device)
-    with torch.cuda.device(im.device):
-        _lib.check(_lib.lib().vstab_st_bilinear_interp(im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow,
-                                                       out.data_ptr(), runtime.stream_ptr()))
+    runtime.call(im.device, "vstab_st_bilinear_interp", im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow, out.data_ptr())
     return out
 
 
 def _bilinear_interp_backward(saved, dout, needs, out_size):
-    from . import training
     return training.st_bilinear_interp_backward(*saved, dout, out_size, need_img=needs[0], need_x=needs[1], need_y=needs[2])
 
 
@@ -90,14 +79,11 @@ def bilinear_interp(im, x, y, out_size):
 def _bicubic_interp_call(im, x, y, oh, ow):
     B, H, W, Cc = im.shape
     out = torch.empty((B * oh * ow, Cc), dtype=torch.float32, device=im.device)
-    with torch.cuda.device(im.device):
-        _lib.check(_lib.lib().vstab_st_bicubic_interp(im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow,
-                                                      out.data_ptr(), runtime.stream_ptr()))
+    runtime.call(im.device, "vstab_st_bicubic_interp", im.data_ptr(), B, H, W, Cc, x.data_ptr(), y.data_ptr(), oh, ow, out.data_ptr())
     return out
 
 
 def _bicubic_interp_backward(saved, dout, needs, out_size):
-    from . import training
     return training.st_bicubic_interp_backward(*saved, dout, out_size, need_img=needs[0], need_x=needs[1], need_y=needs[2])
 
 
@@ -134,18 +120,15 @@ def _interp_code(method):
 def _theta_transform_call(inp, theta, param_dim, oh, ow, interp):
     B, H, W, Cc = inp.shape
     out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
-    with torch.cuda.device(inp.device):
-        if interp == 0:
-            _lib.check(_lib.lib().vstab_st_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), param_dim,
-                                                     out.data_ptr(), oh, ow, runtime.stream_ptr()))
-        else:
-            _lib.check(_lib.lib().vstab_st_transform_interp(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), param_dim,
-                                                            interp, out.data_ptr(), oh, ow, runtime.stream_ptr()))
+    if interp == 0:
+        runtime.call(inp.device, "vstab_st_transform", inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), param_dim, out.data_ptr(), oh, ow)
+    else:
+        runtime.call(inp.device, "vstab_st_transform_interp", inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), param_dim, interp, out.data_ptr(),
+                     oh, ow)
     return out
 
 
 def _theta_transform_backward(saved, dout, needs, statics):
-    from . import training
     _, oh, ow, interp = statics
     d_inp, d_theta = training.st_transform_backward(*saved, dout, (oh, ow), need_img=needs[0], need_theta=needs[1],
                                                     interp=_lib.INTERP_NAMES[interp])
@@ -201,14 +184,11 @@ class ProjectiveTransformer(_ThetaTransformer):
 def _symmetry_transform_call(inp, theta, kind, oh, ow, interp):
     B, H, W, Cc = inp.shape
     out = torch.empty((B, ow, oh, Cc), dtype=torch.float32, device=inp.device)
-    with torch.cuda.device(inp.device):
-        _lib.check(_lib.lib().vstab_st_symmetry_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), kind, interp,
-                                                          out.data_ptr(), oh, ow, runtime.stream_ptr()))
+    runtime.call(inp.device, "vstab_st_symmetry_transform", inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), kind, interp, out.data_ptr(), oh, ow)
     return out
 
 
 def _symmetry_transform_backward(saved, dout, needs, statics):
-    from . import training
     kind, oh, ow, interp = statics
     d_inp, d_theta = training.st_symmetry_transform_backward(*saved, dout, (oh, ow), kind, need_img=needs[0], need_theta=needs[1],
                                                              interp=_lib.INTERP_NAMES[interp])
@@ -254,8 +234,7 @@ class _SymmetryTransformer(object):
         theta = self._theta(theta.detach())
         B = theta.numel() // self.param_dim
         out = torch.empty((B, 3, 3), dtype=torch.float32, device=theta.device)
-        with torch.cuda.device(theta.device):
-            _lib.check(_lib.lib().vstab_st_symmetry_matrix(theta.data_ptr(), B, self.kind, out.data_ptr(), runtime.stream_ptr()))
+        runtime.call(theta.device, "vstab_st_symmetry_matrix", theta.data_ptr(), B, self.kind, out.data_ptr())
         return out
 
     def transform_coords(self, theta):
@@ -267,9 +246,7 @@ class _SymmetryTransformer(object):
         oh, ow = self.out_size
         x_s = torch.empty(B * oh * ow, dtype=torch.float32, device=theta.device)
         y_s = torch.empty_like(x_s)
-        with torch.cuda.device(theta.device):
-            _lib.check(_lib.lib().vstab_st_symmetry_coords(theta.data_ptr(), B, self.kind, oh, ow, x_s.data_ptr(), y_s.data_ptr(),
-                                                           runtime.stream_ptr()))
+        runtime.call(theta.device, "vstab_st_symmetry_coords", theta.data_ptr(), B, self.kind, oh, ow, x_s.data_ptr(), y_s.data_ptr())
         return x_s, y_s
 
 
@@ -318,21 +295,19 @@ def _tps_linv(g):
     and rounded to fp32."""
     K = g * g
     buf = np.empty((K, K + 3), dtype=np.float32)
-    _lib.check(_lib.lib().vstab_host_tps_linv(int(g), buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), buf.size))
+    _lib.check(_lib.lib().vstab_host_tps_linv(int(g), buf.ctypes.data, buf.size))
     return buf
 
 
 def _elastic_transform_call(inp, theta, linv_t, g, oh, ow, interp):
     B, H, W, Cc = inp.shape
     out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=inp.device)
-    with torch.cuda.device(inp.device):
-        _lib.check(_lib.lib().vstab_st_elastic_transform(inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), g, linv_t.data_ptr(), interp,
-                                                         out.data_ptr(), oh, ow, runtime.stream_ptr()))
+    runtime.call(inp.device, "vstab_st_elastic_transform", inp.data_ptr(), B, H, W, Cc, theta.data_ptr(), g, linv_t.data_ptr(), interp,
+                 out.data_ptr(), oh, ow)
     return out
 
 
 def _elastic_transform_backward(saved, dout, needs, statics):
-    from . import training
     inp, theta, linv_t = saved
     g, oh, ow, interp = statics
     d_inp, d_theta = training.st_elastic_transform_backward(inp, theta, dout, (oh, ow), g, linv_t, need_img=needs[0], need_theta=needs[1],
@@ -392,9 +367,8 @@ class ElasticTransformer(object):
         oh, ow = self.out_size
         x_s = torch.empty(B * oh * ow, dtype=torch.float32, device=theta.device)
         y_s = torch.empty_like(x_s)
-        with torch.cuda.device(theta.device):
-            _lib.check(_lib.lib().vstab_st_elastic_coords(theta.data_ptr(), B, self.grid_size, self.L_inv.data_ptr(), oh, ow,
-                                                          x_s.data_ptr(), y_s.data_ptr(), runtime.stream_ptr()))
+        runtime.call(theta.device, "vstab_st_elastic_coords", theta.data_ptr(), B, self.grid_size, self.L_inv.data_ptr(), oh, ow,
+                     x_s.data_ptr(), y_s.data_ptr())
         return x_s, y_s
 
 
@@ -418,8 +392,7 @@ def _meshgrid3d(out_size, device=None):
     od, oh, ow = _out_size3(out_size)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     out = torch.empty(4 * od * oh * ow, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().vstab_st3d_meshgrid(out.data_ptr(), od, oh, ow, runtime.stream_ptr()))
+    runtime.call(dev, "vstab_st3d_meshgrid", out.data_ptr(), od, oh, ow)
     return out
 
 
@@ -427,14 +400,12 @@ def _bilinear_interp3d_call(vol, x, y, z, out_size, edge_size):
     B, D, H, W, Cc = vol.shape
     od, oh, ow = out_size
     out = torch.empty((B * od * oh * ow, Cc), dtype=torch.float32, device=vol.device)
-    with torch.cuda.device(vol.device):
-        _lib.check(_lib.lib().vstab_st3d_bilinear_interp(vol.data_ptr(), B, D, H, W, Cc, x.data_ptr(), y.data_ptr(), z.data_ptr(), od, oh, ow,
-                                                         edge_size, out.data_ptr(), runtime.stream_ptr()))
+    runtime.call(vol.device, "vstab_st3d_bilinear_interp", vol.data_ptr(), B, D, H, W, Cc, x.data_ptr(), y.data_ptr(), z.data_ptr(), od, oh, ow,
+                 edge_size, out.data_ptr())
     return out
 
 
 def _bilinear_interp3d_backward(saved, dout, needs, statics):
-    from . import training
     out_size, edge_size = statics
     return training.st3d_bilinear_interp_backward(*saved, dout, out_size, edge_size=edge_size, need_vol=needs[0], need_x=needs[1],
                                                   need_y=needs[2], need_z=needs[3])
@@ -465,14 +436,11 @@ def _volume_transform_call(inp, theta, out_size):
     B, D, H, W, Cc = inp.shape
     od, oh, ow = out_size
     out = torch.empty((B, od, oh, ow, Cc), dtype=torch.float32, device=inp.device)
-    with torch.cuda.device(inp.device):
-        _lib.check(_lib.lib().vstab_st3d_transform(inp.data_ptr(), B, D, H, W, Cc, theta.data_ptr(), out.data_ptr(), od, oh, ow,
-                                                   runtime.stream_ptr()))
+    runtime.call(inp.device, "vstab_st3d_transform", inp.data_ptr(), B, D, H, W, Cc, theta.data_ptr(), out.data_ptr(), od, oh, ow)
     return out
 
 
 def _volume_transform_backward(saved, dout, needs, statics):
-    from . import training
     (out_size,) = statics
     d_inp, d_theta = training.st3d_transform_backward(*saved, dout, out_size, need_vol=needs[0], need_theta=needs[1])
     return d_inp, _flat(d_theta)

@@ -23,8 +23,9 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib, runtime
+from . import runtime
 from ._autograd import wants_grad as _wants_grad
+from .runtime import ptr as _ptr
 
 _MAX_SIZE = 11
 
@@ -42,11 +43,10 @@ def _tf_fspecial_gauss(size, sigma):
 
 
 def _image(t, name):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
-        raise ValueError(f"{name} must be a float32 CUDA tensor [B,H,W,1]")
+    t = runtime.f32_cuda(t, name, 4, layout="[B,H,W,1]")
     if t.shape[3] != 1:
         raise ValueError(f"{name} has {t.shape[3]} channels: the reference's [k,k,1,1] window takes one channel only")
-    return t.contiguous()
+    return t
 
 
 def _pair(img1, img2, size, sigma):
@@ -65,22 +65,44 @@ def _pair(img1, img2, size, sigma):
 
 def _ssim_call(a, b, size, sigma, want_map, want_means):
     B, H, W, _ = a.shape
-    L = _lib.lib()
     smap = torch.empty((B, H - size + 1, W - size + 1, 1), dtype=torch.float32, device=a.device) if want_map else None
-    means, ws, n = None, None, 0
+    means, ws = None, None
     if want_means:
         means = torch.empty((B,), dtype=torch.float32, device=a.device)
-        n = int(L.vstab_ssim_forward_workspace_bytes(B, H, W, size))
-        ws = torch.empty(max(n, 4), dtype=torch.uint8, device=a.device)
-    with torch.cuda.device(a.device):
-        _lib.check(L.vstab_ssim_forward(a.data_ptr(), b.data_ptr(), B, H, W, size, sigma, smap.data_ptr() if want_map else None,
-                                        means.data_ptr() if want_means else None, ws.data_ptr() if want_means else None, n,
-                                        runtime.stream_ptr()))
+        ws = runtime.workspace(a.device, "vstab_ssim_forward_workspace_bytes", B, H, W, size)
+    runtime.call(a.device, "vstab_ssim_forward", a.data_ptr(), b.data_ptr(), B, H, W, size, sigma, _ptr(smap), _ptr(means), _ptr(ws),
+                 ws.numel() if want_means else 0)
     return smap, means
 
 
+def ssim_backward(img1, img2, dout, size: int = 9, sigma: float = 0.5, need_img1: bool = True, need_img2: bool = True):
+    """Gradients of tf_ssim's value s (utils.py:111; l**0 and c**0 are constants) with respect to both images [B,H,W,1]: (d img1
+    or None, d img2 or None).  dout is the gradient of the map, [B,H-size+1,W-size+1,1], or -- one dimension, [B] -- that of the
+    per-sample means, broadcast over the sample's map inside the kernel.  need_img1 / need_img2 False skips that image.  Gathered
+    through the flipped window without atomics: bit-reproducible, and what the autograd functions below call."""
+    a, b = (runtime.f32_cuda(t, name, 4, 1, "[B,H,W,1]") for t, name in ((img1, "img1"), (img2, "img2")))
+    if img1.shape != img2.shape or img1.device != img2.device:
+        raise ValueError("img1 and img2 must have the same shape and device")
+    if not need_img1 and not need_img2:
+        return None, None
+    size = int(size)
+    B, H, W, _ = a.shape
+    ws = runtime.workspace(a.device, "vstab_ssim_backward_workspace_bytes", B, H, W, size, refused=(
+        f"ssim_backward: need B >= 1, 1 <= size <= 11 and images of at least size x size, got {B}x{H}x{W}, size {size}"))
+    per_sample = torch.is_tensor(dout) and dout.dim() == 1
+    want = B if per_sample else B * (H - size + 1) * (W - size + 1)
+    if not torch.is_tensor(dout) or dout.device != a.device or dout.dtype != torch.float32 or dout.numel() != want:
+        raise ValueError(f"dout must be a float32 tensor of {want} elements beside the images")
+    dout = dout.contiguous()
+    d1 = torch.empty_like(a) if need_img1 else None
+    d2 = torch.empty_like(a) if need_img2 else None
+    runtime.call(a.device, "vstab_ssim_backward", a.data_ptr(), b.data_ptr(), B, H, W, size, float(sigma), None if per_sample else dout.data_ptr(),
+                 dout.data_ptr() if per_sample else None, _ptr(d1), _ptr(d2), ws.data_ptr(), ws.numel())
+    return d1, d2
+
+
 class _SsimMapFn(torch.autograd.Function):
-    """s map [B,oh,ow,1] with its HIP backward (training.ssim_backward)."""
+    """s map [B,oh,ow,1] with its HIP backward (ssim_backward)."""
 
     @staticmethod
     def forward(ctx, a, b, size, sigma):
@@ -91,10 +113,9 @@ class _SsimMapFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        from . import training
         a, b = ctx.saved_tensors
         need = ctx.needs_input_grad
-        d1, d2 = training.ssim_backward(a, b, dout, ctx.size, ctx.sigma, need_img1=need[0], need_img2=need[1])
+        d1, d2 = ssim_backward(a, b, dout, ctx.size, ctx.sigma, need_img1=need[0], need_img2=need[1])
         return d1, d2, None, None
 
 
@@ -111,10 +132,9 @@ class _SsimMeansFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dmeans):
-        from . import training
         a, b = ctx.saved_tensors
         need = ctx.needs_input_grad
-        d1, d2 = training.ssim_backward(a, b, dmeans.reshape(-1), ctx.size, ctx.sigma, need_img1=need[0], need_img2=need[1])
+        d1, d2 = ssim_backward(a, b, dmeans.reshape(-1), ctx.size, ctx.sigma, need_img1=need[0], need_img2=need[1])
         return d1, d2, None, None
 
 
@@ -133,8 +153,7 @@ def _ssim_means(a, b, size, sigma):
 def _avg_pool_call(x):
     B, H, W, C = x.shape
     out = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().vstab_avgpool2x2_same(x.data_ptr(), B, H, W, C, out.data_ptr(), runtime.stream_ptr()))
+    runtime.call(x.device, "vstab_avgpool2x2_same", x.data_ptr(), B, H, W, C, out.data_ptr())
     return out
 
 
@@ -150,17 +169,14 @@ class _AvgPoolFn(torch.autograd.Function):
         B, H, W, C = ctx.in_shape
         dout = dout.contiguous()
         dx = torch.empty(ctx.in_shape, dtype=torch.float32, device=dout.device)
-        with torch.cuda.device(dout.device):
-            _lib.check(_lib.lib().vstab_avgpool2x2_same_backward(dout.data_ptr(), B, H, W, C, dx.data_ptr(), runtime.stream_ptr()))
+        runtime.call(dout.device, "vstab_avgpool2x2_same_backward", dout.data_ptr(), B, H, W, C, dx.data_ptr())
         return dx
 
 
 def avg_pool_2x2_same(x):
     """tf.nn.avg_pool(x, [1,2,2,1], [1,2,2,1], padding='SAME') on a float32 CUDA tensor [B,H,W,C] (utils.py:146-147): the output is
     [B,ceil(H/2),ceil(W/2),C] and a window that hangs over the edge averages the pixels that exist.  Differentiable."""
-    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
-        raise ValueError("x must be a float32 CUDA tensor [B,H,W,C]")
-    x = x.contiguous()
+    x = runtime.f32_cuda(x, "x", 4, layout="[B,H,W,C]")
     return _AvgPoolFn.apply(x) if _wants_grad(x) else _avg_pool_call(x)
 
 

@@ -38,9 +38,7 @@ def preprocess(x: torch.Tensor) -> torch.Tensor:
     x = x.contiguous()
     out = torch.empty_like(x)
     mean = (C.c_float * 4)(*VGG_MEAN, 0.0)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().vstab_scale_shift(x.data_ptr(), x.numel() // 3, 3, 255.0, mean, out.data_ptr(),
-                                                runtime.stream_ptr()))
+    runtime.call(x.device, "vstab_scale_shift", x.data_ptr(), x.numel() // 3, 3, 255.0, mean, out.data_ptr())
     return out
 
 
@@ -113,9 +111,7 @@ class Vgg16:
         else:
             outs, ws, nws = cached
         ptrs = (C.c_void_p * 18)(*[o.data_ptr() for o in outs])
-        with torch.cuda.device(x.device):
-            _lib.check(L.vstab_vgg16_forward(ctx._h, x.data_ptr(), B, H, W, ptrs, ws.data_ptr(), nws, runtime.stream_ptr()),
-                       ctx._h)
+        runtime.call(x.device, "vstab_vgg16_forward", ctx._h, x.data_ptr(), B, H, W, ptrs, ws.data_ptr(), nws, ctx=ctx._h)
         for name, t in zip(OUTPUTS, outs):
             setattr(self, name, t)
         return self

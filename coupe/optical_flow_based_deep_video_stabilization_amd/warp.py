@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _autograd, _lib, runtime
+from . import _autograd, runtime, sampler_grad
 
 
 def fit(Xsrc, Xdst):
@@ -51,15 +51,13 @@ def _f32_cuda(t, name):
 def _vec2mtrx_call(p, warp_type, dim, approx):
     B = p.shape[0]
     out = torch.empty((B, 3, 3), dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        _lib.check(_lib.lib().vstab_vec2mtrx(p.data_ptr(), B, dim, approx, out.data_ptr(), runtime.stream_ptr()))
+    runtime.call(p.device, "vstab_vec2mtrx", p.data_ptr(), B, dim, approx, out.data_ptr())
     return out
 
 
 def _vec2mtrx_backward(saved, d_out, needs, statics):
-    from . import training
     warp_type, _, approx = statics
-    return (training.vec2mtrx_backward(saved[0], d_out, warp_type, approx),)
+    return (sampler_grad.vec2mtrx_backward(saved[0], d_out, warp_type, approx),)
 
 
 def vec2mtrx(config, p):
@@ -82,22 +80,18 @@ def _warp_call(image, mat, ref, oh, ow):
     reference) is composed inside the warp launch -- every product and sum rounded to fp32 -- not by a library GEMM in front of it."""
     B, Hi, Wi, Cc = image.shape
     out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=image.device)
-    with torch.cuda.device(image.device):
-        if ref is None:
-            _lib.check(_lib.lib().vstab_homography_warp(image.data_ptr(), B, Hi, Wi, Cc, mat.data_ptr(), out.data_ptr(),
-                                                        oh, ow, runtime.stream_ptr()))
-        else:
-            _lib.check(_lib.lib().vstab_transform_image(image.data_ptr(), B, Hi, Wi, Cc, ref.data_ptr(), mat.data_ptr(), out.data_ptr(),
-                                                        oh, ow, runtime.stream_ptr()))
+    if ref is None:
+        runtime.call(image.device, "vstab_homography_warp", image.data_ptr(), B, Hi, Wi, Cc, mat.data_ptr(), out.data_ptr(), oh, ow)
+    else:
+        runtime.call(image.device, "vstab_transform_image", image.data_ptr(), B, Hi, Wi, Cc, ref.data_ptr(), mat.data_ptr(), out.data_ptr(), oh, ow)
     return out
 
 
 def _warp_backward(saved, dout, needs, statics):
     """d image and d M, or with ref d pMtrx."""
-    from . import training
     image, mat = saved
     ref, oh, ow = statics
-    d_img, d_mat = training.homography_warp_backward(image, mat, dout, (oh, ow), need_img=needs[0], need_M=needs[1], ref=ref)
+    d_img, d_mat = sampler_grad.homography_warp_backward(image, mat, dout, (oh, ow), need_img=needs[0], need_M=needs[1], ref=ref)
     return d_img, (d_mat.reshape(mat.shape) if d_mat is not None else None)
 
 

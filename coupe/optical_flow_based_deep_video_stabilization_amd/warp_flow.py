@@ -3,7 +3,7 @@
 `evaluate_originalSize` (main:497-498) and `evaluate` (main:806).
 ("main" = main_flownetS_pyramid_noprevloss_dataloader.py.)  HIP kernels only.
 
-Differentiable (torch.autograd, HIP backward kernels behind `training.*_backward`): `tf_warp` with respect to the image and the flow,
+Differentiable (torch.autograd, HIP backward kernels behind `sampler_grad.*_backward`): `tf_warp` with respect to the image and the flow,
 `get_pixel_value` with respect to the image, `resize_images` / `resize_images_slice3` with respect to their input,
 `flow_to_output_res` with respect to predict_flow2, `flow_glue_warp` with respect to predict_flow2 and the frame.  The gradients are
 what TensorFlow's autodiff yields: tf_warp's corner indices come from integer casts and carry no gradient, the flow enters through the
@@ -16,29 +16,21 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _autograd, _lib, runtime
+from . import _autograd, runtime, sampler_grad
 from ._autograd import wants_grad as _wants_grad
-
-
-def _f32_cuda(t, name):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be a float32 CUDA tensor")
-    return t.contiguous()
+from .runtime import f32_cuda as _f32_cuda
 
 
 def _tf_warp_call(img, flow):
     B, H, W, Cc = img.shape
     out = torch.empty_like(img)
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.lib().vstab_warp_flow(img.data_ptr(), flow.data_ptr(), out.data_ptr(), B, H, W, Cc,
-                                              runtime.stream_ptr()))
+    runtime.call(img.device, "vstab_warp_flow", img.data_ptr(), flow.data_ptr(), out.data_ptr(), B, H, W, Cc)
     return out
 
 
 def _tf_warp_backward(saved, dout, needs, statics):
     """d img and / or d flow, whichever is needed."""
-    from . import training
-    return training.warp_flow_backward(*saved, dout, need_img=needs[0], need_flow=needs[1])
+    return sampler_grad.warp_flow_backward(*saved, dout, need_img=needs[0], need_flow=needs[1])
 
 
 def tf_warp(img, flow, H, W):
@@ -55,14 +47,12 @@ def _get_pixel_value_call(img, x, y):
     B, Hi, Wi, Cc = img.shape
     _, H, W = x.shape
     out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=img.device)
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.lib().vstab_get_pixel_value(img.data_ptr(), x.data_ptr(), y.data_ptr(), out.data_ptr(),
-                                                    B, H, W, Cc, Hi, Wi, runtime.stream_ptr()))
+    runtime.call(img.device, "vstab_get_pixel_value", img.data_ptr(), x.data_ptr(), y.data_ptr(), out.data_ptr(), B, H, W, Cc, Hi, Wi)
     return out
 
 
 class _GetPixelValueFn(torch.autograd.Function):
-    """get_pixel_value with its HIP backward (training.get_pixel_value_backward): the scatter-add into d img."""
+    """get_pixel_value with its HIP backward (sampler_grad.get_pixel_value_backward): the scatter-add into d img."""
 
     @staticmethod
     def forward(ctx, img, x, y):
@@ -73,9 +63,8 @@ class _GetPixelValueFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        from . import training
         x, y = ctx.saved_tensors
-        return training.get_pixel_value_backward(dout, x, y, ctx.img_hw), None, None
+        return sampler_grad.get_pixel_value_backward(dout, x, y, ctx.img_hw), None, None
 
 
 def get_pixel_value(img, x, y):
@@ -93,14 +82,12 @@ def get_pixel_value(img, x, y):
 def _resize_call(x, oh, ow):
     B, h, w, Cc = x.shape
     out = torch.empty((B, oh, ow, Cc), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().vstab_resize_bilinear(x.data_ptr(), B, h, w, Cc, out.data_ptr(), oh, ow,
-                                                    runtime.stream_ptr()))
+    runtime.call(x.device, "vstab_resize_bilinear", x.data_ptr(), B, h, w, Cc, out.data_ptr(), oh, ow)
     return out
 
 
 class _ResizeFn(torch.autograd.Function):
-    """resize_images with the adjoint of the legacy bilinear resize (training.resize_bilinear_backward; atomic-free)."""
+    """resize_images with the adjoint of the legacy bilinear resize (sampler_grad.resize_bilinear_backward; atomic-free)."""
 
     @staticmethod
     def forward(ctx, x, oh, ow):
@@ -110,8 +97,7 @@ class _ResizeFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        from . import training
-        return training.resize_bilinear_backward(dout, ctx.in_hw), None, None
+        return sampler_grad.resize_bilinear_backward(dout, ctx.in_hw), None, None
 
 
 def resize_images(x, size):
@@ -126,14 +112,12 @@ def resize_images(x, size):
 def _resize_slice3_call(x, c_off, oh, ow):
     B, h, w, Cs = x.shape
     out = torch.empty((B, oh, ow, 3), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().vstab_resize_bilinear_slice3(x.data_ptr(), B, h, w, Cs, int(c_off), out.data_ptr(), oh, ow,
-                                                           runtime.stream_ptr()))
+    runtime.call(x.device, "vstab_resize_bilinear_slice3", x.data_ptr(), B, h, w, Cs, int(c_off), out.data_ptr(), oh, ow)
     return out
 
 
 class _ResizeSlice3Fn(torch.autograd.Function):
-    """resize_images_slice3: the three channels' adjoint by training.resize_bilinear_backward, placed into a zero tensor of x's shape."""
+    """resize_images_slice3: the three channels' adjoint by sampler_grad.resize_bilinear_backward, placed into a zero tensor of x's shape."""
 
     @staticmethod
     def forward(ctx, x, c_off, oh, ow):
@@ -143,9 +127,8 @@ class _ResizeSlice3Fn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        from . import training
         dx = torch.zeros(ctx.in_shape, dtype=torch.float32, device=dout.device)
-        dx[..., ctx.c_off:ctx.c_off + 3] = training.resize_bilinear_backward(dout, ctx.in_shape[1:3])
+        dx[..., ctx.c_off:ctx.c_off + 3] = sampler_grad.resize_bilinear_backward(dout, ctx.in_shape[1:3])
         return dx, None, None, None
 
 
@@ -166,14 +149,12 @@ def resize_images_slice3(x, c_off, size):
 def _flow_to_output_res_call(f, net_h, net_w, out_h, out_w):
     B, h, w, two = f.shape
     out = torch.empty((B, out_h, out_w, 2), dtype=torch.float32, device=f.device)
-    with torch.cuda.device(f.device):
-        _lib.check(_lib.lib().vstab_flow_resize_scale(f.data_ptr(), B, h, w, out.data_ptr(), out_h, out_w,
-                                                      int(net_h), int(net_w), runtime.stream_ptr()))
+    runtime.call(f.device, "vstab_flow_resize_scale", f.data_ptr(), B, h, w, out.data_ptr(), out_h, out_w, int(net_h), int(net_w))
     return out
 
 
 class _FlowToOutputResFn(torch.autograd.Function):
-    """flow_to_output_res with its adjoint (training.flow_resize_scale_backward; atomic-free)."""
+    """flow_to_output_res with its adjoint (sampler_grad.flow_resize_scale_backward; atomic-free)."""
 
     @staticmethod
     def forward(ctx, f, net_h, net_w, out_h, out_w):
@@ -183,8 +164,7 @@ class _FlowToOutputResFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        from . import training
-        return training.flow_resize_scale_backward(dout, ctx.in_hw, *ctx.net), None, None, None, None
+        return sampler_grad.flow_resize_scale_backward(dout, ctx.in_hw, *ctx.net), None, None, None, None
 
 
 def flow_to_output_res(predict_flow2, net_h, net_w, out_h, out_w):
@@ -206,10 +186,8 @@ def _flow_glue_warp_call(f, img, net_h, net_w, want_outflow):
     _, oh, ow, Cc = img.shape
     outflow = torch.empty((B, oh, ow, 2), dtype=torch.float32, device=f.device) if want_outflow else None
     out = torch.empty_like(img)
-    with torch.cuda.device(f.device):
-        _lib.check(_lib.lib().vstab_flow_glue_warp(f.data_ptr(), B, h, w, img.data_ptr(),
-                                                   outflow.data_ptr() if want_outflow else None, out.data_ptr(), oh, ow, Cc,
-                                                   int(net_h), int(net_w), runtime.stream_ptr()))
+    runtime.call(f.device, "vstab_flow_glue_warp", f.data_ptr(), B, h, w, img.data_ptr(), runtime.ptr(outflow), out.data_ptr(), oh, ow, Cc,
+                 int(net_h), int(net_w))
     return outflow, out
 
 
@@ -232,7 +210,6 @@ class _FlowGlueWarpFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        from . import training
         g_outflow, d_warped = grads if ctx.want_outflow else (None, grads[0])
         f, img = ctx.saved_tensors[:2]
         need_f, need_img = ctx.needs_input_grad[:2]
@@ -240,13 +217,13 @@ class _FlowGlueWarpFn(torch.autograd.Function):
         if d_warped is not None:
             oh, ow = img.shape[1:3]
             outflow = ctx.saved_tensors[2] if ctx.want_outflow else _flow_to_output_res_call(f, *ctx.net, oh, ow)
-            d_img, d_of = training.warp_flow_backward(img, outflow, d_warped, need_img=need_img, need_flow=need_f)
+            d_img, d_of = sampler_grad.warp_flow_backward(img, outflow, d_warped, need_img=need_img, need_flow=need_f)
         d_f = None
         if need_f:
             if g_outflow is not None:
                 d_of = g_outflow if d_of is None else d_of + g_outflow
             if d_of is not None:
-                d_f = training.flow_resize_scale_backward(d_of, f.shape[1:3], *ctx.net)
+                d_f = sampler_grad.flow_resize_scale_backward(d_of, f.shape[1:3], *ctx.net)
         return d_f, d_img, None, None, None
 
 
