@@ -3,7 +3,11 @@ non-local deep-feature saliency head at the reference's hard-wired 352x352 geome
 never instantiates this model and the file only runs under Python 2 (`k_s / 2` as a pad width,
 NLDF.py:132); it is provided because BASELINE.json's north_star names it.  Variable names follow the
 TF scopes: `<layer>/W`, `<layer>/b` for Fea_Global_1, Fea_Global_2, Fea_Global, Fea_P1..5,
-Fea_P2_Deconv..Fea_P5_Deconv, Local_Fea, Local_Score, Global_Score."""
+Fea_P2_Deconv..Fea_P5_Deconv, Local_Fea, Local_Score, Global_Score.
+
+The objective the reference's build_model spells out (NLDF.py:79-100: contour term, IoU loss, softmax cross-entropy, accuracy) is
+`Model.build_loss` and the module-level `saliency_loss`; `Model.sobel_filter`, `im_gradient`, `Loss_IoU`, `Loss_Contour` and `L2`
+(:136-171) are its pieces, each differentiable through a HIP backward (nldf_loss.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +16,8 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, runtime, vgg16
+from . import _lib, nldf_loss, runtime, vgg16
+from .nldf_loss import SaliencyLoss, saliency_loss  # noqa: F401  (the module-level entry of the fused loss)
 
 img_size = 352
 label_size = img_size // 2
@@ -117,6 +122,49 @@ class Model:
                                             self.Local_Fea.data_ptr(), self.Fea_Global.data_ptr(), ws.data_ptr(), nws,
                                             runtime.stream_ptr()), ctx._h)
         return self.Prob
+
+    # ---- the objective (NLDF.py:79-100, :136-171): nldf_loss.py over csrc/nldf_loss_ops.hip
+    def sobel_filter(self):
+        """NLDF.py:136-149: the depthwise Sobel filters (fx, fy), each [3,3,2,1] float32 (host tensors; the kernels hold the taps)."""
+        fx = torch.tensor([[-1., 0., 1.], [-2., 0., 2.], [-1., 0., 1.]], dtype=torch.float32)
+        fy = fx.t().contiguous()
+        return tuple(torch.stack((f, f), dim=2).reshape(3, 3, 2, 1) for f in (fx, fy))
+
+    def im_gradient(self, im):
+        """NLDF.py:151-156 on a float32 CUDA tensor [B,H,W,C], 1 <= C <= 4: per channel sqrt(gx^2 + gy^2) of the two 3x3 Sobel
+        correlations of the one-pixel SYMMETRIC pad (clamp to edge).  Differentiable; a pixel whose magnitude is exactly 0 passes no
+        gradient (TensorFlow: NaN)."""
+        return nldf_loss.im_gradient(im)
+
+    def Loss_IoU(self, pred, gt):
+        """NLDF.py:158-165: 1 - 2 (sum pred gt + 1) / (sum pred^2 + sum gt^2 + 1) over every element, a 0-dim tensor.  The reference's
+        `if inter == 0: return 0` compares a tensor object with an int, which is never true in TF 1.x: the else branch is the
+        function.  Differentiable with respect to pred; a gt that requires grad raises."""
+        return nldf_loss.loss_iou(pred, gt)
+
+    def Loss_Contour(self, pred, gt):
+        """NLDF.py:167-168: mean(-gt log(pred + 1e-5) - (1 - gt) log(1 - pred + 1e-5)).  Differentiable with respect to pred; a gt that
+        requires grad raises."""
+        return nldf_loss.loss_contour(pred, gt)
+
+    def L2(self, tensor, wd=0.0005):
+        """NLDF.py:170-171: wd * sum(tensor^2) / 2 (the product the reference's `tf.mul`, gone from TF 1.x, names).  Differentiable."""
+        return nldf_loss.l2(tensor, wd)
+
+    def build_loss(self, label_holder, contour_th=1.5):
+        """The loss graph of NLDF.py:79-100 on the Score of the last build_model and label_holder [B,176,176,2] (per pixel a distribution
+        over the two classes).  Sets label_holder, contour_th, Prob_Grad, label_Grad [B,176,176,1], C_IoU_LOSS, CE, Loss_Mean = C_IoU_LOSS +
+        CE, accuracy (0-dim) and Score_grad = d Loss_Mean / d Score [B,176,176,2], all from one fused call (Score has no autograd graph
+        behind it; back-propagation into the head and the trunk is not built).  Returns Loss_Mean."""
+        if getattr(self, "Score", None) is None:
+            raise RuntimeError("build_loss() needs a build_model() call first")
+        if not torch.is_tensor(label_holder) or tuple(label_holder.shape) != tuple(self.Score.shape):
+            raise ValueError(f"label_holder must be a float32 CUDA tensor {list(self.Score.shape)}")
+        scalars, pg, lg, dscore = nldf_loss.saliency_loss_call(self.Score, label_holder, contour_th, True, True)
+        self.label_holder, self.contour_th = label_holder, float(contour_th)
+        self.Prob_Grad, self.label_Grad, self.Score_grad = pg, lg, dscore
+        self.Loss_Mean, self.C_IoU_LOSS, self.CE, self.accuracy = scalars[0], scalars[1], scalars[2], scalars[3]
+        return self.Loss_Mean
 
     def internals(self):
         """Views (no copy, no launch) of the head's intermediate tensors in the workspace of the last build_model (tests):

@@ -566,6 +566,18 @@ hipError_t launch_ssim_backward(const float *img1, const float *img2, int B, int
 hipError_t launch_avgpool2x2_same(const float *x, int B, int H, int W, int C, float *out, hipStream_t stream);
 hipError_t launch_avgpool2x2_same_backward(const float *dout, int B, int H, int W, int C, float *dx, hipStream_t stream);
 
+// NLDF's objective (nldf_loss_ops.hip; NLDF.py:79-100, :136-171).  workspace of the fused loss: 2 + 5 * nldf_loss_tiles(B, H, W) doubles
+// (the batch sums I and U, then five partial sums per tile); of a reduction: 2 + 3 * nldf_reduce_blocks(n) doubles.
+constexpr int NLDF_REDUCE_IOU = 0, NLDF_REDUCE_CONTOUR = 1, NLDF_REDUCE_L2 = 2;
+size_t nldf_loss_tiles(int B, int H, int W);
+unsigned nldf_reduce_blocks(long long n);
+hipError_t launch_nldf_loss(const float *score, const float *label, int B, int H, int W, float contour_th, float *scalars, float *prob_grad,
+                            float *label_grad, float *dscore, float dscale, double *workspace, hipStream_t stream);
+hipError_t launch_sobel_magnitude(const float *x, int B, int H, int W, int C, float *out, hipStream_t stream);
+hipError_t launch_sobel_magnitude_backward(const float *x, const float *dout, int B, int H, int W, int C, float *dx, hipStream_t stream);
+hipError_t launch_nldf_reduce(int mode, const float *a, const float *b, long long n, float wd, float *value, float *grad, double *workspace,
+                              hipStream_t stream);
+
 // Middlebury colour code of a flow field (flow_vis_ops.hip; flow_to_image, main_flownetS_pyramid.py:824-957).  Without maxrad_in a
 // first launch leaves flow_vis_partials(H, W) floats per sample in partial (one workgroup per FLOW_VIS_SLICE pixels, at most
 // FLOW_VIS_MAX_PARTIALS); flow 8-byte aligned, B <= 65535, B*H*W < 2^31 (the entry point checks).

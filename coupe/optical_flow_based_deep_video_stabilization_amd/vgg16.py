@@ -12,7 +12,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, runtime
+from . import _lib, nldf_loss, runtime
 
 VGG_MEAN = [103.939, 116.779, 123.68]     # vgg16.py:7 (BGR order; NLDF.py:29 applies it to RGB as is)
 
@@ -115,3 +115,8 @@ class Vgg16:
         for name, t in zip(OUTPUTS, outs):
             setattr(self, name, t)
         return self
+
+    def L2(self, tensor, wd=0.001):
+        """vgg16.py:99-100: wd * sum(tensor^2) / 2 of a float32 CUDA tensor (the product the reference's `tf.mul`, gone from TF 1.x,
+        names), a 0-dim tensor.  Differentiable; summed in a fixed order (nldf_loss.py)."""
+        return nldf_loss.l2(tensor, wd)

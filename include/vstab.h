@@ -439,6 +439,37 @@ VSTAB_API int vstab_nldf_forward(vstab_ctx *ctx, const float *const *pools5, int
                                  float *local_fea, float *fea_global, void *workspace, size_t workspace_bytes,
                                  void *stream);
 
+/* ---- NLDF's objective (NLDF.py:79-100, :136-171; csrc/nldf_loss_ops.hip states the formulas) -------------------------------
+ * Shared refusals: VSTAB_E_STATE for a required pointer that is NULL, VSTAB_E_SHAPE unless every dimension is >= 1 and the tensor has
+ * fewer than 2^31 elements, VSTAB_E_ALIGN / VSTAB_E_NOMEM for a workspace that is not 8-byte aligned / too short.  A refused call
+ * launches nothing and writes nothing.  No float atomics: two calls give the same bits. */
+/* im_gradient (NLDF.py:151-156) per channel of x [B,H,W,C], 1 <= C <= 4: sqrt(gx^2 + gy^2) of the two 3x3 Sobel correlations of the
+ * one-pixel SYMMETRIC (= clamp-to-edge) pad.  out [B,H,W,C]. */
+VSTAB_API int vstab_sobel_magnitude(const float *x, int B, int H, int W, int C, float *out, void *stream);
+/* dx [B,H,W,C] = the adjoint of that map at x applied to dout [B,H,W,C].  A pixel whose magnitude is exactly 0 passes no gradient
+ * (TensorFlow gives inf * 0 = NaN there). */
+VSTAB_API int vstab_sobel_magnitude_backward(const float *x, const float *dout, int B, int H, int W, int C, float *dx, void *stream);
+/* The fused loss on score, label [B,H,W,2] (8-byte aligned): Prob_Grad = tanh(sum_c im_gradient(softmax(score))_c), label_Grad =
+ * (sum_c im_gradient(label)_c > contour_th), C_IoU_LOSS = 1 - 2 (sum pg lg + 1) / (sum pg^2 + sum lg^2 + 1) over the whole batch,
+ * CE = mean over pixels of -sum_c label_c log_softmax(score)_c, accuracy = share of pixels whose argmax (ties to channel 0) agree.
+ * scalars4 (device, required) = {Loss_Mean = C_IoU_LOSS + CE, C_IoU_LOSS, CE, accuracy}; prob_grad, label_grad [B,H,W,1] and dscore
+ * [B,H,W,2] optional (NULL to skip); dscore = dscale * d Loss_Mean / d score (label_Grad carries no gradient; a channel whose Sobel
+ * magnitude is exactly 0 passes none).  Two launches, three with dscore, whatever B, H and W.  workspace:
+ * vstab_nldf_loss_workspace_bytes() bytes (0 for a refused shape), 8-byte aligned. */
+VSTAB_API size_t vstab_nldf_loss_workspace_bytes(int B, int H, int W);
+VSTAB_API int vstab_nldf_loss(const float *score, const float *label, int B, int H, int W, float contour_th, float *scalars4, float *prob_grad,
+                              float *label_grad, float *dscore, float dscale, void *workspace, size_t workspace_bytes, void *stream);
+/* The reductions behind Loss_IoU (mode 0: 1 - 2 (sum a b + 1) / (sum a^2 + sum b^2 + 1); NLDF.py:158-165, whose `inter == 0` branch is never
+ * taken), Loss_Contour (mode 1: mean(-b log(a + 1e-5) - (1 - b) log(1 - a + 1e-5)); :167-168) and L2 (mode 2: wd sum a^2 / 2; :170-171, b not
+ * read) over n elements: *value (device) and, when grad != NULL, grad [n] = d value / d a.  wd is read by mode 2 only.  Two launches, three
+ * with grad.  VSTAB_E_SHAPE also for another mode. */
+#define VSTAB_NLDF_REDUCE_IOU     0
+#define VSTAB_NLDF_REDUCE_CONTOUR 1
+#define VSTAB_NLDF_REDUCE_L2      2
+VSTAB_API size_t vstab_nldf_reduce_workspace_bytes(long long n);
+VSTAB_API int vstab_nldf_reduce(int mode, const float *a, const float *b, long long n, float wd, float *value, float *grad, void *workspace,
+                                size_t workspace_bytes, void *stream);
+
 /* ---- autoregressive clip driver pieces (per-frame loop of evaluate_originalSize, main:535-630) ----
  * All frames are uint8 [B,h,w,3] in cv2's BGR order, device memory. */
 /* cv2.resize(src, (dw, dh)), INTER_LINEAR, 8-bit (main:550,556-558): restated fixed-point algorithm, see clip_ops.hip. */
