@@ -1,96 +1,21 @@
 // VALU kernels of the flow pyramid and the warp: everything on the hot path that is not
 // a wide-output convolution.  All are HBM/latency-bound gathers and lerps (~1 FLOP/byte).
 // The 3-channel tile kernels (warp, fused glue + warp, the fused tails, glue, resize) stand on the skeleton of tile3.h; each
-// piece of the reference's arithmetic is one device function (tf_warp_taps / tf_warp_blend, glue_fetch / glue_interp, lerp2)
-// that the one-thread-per-pixel kernel and every tile kernel call.
+// piece of the reference's arithmetic is one function that every kernel needing it calls: the index maps legacy_coord / nearest_ac /
+// lerp2 (resample_coords.h; the host sizes the LDS windows with the same ones), tf_warp_taps / tf_warp_blend, glue_fetch / glue_interp,
+// predict_flow2's window and sums (tap_span, fill_tap_window, pf2_nine_taps, pf2_finish), the way a warped pixel leaves (warp3_emit).
 // Built with -ffp-contract=off so that the lerp / weight arithmetic is the same sequence
 // of fp32 roundings the reference's TF graph performs; dot products use explicit fmaf.
 #include "vstab_internal.h"
 #include "hbm_profile.h"
+#include "resample_coords.h"
 #include "tile3.h"
 #include "warp_taps.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 namespace vstab {
-
-// ---- records of the optional per-launch timing of the HBM-side kernels (hbm_profile.h has the launch wrapper)
-struct HbmProfState {
-    std::mutex mu;
-    bool on = false;
-    struct Rec { hipEvent_t a, b; };
-    std::vector<Rec> recs[HBM_SLOTS];
-    double bytes[HBM_SLOTS] = {0};
-};
-static HbmProfState &hbm_prof() { static HbmProfState s; return s; }
-
-void hbm_profile_enable(int mode)      // 0 = off (records kept), 1 = clear the records and switch on, 2 = switch on again, records kept
-{
-    HbmProfState &P = hbm_prof();
-    std::lock_guard<std::mutex> g(P.mu);
-    const bool on = mode != 0;
-    if (mode == 1)
-        for (int i = 0; i < HBM_SLOTS; ++i) {
-            for (auto &r : P.recs[i]) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-            P.recs[i].clear(); P.bytes[i] = 0;
-        }
-    P.on = on;
-}
-
-hipError_t hbm_profile_read(int slot, double *ms_sum, int *launches, double *alg_bytes_sum)
-{
-    HbmProfState &P = hbm_prof();
-    std::lock_guard<std::mutex> g(P.mu);
-    if (slot < 0 || slot >= HBM_SLOTS) return hipErrorInvalidValue;
-    double ms = 0;
-    for (auto &r : P.recs[slot]) {
-        float m = 0.f;
-        const hipError_t e = hipEventElapsedTime(&m, r.a, r.b);      // the stream must have been synchronised
-        if (e != hipSuccess) return e;
-        ms += m;
-    }
-    *ms_sum = ms; *launches = (int)P.recs[slot].size(); *alg_bytes_sum = P.bytes[slot];
-    return hipSuccess;
-}
-
-hipError_t hbm_profile_begin(int slot, double alg_bytes, hipEvent_t *a, hipEvent_t *b)
-{
-    HbmProfState &P = hbm_prof();
-    *a = *b = nullptr;
-    if (!P.on || slot < 0) return hipSuccess;        // slot < 0: a launch that is not timed
-    HbmProfState::Rec r;
-    hipError_t e = hipEventCreate(&r.a);
-    if (e != hipSuccess) return e;
-    e = hipEventCreate(&r.b);
-    if (e != hipSuccess) { (void)hipEventDestroy(r.a); return e; }
-    std::lock_guard<std::mutex> g(P.mu);
-    P.recs[slot].push_back(r); P.bytes[slot] += alg_bytes;
-    *a = r.a; *b = r.b;
-    return hipSuccess;
-}
-
-// ---- legacy TF bilinear (ResizeBilinear, align_corners=False, no half-pixel centres):
-// f = i * (in/out) in fp32, lo = floor(f), hi = min(lo+1, in-1), t = f - lo
-struct Lerp { int lo, hi; float t; };
-__device__ __forceinline__ Lerp legacy_coord(int o, float scale, int n_in)
-{
-    const float f = (float)o * scale;
-    const float fl = floorf(f);
-    Lerp L;
-    L.lo = min((int)fl, n_in - 1);
-    L.hi = min(L.lo + 1, n_in - 1);
-    L.t = f - fl;
-    return L;
-}
-__device__ __forceinline__ float lerp2(float tl, float tr, float bl, float br, float tx, float ty)
-{
-    const float top = tl + (tr - tl) * tx;
-    const float bot = bl + (br - bl) * tx;
-    return top + (bot - top) * ty;
-}
 
 __device__ __forceinline__ f32x2 sample_flow_legacy(const float *f, int n, int h, int w, int oy, int ox,
                                                     float sy, float sx)
@@ -305,9 +230,14 @@ hipError_t launch_predict_up(const float *src, int ks, long long slab_stride, in
 // kernel does the 9 gathers, then pf2 = pf2_raw + 8 sequential adds of up(pf3).
 // Index map: src = min((int)roundf(i * (in-1)/(out-1)), in-1) on the padded grid.
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ int nearest_ac(int i, float scale, int n_in)
+// predict_flow2 = the tap sum (a0, a1) + 8 sequential adds of up(pf3)
+__device__ __forceinline__ f32x2 pf2_finish(float a0, float a1, const float *pf3, int n, int h3, int w3, int y, int x, float usy, float usx)
 {
-    return min((int)roundf((float)i * scale), n_in - 1);
+    const f32x2 u = sample_flow_legacy(pf3, n, h3, w3, y, x, usy, usx);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { a0 += u.x; a1 += u.y; }
+    f32x2 o; o.x = a0; o.y = a1;
+    return o;
 }
 
 __global__ __launch_bounds__(256) void pf2_kernel(const float *__restrict__ T, int B, int h2, int w2,
@@ -341,11 +271,7 @@ __global__ __launch_bounds__(256) void pf2_kernel(const float *__restrict__ T, i
             a1 += t.y;
         }
     }
-    const f32x2 u = sample_flow_legacy(pf3, n, h3, w3, y, x, usy, usx);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { a0 += u.x; a1 += u.y; }
-    f32x2 o; o.x = a0; o.y = a1;
-    reinterpret_cast<f32x2 *>(pf2)[idx] = o;
+    reinterpret_cast<f32x2 *>(pf2)[idx] = pf2_finish(a0, a1, pf3, n, h3, w3, y, x, usy, usx);
 }
 
 // Tiled form: a workgroup owns a 16 x 64 tile of output pixels.  The nearest-neighbour map is monotone, so the source pixels the
@@ -354,6 +280,53 @@ __global__ __launch_bounds__(256) void pf2_kernel(const float *__restrict__ T, i
 // its nine taps as 8-byte LDS reads instead of nine 8-byte global gathers -- the direct kernel spent its time in the L1 tag pipe
 // (nine lookups per pixel) with the table itself L2-resident.  Same sums in the same (dy, dx) order; a skipped out-of-image tap
 // is now an added +0.0f.
+// One axis of the window, for the kernel and for the hosts that check it against the LDS caps: the 3-tap windows of the flow-grid
+// indices [first, last] reach `n` tap-table indices from `lo` on (on the UNPADDED concat2 grid, so -1 and n_tab are the zero ring)
+struct TapSpan { int lo, n; };
+__host__ __device__ __forceinline__ TapSpan tap_span(int first, int last, float ns, int n_tab)
+{
+    const int lo = nearest_ac(first, ns, n_tab + 2) - 1, hi = nearest_ac(last + 2, ns, n_tab + 2) - 1;
+    return TapSpan{lo, hi - lo + 1};
+}
+// the workgroup copies the window (rows from r_lo, columns from c_lo, wcols wide, npx pixels) of the sample's table Tn into `tab`: the 18
+// used floats of each table row, the zero ring as zeros; the caller's barrier follows
+__device__ __forceinline__ void fill_tap_window(float *tab, const float *Tn, int h2, int w2, int r_lo, int c_lo, int wcols, int npx)
+{
+    const float inv = 1.0f / (float)wcols;
+    for (int u = threadIdx.x; u < npx * 9; u += 256) {
+        const int px = u / 9, t = u - px * 9;
+        const int wr = (int)(((float)px + 0.5f) * inv), wc = px - wr * wcols;
+        const int sy = r_lo + wr, sx = c_lo + wc;
+        f32x2 v = {0.f, 0.f};
+        if ((unsigned)sy < (unsigned)h2 && (unsigned)sx < (unsigned)w2) v = *reinterpret_cast<const f32x2 *>(Tn + ((size_t)sy * w2 + sx) * 32 + t * 2);
+        *reinterpret_cast<f32x2 *>(tab + px * 18 + t * 2) = v;
+    }
+}
+// the nine taps of one pixel out of the LDS window, added to (a0, a1) in (dy, dx) order; ry / rx = the window offsets of the pixel's
+// three tap rows (times the window's width) and columns
+__device__ __forceinline__ void pf2_nine_taps(const float *tab, const int (&ry)[3], const int (&rx)[3], float &a0, float &a1)
+{
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const f32x2 t = *reinterpret_cast<const f32x2 *>(tab + (ry[dy] + rx[dx]) * 18 + (dy * 3 + dx) * 2);
+            a0 += t.x;
+            a1 += t.y;
+        }
+}
+// Host: over the tiles of one axis, the largest flow-grid extent a workgroup covers ([first, last] = cover(t)) and the largest tap_span
+template <typename Cover>
+static void max_spans(int tiles, float ns, int n_tab, Cover cover, int &flow_max, int &tab_max)
+{
+    flow_max = tab_max = 0;
+    for (int t = 0; t < tiles; ++t) {
+        int first, last; cover(t, first, last);
+        flow_max = std::max(flow_max, last - first + 1);
+        tab_max = std::max(tab_max, tap_span(first, last, ns, n_tab).n);
+    }
+}
+
 constexpr int PF2_TW = 64, PF2_PPT = 4, PF2_CAP = 320;      // CAP: window pixels held in LDS (23 KB)
 using Pf2Tile = Tile3<4, 16, PF2_TW, PF2_PPT>;              // tile3.h's skeleton with a 16 x 64 tile, no staged store
 constexpr int PF2_TH = Pf2Tile::TH;
@@ -367,19 +340,9 @@ __global__ __launch_bounds__(256) void pf2_tile_kernel(const float *__restrict__
     const Pf2Tile tile(tiles_x, tiles_y);
     const int n = tile.n, ty0 = tile.ty0, tx0 = tile.tx0;
     // source window (indices into the UNPADDED concat2 grid, so -1 and h2 / w2 are the zero ring)
-    const int r_lo = nearest_ac(ty0, nsy, h2 + 2) - 1, r_hi = nearest_ac(min(ty0 + PF2_TH - 1, oh - 1) + 2, nsy, h2 + 2) - 1;
-    const int c_lo = nearest_ac(tx0, nsx, w2 + 2) - 1, c_hi = nearest_ac(min(tx0 + PF2_TW - 1, ow - 1) + 2, nsx, w2 + 2) - 1;
-    const int wcols = c_hi - c_lo + 1, npx = (r_hi - r_lo + 1) * wcols;       // npx <= PF2_CAP: checked on the host
-    const float *Tn = T + (size_t)n * h2 * w2 * 32;
-    const float inv = 1.0f / (float)wcols;
-    for (int u = threadIdx.x; u < npx * 9; u += 256) {
-        const int px = u / 9, t = u - px * 9;
-        const int wr = (int)(((float)px + 0.5f) * inv), wc = px - wr * wcols;
-        const int sy = r_lo + wr, sx = c_lo + wc;
-        f32x2 v = {0.f, 0.f};
-        if ((unsigned)sy < (unsigned)h2 && (unsigned)sx < (unsigned)w2) v = *reinterpret_cast<const f32x2 *>(Tn + ((size_t)sy * w2 + sx) * 32 + t * 2);
-        *reinterpret_cast<f32x2 *>(tab + px * 18 + t * 2) = v;
-    }
+    const TapSpan R = tap_span(ty0, min(ty0 + PF2_TH - 1, oh - 1), nsy, h2), C = tap_span(tx0, min(tx0 + PF2_TW - 1, ow - 1), nsx, w2);
+    const int r_lo = R.lo, c_lo = C.lo, wcols = C.n, npx = R.n * C.n;       // npx <= PF2_CAP: checked on the host
+    fill_tap_window(tab, T + (size_t)n * h2 * w2 * 32, h2, w2, r_lo, c_lo, wcols, npx);
     __syncthreads();
     const float b0 = bias2[0], b1 = bias2[1];
 #pragma unroll
@@ -393,25 +356,9 @@ __global__ __launch_bounds__(256) void pf2_tile_kernel(const float *__restrict__
             rx[d] = nearest_ac(x + d, nsx, w2 + 2) - 1 - c_lo;
         }
         float a0 = b0, a1 = b1;
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const f32x2 t = *reinterpret_cast<const f32x2 *>(tab + (ry[dy] + rx[dx]) * 18 + (dy * 3 + dx) * 2);
-                a0 += t.x;
-                a1 += t.y;
-            }
-        const f32x2 u = sample_flow_legacy(pf3, n, h3, w3, y, x, usy, usx);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { a0 += u.x; a1 += u.y; }
-        f32x2 o; o.x = a0; o.y = a1;
-        reinterpret_cast<f32x2 *>(pf2)[((size_t)n * oh + y) * ow + x] = o;
+        pf2_nine_taps(tab, ry, rx, a0, a1);
+        reinterpret_cast<f32x2 *>(pf2)[((size_t)n * oh + y) * ow + x] = pf2_finish(a0, a1, pf3, n, h3, w3, y, x, usy, usx);
     }
-}
-
-static int nearest_ac_host(int i, float scale, int n_in)
-{
-    return std::min((int)roundf((float)i * scale), n_in - 1);
 }
 
 hipError_t launch_pf2(const float *T, int B, int h2, int w2, const float *bias2, const float *pf3, int h3, int w3,
@@ -423,12 +370,10 @@ hipError_t launch_pf2(const float *T, int B, int h2, int w2, const float *bias2,
     const float usy = (float)h3 / (float)(H - 2), usx = (float)w3 / (float)(W - 2);
     const int oh = H - 2, ow = W - 2;
     const int tiles_x = (ow + PF2_TW - 1) / PF2_TW, tiles_y = (oh + PF2_TH - 1) / PF2_TH;
-    // largest source window of any tile (the device evaluates the same fp32 map): rows and columns separately
-    int rows_max = 0, cols_max = 0;
-    for (int t = 0; t < tiles_y; ++t)
-        rows_max = std::max(rows_max, nearest_ac_host(std::min(t * PF2_TH + PF2_TH - 1, oh - 1) + 2, nsy, h2 + 2) - nearest_ac_host(t * PF2_TH, nsy, h2 + 2) + 1);
-    for (int t = 0; t < tiles_x; ++t)
-        cols_max = std::max(cols_max, nearest_ac_host(std::min(t * PF2_TW + PF2_TW - 1, ow - 1) + 2, nsx, w2 + 2) - nearest_ac_host(t * PF2_TW, nsx, w2 + 2) + 1);
+    // largest source window of any tile (tap_span, the map the device evaluates): rows and columns separately
+    int rows_max, cols_max, unused;
+    max_spans(tiles_y, nsy, h2, [&](int t, int &f, int &l) { f = t * PF2_TH; l = std::min(f + PF2_TH - 1, oh - 1); }, unused, rows_max);
+    max_spans(tiles_x, nsx, w2, [&](int t, int &f, int &l) { f = t * PF2_TW; l = std::min(f + PF2_TW - 1, ow - 1); }, unused, cols_max);
     // compulsory traffic (K9 is LDS / L2-bound, reported against the HBM bound of these bytes): the 128-byte table rows
     // and the coarser flow read once, 8 bytes written per output pixel
     const double alg_bytes = 128.0 * B * h2 * w2 + 8.0 * B * h3 * w3 + 8.0 * total;
@@ -698,6 +643,28 @@ __device__ __forceinline__ void quantise3(const rgb3 &r, unsigned char *o)
     for (int c = 0; c < 3; ++c) o[c] = (unsigned char)fminf(fmaxf(truncf(rr[2 - c] * 255.0f), 0.f), 255.f);
 }
 
+// How a warped pixel leaves a tile kernel.  U8: quantised bytes into the staging tile `stage`; STAGE: fp32 into the staging tile;
+// otherwise straight to pixel `pix` of `out` (NT: non-temporal stores) unless its pass is parked (`ok` false).
+template <bool U8, bool STAGE, bool NT>
+__device__ __forceinline__ void warp3_emit(const rgb3 &r, void *stage, int staged, void *out, long long pix, bool ok)
+{
+    if constexpr (U8) quantise3(r, reinterpret_cast<unsigned char *>(stage) + staged * 3);
+    else if (STAGE) *reinterpret_cast<rgb3 *>(reinterpret_cast<float *>(stage) + staged * 3) = r;
+    else if (ok) {
+        float *o = reinterpret_cast<float *>(out) + pix * 3;
+        if (NT) { __builtin_nontemporal_store(r.r, o); __builtin_nontemporal_store(r.g, o + 1); __builtin_nontemporal_store(r.b, o + 2); }
+        else reinterpret_cast<rgb3 *>(out)[pix] = r;
+    }
+}
+// ... and the staged tile's rows after the last pixel (tile3.h's store_rows).  A tile row of bytes is TW*3 = 96 bytes: 4-byte stores
+// where rows start on a 4-byte boundary (W % 4 == 0), bytes otherwise / at a ragged edge; fp32 rows: W % 4 == 0 (host)
+template <bool U8, bool STAGE, bool NT, typename Tile>
+__device__ __forceinline__ void warp3_rows(const Tile &tile, void *stage, void *out, int H, int W)
+{
+    if constexpr (U8) tile.template store_rows<3>(reinterpret_cast<const unsigned char *>(stage), reinterpret_cast<unsigned char *>(out), H, W, (W & 3) == 0);
+    else if (STAGE) tile.template store_rows<3, NT>(reinterpret_cast<const float *>(stage), reinterpret_cast<float *>(out), H, W);
+}
+
 template <bool FUSED, bool WRITE_FLOW, int WH, int WW, int TW, int PPT, bool REMAP = true, bool NT = false, bool STAGE = false>
 __global__ __launch_bounds__(256) void warp3_tile_kernel(const float *__restrict__ img, const float *__restrict__ flow,
                                                          float *__restrict__ out, float *__restrict__ outflow, int B,
@@ -713,9 +680,7 @@ __global__ __launch_bounds__(256) void warp3_tile_kernel(const float *__restrict
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        yy[j] = tile.y(j); xx[j] = tile.x(j);
-        ok[j] = yy[j] < H && xx[j] < W;
-        if (!ok[j]) { yy[j] = 0; xx[j] = 0; }
+        ok[j] = tile.template pixel<Park::ORIGIN>(j, H, W, yy[j], xx[j]);
     }
     f32x2 f[PPT];
     if (FUSED) {
@@ -730,15 +695,9 @@ __global__ __launch_bounds__(256) void warp3_tile_kernel(const float *__restrict
         }
     }
     warp3_pixels<false, PPT>(reinterpret_cast<const rgb3 *>(img) + n * HW, nullptr, yy, xx, f, H, W, [&](int j, const rgb3 &r) {
-        if (STAGE) {
-            *reinterpret_cast<rgb3 *>(stage + tile.staged(j) * 3) = r;
-        } else if (ok[j]) {
-            float *o = out + (n * HW + (long long)yy[j] * W + xx[j]) * 3;
-            if (NT) { __builtin_nontemporal_store(r.r, o); __builtin_nontemporal_store(r.g, o + 1); __builtin_nontemporal_store(r.b, o + 2); }
-            else *reinterpret_cast<rgb3 *>(o) = r;
-        }
+        warp3_emit<false, STAGE, NT>(r, stage, tile.staged(j), out, n * HW + (long long)yy[j] * W + xx[j], ok[j]);
     });
-    if (STAGE) tile.template store_rows<3, NT>(stage, out, H, W);
+    warp3_rows<false, STAGE, NT>(tile, stage, out, H, W);
 }
 
 static bool warp3_ok(const void *img, const void *out, const void *outflow, int B, int H, int W, int C)
@@ -793,7 +752,7 @@ hipError_t launch_flow_glue_warp(const float *flow, int B, int h, int w, const f
 // table + eight adds of the upsampled predict_flow3, pf2_tile_kernel above), the glue of main:497-498 and tf_warp (main:514,
 // warp3_tile_kernel<FUSED>).  A workgroup owns the same 16 x 32 tile of OUTPUT pixels the warp kernel does.  The glue's bilinear taps
 // of that tile reach a small rectangle of predict_flow2 (<= 18 x 34 pixels when the output is no smaller than the flow grid); the
-// workgroup computes exactly that rectangle -- statement for statement pf2_tile_kernel's sums, out of a tap-table window
+// workgroup computes exactly that rectangle -- pf2_nine_taps and pf2_finish, as pf2_tile_kernel does, out of a tap-table window
 // in LDS -- keeps it in LDS, writes the part it OWNS to the returned predict_flow2 tensor (rows [lo(ty0), lo(ty0 + TH)), the last
 // tile to the end: neighbouring tiles' rectangles overlap by a pixel or two, every pixel is written once), and glue + warp read
 // their four flow taps from LDS.  predict_flow2 is written (it is a returned tensor) but never re-read: 33 MB less traffic at B=8
@@ -805,6 +764,16 @@ struct TailParams {
     int h2, w2, h3, w3, H, W;                       // tap table grid, predict_flow3 grid, network input size (predict_flow2 is (H-2) x (W-2))
     float nsy, nsx, usy, usx;
 };
+// One axis of a tile's predict_flow2 rectangle, for the kernel and the host's cap check (the tile starts at output index o0, T_ of OUT
+// output indices per tile, `last` = the axis' last tile): it owns [flow_lo, flow_own1) and holds [flow_lo, flow_hi], what its glue taps
+// reach extended to what it owns
+__host__ __device__ __forceinline__ int flow_lo(int o0, float r, int n_flow) { return legacy_coord(o0, r, n_flow).lo; }
+__host__ __device__ __forceinline__ int flow_own1(int o0, int T_, bool last, float r, int n_flow) { return last ? n_flow : legacy_coord(o0 + T_, r, n_flow).lo; }
+__host__ __device__ __forceinline__ int flow_hi(int ol, int own1, float r, int n_flow)      // ol = the tile's last output index
+{
+    const int reach = legacy_coord(ol, r, n_flow).hi;
+    return reach > own1 - 1 ? reach : own1 - 1;
+}
 // U8 = the clip driver's frame path (BGR bytes -> swap / 255 through the 256-entry table, the warp, truncating quantiser, bytes out:
 // warp3_u8_tile_kernel's frame handling); otherwise fp32 frames in and out (warp3_tile_kernel's)
 template <bool WRITE_FLOW, bool STAGE, bool U8>
@@ -827,29 +796,16 @@ __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restr
     const int h = G.h, w = G.w;                       // predict_flow2's grid
     // ---- the predict_flow2 rectangle: what the tile's glue taps reach, extended to what the tile owns
     const int yl = min(ty0 + TH - 1, OH - 1), xl = min(tx0 + TW - 1, OW - 1);
-    const int wy0 = legacy_coord(ty0, G.ry, h).lo, wx0 = legacy_coord(tx0, G.rx, w).lo;
-    const int own_y1 = ty0 / TH == tiles_y - 1 ? h : legacy_coord(ty0 + TH, G.ry, h).lo;
-    const int own_x1 = tx0 / TW == tiles_x - 1 ? w : legacy_coord(tx0 + TW, G.rx, w).lo;
-    const int wy1 = max(legacy_coord(yl, G.ry, h).hi, own_y1 - 1), wx1 = max(legacy_coord(xl, G.rx, w).hi, own_x1 - 1);
+    const int wy0 = flow_lo(ty0, G.ry, h), wx0 = flow_lo(tx0, G.rx, w);
+    const int own_y1 = flow_own1(ty0, TH, ty0 / TH == tiles_y - 1, G.ry, h), own_x1 = flow_own1(tx0, TW, tx0 / TW == tiles_x - 1, G.rx, w);
+    const int wy1 = flow_hi(yl, own_y1, G.ry, h), wx1 = flow_hi(xl, own_x1, G.rx, w);
     const int WC = wx1 - wx0 + 1, npf = (wy1 - wy0 + 1) * WC;          // <= FT_PF_CAP: checked on the host
-    // ---- its tap-table window (indices into the UNPADDED concat2 grid: -1 and h2 / w2 are the zero ring), pf2_tile_kernel's way
-    const int r_lo = nearest_ac(wy0, P.nsy, P.h2 + 2) - 1, r_hi = nearest_ac(wy1 + 2, P.nsy, P.h2 + 2) - 1;
-    const int c_lo = nearest_ac(wx0, P.nsx, P.w2 + 2) - 1, c_hi = nearest_ac(wx1 + 2, P.nsx, P.w2 + 2) - 1;
-    const int wcols = c_hi - c_lo + 1, npx = (r_hi - r_lo + 1) * wcols;  // <= FT_T_CAP: checked on the host
-    const float *Tn = T + (size_t)n * P.h2 * P.w2 * 32;
-    {
-        const float inv = 1.0f / (float)wcols;
-        for (int u = threadIdx.x; u < npx * 9; u += 256) {
-            const int px = u / 9, t = u - px * 9;
-            const int wr = (int)(((float)px + 0.5f) * inv), wc = px - wr * wcols;
-            const int sy = r_lo + wr, sx = c_lo + wc;
-            f32x2 v = {0.f, 0.f};
-            if ((unsigned)sy < (unsigned)P.h2 && (unsigned)sx < (unsigned)P.w2) v = *reinterpret_cast<const f32x2 *>(Tn + ((size_t)sy * P.w2 + sx) * 32 + t * 2);
-            *reinterpret_cast<f32x2 *>(tab + px * 18 + t * 2) = v;
-        }
-    }
+    // ---- its tap-table window (indices into the UNPADDED concat2 grid: -1 and h2 / w2 are the zero ring)
+    const TapSpan R = tap_span(wy0, wy1, P.nsy, P.h2), C = tap_span(wx0, wx1, P.nsx, P.w2);
+    const int r_lo = R.lo, c_lo = C.lo, wcols = C.n, npx = R.n * C.n;      // <= FT_T_CAP: checked on the host
+    fill_tap_window(tab, T + (size_t)n * P.h2 * P.w2 * 32, P.h2, P.w2, r_lo, c_lo, wcols, npx);
     __syncthreads();
-    // ---- predict_flow2 over the rectangle (pf2_tile_kernel's statements), kept in LDS; the owned part leaves for HBM
+    // ---- predict_flow2 over the rectangle (pf2_tile_kernel's functions), kept in LDS; the owned part leaves for HBM
     {
         const float b0 = bias2[0], b1 = bias2[1];
         const float invc = 1.0f / (float)WC;
@@ -863,18 +819,8 @@ __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restr
                 rx[d] = nearest_ac(x + d, P.nsx, P.w2 + 2) - 1 - c_lo;
             }
             float a0 = b0, a1 = b1;
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const f32x2 t = *reinterpret_cast<const f32x2 *>(tab + (ry[dy] + rx[dx]) * 18 + (dy * 3 + dx) * 2);
-                    a0 += t.x;
-                    a1 += t.y;
-                }
-            const f32x2 uu = sample_flow_legacy(pf3, n, P.h3, P.w3, y, x, P.usy, P.usx);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { a0 += uu.x; a1 += uu.y; }
-            f32x2 o; o.x = a0; o.y = a1;
+            pf2_nine_taps(tab, ry, rx, a0, a1);
+            const f32x2 o = pf2_finish(a0, a1, pf3, n, P.h3, P.w3, y, x, P.usy, P.usx);
             pfw[u] = o;
             if (y < own_y1 && x < own_x1) reinterpret_cast<f32x2 *>(pf2)[((size_t)n * h + y) * w + x] = o;
         }
@@ -886,9 +832,7 @@ __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restr
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        yy[j] = tile.y(j); xx[j] = tile.x(j);
-        ok[j] = yy[j] < OH && xx[j] < OW;
-        if (!ok[j]) { yy[j] = ty0; xx[j] = tx0; }              // a pixel of this tile (its taps are inside the LDS rectangle); never stored
+        ok[j] = tile.pixel<Park::TILE>(j, OH, OW, yy[j], xx[j]);              // a pixel of this tile (its taps are inside the LDS rectangle); never stored
     }
     f32x2 f[PPT];
 #pragma unroll
@@ -900,24 +844,9 @@ __global__ __launch_bounds__(256) void pf2_glue_warp_kernel(const float *__restr
     }
     warp3_pixels<U8, PPT>(U8 ? (const void *)(reinterpret_cast<const unsigned char *>(img_) + n * HW * 3)
                              : (const void *)(reinterpret_cast<const rgb3 *>(img_) + n * HW), lut, yy, xx, f, OH, OW, [&](int j, const rgb3 &r) {
-        if constexpr (U8) quantise3(r, reinterpret_cast<unsigned char *>(stage) + tile.staged(j) * 3);
-        else if (STAGE) *reinterpret_cast<rgb3 *>(stage + tile.staged(j) * 3) = r;
-        else if (ok[j]) reinterpret_cast<rgb3 *>(out_)[n * HW + (long long)yy[j] * OW + xx[j]] = r;
+        warp3_emit<U8, STAGE, false>(r, stage, tile.staged(j), out_, n * HW + (long long)yy[j] * OW + xx[j], ok[j]);
     });
-    // a tile row of bytes is TW*3 = 96 bytes; 4-byte stores where rows start on a 4-byte boundary (OW % 4 == 0), bytes otherwise
-    if constexpr (U8) tile.template store_rows<3>(reinterpret_cast<const unsigned char *>(stage), reinterpret_cast<unsigned char *>(out_), OH, OW, (OW & 3) == 0);
-    else if (STAGE) tile.template store_rows<3>(stage, reinterpret_cast<float *>(out_), OH, OW);
-}
-
-static Lerp legacy_coord_host(int o, float scale, int n_in)
-{
-    const float f = (float)o * scale;
-    const float fl = floorf(f);
-    Lerp L;
-    L.lo = std::min((int)fl, n_in - 1);
-    L.hi = std::min(L.lo + 1, n_in - 1);
-    L.t = f - fl;
-    return L;
+    warp3_rows<U8, STAGE, false>(tile, stage, out_, OH, OW);
 }
 
 // predict_flow2 gather + glue + warp as one launch; hipErrorNotSupported when a tile's rectangles would not fit the LDS windows (an output
@@ -937,22 +866,18 @@ static hipError_t launch_tail(const float *T, int B, int h2, int w2, const float
     int tx, ty;
     dim3 grid;
     if (!WarpTile::plan(B, oh, ow, (long long)B * oh * ow * (u8 ? 3 : 1), tx, ty, grid)) return hipErrorNotSupported;
-    // the largest rectangles of any tile, rows and columns separately (the device evaluates the same fp32 maps); the tiles' owned ranges
-    // must tile [0, h) x [0, w) without gaps: lo(0) = 0 and the ranges are consecutive by construction
-    auto span = [&](int tiles, int T_, int OUT, float r, int nflow, float ns, int ntab, int &pf_max, int &t_max) {
-        for (int t = 0; t < tiles; ++t) {
-            const int o0 = t * T_, ol = std::min(o0 + T_ - 1, OUT - 1);
-            const int w0 = legacy_coord_host(o0, r, nflow).lo;
-            const int own1 = t == tiles - 1 ? nflow : legacy_coord_host(o0 + T_, r, nflow).lo;
-            const int w1 = std::max(legacy_coord_host(ol, r, nflow).hi, own1 - 1);
-            pf_max = std::max(pf_max, w1 - w0 + 1);
-            t_max = std::max(t_max, nearest_ac_host(w1 + 2, ns, ntab + 2) - nearest_ac_host(w0, ns, ntab + 2) + 1);
-        }
+    // the largest rectangles of any tile, rows and columns separately (the device evaluates the same legacy_coord / nearest_ac); the
+    // tiles' owned ranges must tile [0, h) x [0, w) without gaps: lo(0) = 0 and the ranges are consecutive by construction
+    if (flow_lo(0, G.ry, h) != 0 || flow_lo(0, G.rx, w) != 0) return hipErrorNotSupported;
+    auto rect = [](int tiles, int T_, int OUT, float r, int n_flow) {       // one axis of tile t's predict_flow2 rectangle: the kernel's rules
+        return [=](int t, int &lo, int &hi) {
+            lo = flow_lo(t * T_, r, n_flow);
+            hi = flow_hi(std::min(t * T_ + T_ - 1, OUT - 1), flow_own1(t * T_, T_, t == tiles - 1, r, n_flow), r, n_flow);
+        };
     };
-    if (legacy_coord_host(0, G.ry, h).lo != 0 || legacy_coord_host(0, G.rx, w).lo != 0) return hipErrorNotSupported;
-    int pr = 0, pc = 0, tr = 0, tc = 0;
-    span(ty, WarpTile::TH, oh, G.ry, h, P.nsy, h2, pr, tr);
-    span(tx, WarpTile::TW, ow, G.rx, w, P.nsx, w2, pc, tc);
+    int pr, pc, tr, tc;
+    max_spans(ty, P.nsy, h2, rect(ty, WarpTile::TH, oh, G.ry, h), pr, tr);
+    max_spans(tx, P.nsx, w2, rect(tx, WarpTile::TW, ow, G.rx, w), pc, tc);
     if (pr * pc > FT_PF_CAP || tr * tc > FT_T_CAP) return hipErrorNotSupported;
     const long long total = (long long)B * oh * ow;
     // compulsory traffic: tap-table rows, the coarser flow, predict_flow2 WRITTEN once (never re-read), frame read, warped (and the
@@ -1004,18 +929,15 @@ __global__ __launch_bounds__(256) void warp3_u8_tile_kernel(const unsigned char 
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        yy[j] = tile.y(j); xx[j] = tile.x(j);
-        ok[j] = yy[j] < H && xx[j] < W;
-        if (!ok[j]) { yy[j] = 0; xx[j] = 0; }
+        ok[j] = tile.template pixel<Park::ORIGIN>(j, H, W, yy[j], xx[j]);
     }
     f32x2 f[PPT];
     glue_pixels<PPT>(reinterpret_cast<const f32x2 *>(flow) + (long long)n * G.h * G.w, yy, xx, G, f, [&](int j) {
         if (WRITE_FLOW && ok[j]) reinterpret_cast<f32x2 *>(outflow)[n * HW + (long long)yy[j] * W + xx[j]] = f[j];
     });
     __syncthreads();                                                  // the table
-    warp3_pixels<true, PPT>(img + n * HW * 3, lut, yy, xx, f, H, W, [&](int j, const rgb3 &r) { quantise3(r, stage + tile.staged(j) * 3); });
-    // a tile row is TW*3 = 96 bytes; 4-byte stores where rows start on a 4-byte boundary (W % 4 == 0), bytes otherwise / at a ragged edge
-    tile.template store_rows<3>(stage, out, H, W, (W & 3) == 0);
+    warp3_pixels<true, PPT>(img + n * HW * 3, lut, yy, xx, f, H, W, [&](int j, const rgb3 &r) { warp3_emit<true, true, false>(r, stage, tile.staged(j), out, 0, true); });
+    warp3_rows<true, true, false>(tile, stage, out, H, W);
 }
 
 hipError_t launch_flow_glue_warp_u8(const float *flow, int B, int h, int w, const unsigned char *frame, float *outflow, unsigned char *out, int oh,
@@ -1051,8 +973,7 @@ __global__ __launch_bounds__(256) void glue_tile_kernel(const float *__restrict_
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        ok[j] = tile.y(j) < oh && tile.x(j) < ow;
-        yy[j] = min(tile.y(j), oh - 1); xx[j] = min(tile.x(j), ow - 1);
+        ok[j] = tile.pixel<Park::CLAMP>(j, oh, ow, yy[j], xx[j]);
     }
     f32x2 o[PPT];
     glue_pixels<PPT>(reinterpret_cast<const f32x2 *>(flow) + (size_t)n * G.h * G.w, yy, xx, G, o, [&](int j) {
@@ -1090,8 +1011,7 @@ __global__ __launch_bounds__(256) void resize3_tile_kernel(const float *__restri
     bool ok[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-        ok[j] = tile.y(j) < oh && tile.x(j) < ow;
-        yy[j] = min(tile.y(j), oh - 1); xx[j] = min(tile.x(j), ow - 1);
+        ok[j] = tile.pixel<Park::CLAMP>(j, oh, ow, yy[j], xx[j]);
         Y[j] = legacy_coord(yy[j], ry, h); X[j] = legacy_coord(xx[j], rx, w);
         tl[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].lo * w + X[j].lo) * Cs); tr[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].lo * w + X[j].hi) * Cs);
         bl[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].hi * w + X[j].lo) * Cs); br[j] = *reinterpret_cast<const rgb3 *>(b + ((size_t)Y[j].hi * w + X[j].hi) * Cs);
@@ -1124,132 +1044,6 @@ static hipError_t launch_resize3_tile(const float *x, int B, int h, int w, int C
 hipError_t launch_resize_bilinear_slice3(const float *x, int B, int h, int w, int Cs, int c_off, float *out, int oh, int ow, hipStream_t stream)
 {
     return launch_resize3_tile(x, B, h, w, Cs, c_off, out, oh, ow, stream);
-}
-
-// tf.nn.max_pool(ksize 2, strides 2, SAME) (vgg16.py:51-53): out = ceil(n/2); the window's taps beyond
-// the bottom/right edge do not take part.  One thread per 4 output channels.
-__global__ __launch_bounds__(256) void maxpool2x2_kernel(const float *__restrict__ x, int B, int H, int W, int C4,
-                                                         float *__restrict__ out, int oh, int ow)
-{
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long total = (long long)B * oh * ow * C4;
-    if (idx >= total) return;
-    const int c = (int)(idx % C4);
-    const long long pix = idx / C4;
-    const int n = (int)(pix / (oh * ow));
-    const int rem = (int)(pix - (long long)n * oh * ow);
-    const int oy = rem / ow, ox = rem - oy * ow;
-    const int y0 = 2 * oy, x0 = 2 * ox;
-    const bool y1ok = y0 + 1 < H, x1ok = x0 + 1 < W;
-    const f32x4 *b = reinterpret_cast<const f32x4 *>(x) + (long long)n * H * W * C4 + c;
-    f32x4 m = b[((long long)y0 * W + x0) * C4];
-    if (x1ok) { const f32x4 v = b[((long long)y0 * W + x0 + 1) * C4]; m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w); }
-    if (y1ok) {
-        const f32x4 v = b[((long long)(y0 + 1) * W + x0) * C4]; m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-        if (x1ok) { const f32x4 u = b[((long long)(y0 + 1) * W + x0 + 1) * C4]; m.x = fmaxf(m.x, u.x); m.y = fmaxf(m.y, u.y); m.z = fmaxf(m.z, u.z); m.w = fmaxf(m.w, u.w); }
-    }
-    reinterpret_cast<f32x4 *>(out)[idx] = m;
-}
-
-hipError_t launch_maxpool2x2(const float *x, int B, int H, int W, int C, float *out, hipStream_t stream)
-{
-    if (C & 3) return hipErrorInvalidValue;
-    const int oh = (H + 1) / 2, ow = (W + 1) / 2;
-    const long long total = (long long)B * oh * ow * (C / 4);
-    maxpool2x2_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream>>>(x, B, H, W, C / 4, out, oh, ow);
-    return hipGetLastError();
-}
-
-// NLDF.py:29: input * 255 - VGG_MEAN (per channel)
-struct Mean4 { float m[4]; };
-__global__ __launch_bounds__(256) void scale_shift_kernel(const float *__restrict__ x, long long n, int C, float scale, Mean4 mean,
-                                                          float *__restrict__ out)
-{
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n) return;
-    const int c = (int)(idx % C);
-    out[idx] = x[idx] * scale - mean.m[c];
-}
-
-// VGG16's first layer (conv1_1, vgg16.py:29: 3x3 SAME on the 3-channel image -> 64 channels, ReLU): K = 27 is a single padded
-// K-tile of the MFMA kernel, whose time is then its 4-byte scattered epilogue (1.2 TB/s on the 2.1 GB it writes at 4 x 1080p).  This
-// layer is an HBM-bound WRITE, so it gets a plain kernel shaped for the store: 16 lanes per pixel, one float4 of output channels
-// each (256 contiguous bytes per pixel), four pixels of a row per thread so that each filter chunk is read from LDS once for the
-// four; the 3x6x3 input window comes through L1 (the 16 lanes of a pixel group hit the same addresses), filter + bias sit in LDS.  W: HWIO [3][3][3][cout], cout % 4 == 0, cout <= 64.
-__global__ __launch_bounds__(256) void conv3x3_rgb_kernel(const float *__restrict__ x, int B, int H, int W, const float *__restrict__ Wf,
-                                                          const float *__restrict__ bias, int cout, int relu, float *__restrict__ out)
-{
-    __shared__ f32x4 sW[27 * 16];
-    __shared__ f32x4 sB[16];
-    const int q4 = cout >> 2;
-    for (int i = threadIdx.x; i < 27 * q4; i += 256) sW[(i / q4) * 16 + (i % q4)] = *reinterpret_cast<const f32x4 *>(Wf + (long long)(i / q4) * cout + (i % q4) * 4);
-    if (threadIdx.x < q4) sB[threadIdx.x] = *reinterpret_cast<const f32x4 *>(bias + threadIdx.x * 4);
-    __syncthreads();
-    // a thread: 4 consecutive pixels of a row x one float4 of output channels (the filter chunk is read once for the four)
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int q = (int)(idx & 15);
-    const long long grp = idx >> 4;
-    const int WQ = (W + 3) >> 2;
-    if (grp >= (long long)B * H * WQ || q >= q4) return;
-    const int n = (int)(grp / ((long long)H * WQ));
-    const int rem = (int)(grp - (long long)n * H * WQ);
-    const int y = rem / WQ, x0 = (rem - y * WQ) * 4;
-    const float *xb = x + (long long)n * H * W * 3;
-    f32x4 acc[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) acc[p] = sB[q];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int iy = y + ky - 1;
-        const bool yok = (unsigned)iy < (unsigned)H;
-        float v[6][3];                                   // input columns x0-1 .. x0+4 of this row
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int ix = x0 + j - 1;
-            const bool ok = yok && (unsigned)ix < (unsigned)W;
-            const float *px = xb + ((long long)iy * W + ix) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[j][c] = ok ? px[c] : 0.f;
-        }
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const f32x4 w = sW[((ky * 3 + kx) * 3 + c) * 16 + q];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) acc[p] += v[p + kx][c] * w;
-            }
-    }
-    float *o = out + (((long long)n * H + y) * W + x0) * cout + q * 4;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        if (x0 + p >= W) break;
-        f32x4 r = acc[p];
-        if (relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = fmaxf(r[e], 0.f);
-        }
-        *reinterpret_cast<f32x4 *>(o + (long long)p * cout) = r;
-    }
-}
-
-hipError_t launch_conv3x3_rgb(const float *x, int B, int H, int W, const float *Wf, const float *bias, int cout, int relu, float *out,
-                              hipStream_t stream)
-{
-    if ((cout & 3) || cout > 64 || cout < 4) return hipErrorInvalidValue;
-    const long long n = (long long)B * H * ((W + 3) / 4) * 16;
-    conv3x3_rgb_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(x, B, H, W, Wf, bias, cout, relu, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_scale_shift(const float *x, long long npix, int C, float scale, const float *mean4, float *out, hipStream_t stream)
-{
-    if (C < 1 || C > 4) return hipErrorInvalidValue;
-    Mean4 m{};
-    for (int c = 0; c < C; ++c) m.m[c] = mean4[c];
-    const long long n = npix * C;
-    scale_shift_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(x, n, C, scale, m, out);
-    return hipGetLastError();
 }
 
 // get_pixel_value (main:44-68): out[b,h,w,:] = img[b, y[b,h,w], x[b,h,w], :]

@@ -1,7 +1,7 @@
 // Optional per-launch timing of the HBM-side kernels (bench.py's roofline_hbm block): when switched on, a launch goes through
 // hipExtLaunchKernelGGL, which stamps the kernel's own start/stop into two events on the launch stream (the same mechanism as
 // the conv launches' profile slots); off (the default) it is a plain launch.  Process-wide, instrumentation only.  The records
-// live in flow_ops.hip (hbm_profile_begin); this header is the launch wrapper shared by flow_ops.hip and sampler_ops.hip.
+// live in hbm_profile.cpp (hbm_profile_begin; host code); this header is the launch wrapper shared by flow_ops.hip and sampler_ops.hip.
 #pragma once
 #include "vstab_internal.h"
 #include <hip/hip_ext.h>

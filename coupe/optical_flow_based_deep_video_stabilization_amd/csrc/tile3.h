@@ -5,7 +5,9 @@
 //     ("passes"), pass j of wave w being patch q = 4 j + w of the tile;
 //   * workgroups are numbered through the XCD map: one XCD's L2 sees a contiguous band of tile rows;
 //   * results leave through LDS as 16-byte stores of whole tile rows (4-byte stores for 8-bit pixels).
-// Stated once here: the shapes, the prologue, a pass's pixel, the staged row store, and the host's tile count / guards.
+// Stated once here: the shapes, the workgroup's tile (the constructor), a pass's pixel and its prologue (pixel<PARK>: each kernel keeps its
+// own parking rule), the staged row store, and the host's tile count / guards.  The tile kernels of sampler_ops.hip and warp_flow_grad.hip
+// interleave the prologue with per-pixel work or skip instead of parking, and keep their loops.
 #pragma once
 #include "vstab_internal.h"
 
@@ -14,6 +16,9 @@ namespace vstab {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed, aligned(4))) rgb3 { float r, g, b; };
+
+// where a pass beyond the output is parked: the output's origin, the tile's origin, or the nearest output pixel
+enum class Park { ORIGIN, TILE, CLAMP };
 
 constexpr int WT_WH = 4, WT_WW = 16, WT_TW = 32, WT_PPT = 2;      // 16 x 32 tile of 4 x 16 patches, two pixels per thread
 
@@ -46,6 +51,20 @@ struct Tile3 {
     __device__ __forceinline__ int y(int j) const { return ty0 + row(j); }
     __device__ __forceinline__ int x(int j) const { return tx0 + col(j); }
     __device__ __forceinline__ int staged(int j) const { return row(j) * TW + col(j); }
+    // the prologue of pass j on an OH x OW output: its pixel (yy, xx); false = the pass is parked (never stored) at PARK
+    template <Park PARK>
+    __device__ __forceinline__ bool pixel(int j, int OH, int OW, int &yy, int &xx) const
+    {
+        if (PARK == Park::CLAMP) {
+            const bool ok = y(j) < OH && x(j) < OW;
+            yy = min(y(j), OH - 1); xx = min(x(j), OW - 1);
+            return ok;
+        }
+        yy = y(j); xx = x(j);
+        const bool ok = yy < OH && xx < OW;
+        if (!ok) { yy = PARK == Park::TILE ? ty0 : 0; xx = PARK == Park::TILE ? tx0 : 0; }
+        return ok;
+    }
 
     // The tile, staged in LDS as TH rows of TW pixels of C elements of type E, to out [B, OH, OW, C]: vectors of four elements (a
     // row is TW*C*sizeof(E) bytes from an address the host found aligned to the vector, OW*C % 4 == 0), single elements at a

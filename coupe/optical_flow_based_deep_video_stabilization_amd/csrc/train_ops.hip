@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "vstab_internal.h"
+#include "resample_coords.h"
 
 namespace vstab {
 
@@ -691,22 +692,9 @@ hipError_t launch_lrelu_backward(const float *y, int cs_y, int cy_off, float *dy
 // ---------------------------------------------------------------------------------
 // Adjoints of the two resamplers in the decoder, and the full-resolution head's upsampler itself.
 // Both backward kernels GATHER (one thread per input element loops over the few output positions that read it and
-// re-derives the forward's index / weight with the forward's own float arithmetic), so sums have a fixed order.
+// re-derives the forward's index / weight with the forward's own maps of resample_coords.h), so sums have a fixed order.
 // ---------------------------------------------------------------------------------
 namespace {
-struct LerpT { int lo, hi; float t; };
-__device__ __forceinline__ LerpT legacy_coord_t(int o, float scale, int n_in)        // = flow_ops.hip legacy_coord
-{
-    const float f = (float)o * scale;
-    const float fl = floorf(f);
-    LerpT L;
-    L.lo = min((int)fl, n_in - 1);
-    L.hi = min(L.lo + 1, n_in - 1);
-    L.t = f - fl;
-    return L;
-}
-__device__ __forceinline__ int nearest_ac_t(int i, float scale, int n_in) { return min((int)roundf((float)i * scale), n_in - 1); }
-
 // backward of tf.image.resize_images / UpSampling2dLayer (legacy bilinear): out = top + (bot - top) * ty with
 // top = tl + (tr - tl) * tx  =>  d out / d tl = (1-tx)(1-ty), tr: tx(1-ty), bl: (1-tx)ty, br: tx*ty
 // A gather over the output pixels whose taps reach the input element, in a fixed order: no atomics, bit-reproducible.  `gain` scales
@@ -727,11 +715,11 @@ __global__ __launch_bounds__(256) void resize_bilinear_bwd_kernel(const float *_
     const float *g = dout + (long long)n * oh * ow * C + c;
     float s = 0.f;
     for (int oy = oy0; oy <= oy1; ++oy) {
-        const LerpT Y = legacy_coord_t(oy, ry, h);
+        const Lerp Y = legacy_coord(oy, ry, h);
         const float wy = (Y.lo == iy ? 1.f - Y.t : 0.f) + (Y.hi == iy ? Y.t : 0.f);
         if (wy == 0.f) continue;
         for (int ox = ox0; ox <= ox1; ++ox) {
-            const LerpT X = legacy_coord_t(ox, rx, w);
+            const Lerp X = legacy_coord(ox, rx, w);
             const float wx = (X.lo == ix ? 1.f - X.t : 0.f) + (X.hi == ix ? X.t : 0.f);
             if (wx != 0.f) s += wy * wx * g[((long long)oy * ow + ox) * C];
         }
@@ -751,7 +739,7 @@ __global__ __launch_bounds__(256) void pad_nearest_up_kernel(const float *__rest
     const int c = (int)(idx % C4);
     const int pix = (int)(idx / C4);
     const int y = pix / W, x = pix - y * W;
-    const int syi = nearest_ac_t(y, sy, h2 + 2) - 1, sxi = nearest_ac_t(x, sx, w2 + 2) - 1;
+    const int syi = nearest_ac(y, sy, h2 + 2) - 1, sxi = nearest_ac(x, sx, w2 + 2) - 1;
     f32x4v v = {0.f, 0.f, 0.f, 0.f};
     if ((unsigned)syi < (unsigned)h2 && (unsigned)sxi < (unsigned)w2)
         v = reinterpret_cast<const f32x4v *>(src)[(((long long)n * h2 + syi) * w2 + sxi) * C4 + c];
@@ -772,9 +760,9 @@ __global__ __launch_bounds__(256) void pad_nearest_up_bwd_kernel(const float *__
     const int span_y = sy > 0.f ? (int)(1.f / sy) + 2 : H, span_x = sx > 0.f ? (int)(1.f / sx) + 2 : W;
     f32x4v s = {0.f, 0.f, 0.f, 0.f};
     for (int y = max(0, yc - span_y); y <= min(H - 1, yc + span_y); ++y) {
-        if (nearest_ac_t(y, sy, h2 + 2) != syi + 1) continue;
+        if (nearest_ac(y, sy, h2 + 2) != syi + 1) continue;
         for (int x = max(0, xc - span_x); x <= min(W - 1, xc + span_x); ++x) {
-            if (nearest_ac_t(x, sx, w2 + 2) != sxi + 1) continue;
+            if (nearest_ac(x, sx, w2 + 2) != sxi + 1) continue;
             s += reinterpret_cast<const f32x4v *>(dout)[(((long long)n * H + y) * W + x) * C4 + c];
         }
     }
@@ -805,10 +793,10 @@ __global__ __launch_bounds__(256) void pf2_taps_bwd_kernel(const float *__restri
     const int span_y = sy > 0.f ? (int)(1.f / sy) + 2 : H, span_x = sx > 0.f ? (int)(1.f / sx) + 2 : W;
     float a0 = 0.f, a1 = 0.f;
     for (int r = max(dy, rc - span_y); r <= min(oh - 1 + dy, rc + span_y); ++r) {          // r = y + dy: row of the padded grid
-        if (nearest_ac_t(r, sy, h2 + 2) != syi + 1) continue;
+        if (nearest_ac(r, sy, h2 + 2) != syi + 1) continue;
         const int y = r - dy;
         for (int c = max(dx, cc - span_x); c <= min(ow - 1 + dx, cc + span_x); ++c) {
-            if (nearest_ac_t(c, sx, w2 + 2) != sxi + 1) continue;
+            if (nearest_ac(c, sx, w2 + 2) != sxi + 1) continue;
             const float *p = g + (((long long)n * oh + y) * ow + (c - dx)) * cs_g;
             a0 += p[0];
             a1 += p[1];

@@ -367,7 +367,7 @@ hipError_t launch_resize_bilinear_slice3(const float *x, int B, int h, int w, in
                                          hipStream_t stream);
 hipError_t launch_warp_flow(const float *img, const float *flow, float *out, int B, int H, int W,
                             int C, hipStream_t stream);
-// per-launch timing of the HBM-side kernels (flow_ops.hip): slots of vstab_hbm_profile_read
+// per-launch timing of the HBM-side kernels (records: hbm_profile.cpp, launch wrapper: hbm_profile.h): slots of vstab_hbm_profile_read
 enum { HBM_SLOT_WARP = 0, HBM_SLOT_GLUE = 1, HBM_SLOT_GLUE_WARP = 2, HBM_SLOT_PF2 = 3, HBM_SLOT_ST = 4, HBM_SLOT_HOMOG = 5, HBM_SLOT_TAIL = 6, HBM_SLOTS = 7 };
 void hbm_profile_enable(int mode);
 hipError_t hbm_profile_read(int slot, double *ms_sum, int *launches, double *alg_bytes_sum);
@@ -379,7 +379,7 @@ hipError_t launch_pf2_glue_warp_u8(const float *T, int B, int h2, int w2, const 
                                    const unsigned char *frame, float *outflow, unsigned char *out, int oh, int ow, hipStream_t stream);
 hipError_t launch_flow_glue_warp(const float *flow, int B, int h, int w, const float *img, float *outflow, float *out, int oh, int ow,
                                  int C, int net_h, int net_w, hipStream_t stream);
-// 2x2 stride-2 SAME max pool (vgg16.py:51-53), NHWC, C % 4 == 0
+// VGG16 front end of the NLDF head (nldf_ops.hip): 2x2 stride-2 SAME max pool (vgg16.py:51-53), NHWC, C % 4 == 0
 hipError_t launch_maxpool2x2(const float *x, int B, int H, int W, int C, float *out, hipStream_t stream);
 // 3x3 SAME conv on a 3-channel image (VGG16 conv1_1): W HWIO [3][3][3][cout] unpacked, cout % 4 == 0, cout <= 64
 hipError_t launch_conv3x3_rgb(const float *x, int B, int H, int W, const float *Wf, const float *bias, int cout, int relu, float *out,

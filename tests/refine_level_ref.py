@@ -82,7 +82,7 @@ def wdec_emulated(x, W, out_hw, geom=None):
 
 
 def legacy_axis(n_in, n_out):
-    """TF-1.10 ResizeBilinear (align_corners=False), one axis, coordinates in fp32 exactly as flow_ops.hip's legacy_coord:
+    """TF-1.10 ResizeBilinear (align_corners=False), one axis, coordinates in fp32 exactly as legacy_coord (csrc/resample_coords.h):
     f = float(o) * (float(n_in) / float(n_out)), lo = min(floor(f), n_in - 1), hi = min(lo + 1, n_in - 1), t = f - floor(f)"""
     scale = np.float32(n_in) / np.float32(n_out)
     f = (np.arange(n_out, dtype=np.float32) * scale).astype(np.float32)
