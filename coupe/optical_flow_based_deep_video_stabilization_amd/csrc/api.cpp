@@ -5,6 +5,7 @@
 #include <new>
 
 #include "api_internal.h"
+#include "vgg_plan.h"
 
 using namespace vstab;
 
@@ -116,6 +117,7 @@ extern "C" void vstab_destroy(vstab_ctx *ctx)
     if (ctx->dev_weights) (void)hipFree(ctx->dev_weights);
     for (hipEvent_t e : ctx->prof_ev) (void)hipEventDestroy(e);
     if (ctx->vgg_weights) (void)hipFree(ctx->vgg_weights);
+    vgg_backward_free(ctx);
     vstab_nldf_free(ctx->nldf);
     delete ctx;
 }

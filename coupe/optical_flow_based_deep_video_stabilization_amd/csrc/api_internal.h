@@ -48,6 +48,8 @@ struct vstab_ctx {
     size_t vgg_wino_w[13] = {0};         // Winograd-domain operands of conv3_2 .. conv5_3
     size_t vgg_raw0 = 0;                 // conv1_1's filter as given (HWIO), for conv3x3_rgb_kernel
     size_t vgg_zero = 0;                 // 1024 zeros (bias of the Winograd-domain GEMM)
+    size_t vgg_raw[13] = {0};            // every filter as given (HWIO): the backward's launchers take raw weights
+    float *vgg_bwd_wino[13] = {nullptr}; // transposed Winograd-domain operands of the input gradient, packed at the first backward that needs them
 };
 
 int fail(vstab_ctx *ctx, int code, const char *fmt, ...);

@@ -1,18 +1,15 @@
 // C ABI of the VGG16 trunk (vgg16.py): thirteen 3x3 convolutions + ReLU and five 2x2 max pools, every activation returned.
 #include "api_internal.h"
 #include "conv_desc.h"
+#include "vgg_plan.h"
 
 using namespace vstab;
 
-namespace {
-struct VggLayer { const char *name; int cin, cout; bool pool_after; };
 const VggLayer VGG[13] = {{"conv1_1", 3, 64, false},   {"conv1_2", 64, 64, true},    {"conv2_1", 64, 128, false},
                           {"conv2_2", 128, 128, true}, {"conv3_1", 128, 256, false}, {"conv3_2", 256, 256, false},
                           {"conv3_3", 256, 256, true}, {"conv4_1", 256, 512, false}, {"conv4_2", 512, 512, false},
                           {"conv4_3", 512, 512, true}, {"conv5_1", 512, 512, false}, {"conv5_2", 512, 512, false},
                           {"conv5_3", 512, 512, true}};
-
-struct VggPlan { int h[18], w[18], c[18]; size_t partial_floats, wino_v, wino_m; bool wino[13]; };
 
 bool vgg_plan(int B, int H, int W, VggPlan &v)
 {
@@ -37,17 +34,19 @@ bool vgg_plan(int B, int H, int W, VggPlan &v)
     return true;
 }
 
+namespace {
 size_t vgg_ws_bytes(const VggPlan &v)       // [split-K slabs | Winograd V | Winograd M], each 256-byte aligned
 {
     return a256(std::max<size_t>(v.partial_floats * 4, 256)) + a256(v.wino_v * 4) + a256(v.wino_m * 4);
 }
+
+}  // namespace
 
 int vgg_max_chunk(int B, int H, int W)
 {
     VggPlan v;
     return largest_fitting(B, [&](int b) { return vgg_plan(b, H, W, v); });
 }
-}  // namespace
 
 extern "C" int vstab_vgg16_shapes(int H, int W, int32_t *hwc54)
 {
@@ -85,10 +84,10 @@ extern "C" int vstab_vgg16_load(vstab_ctx *ctx, const vstab_tensor *t, int count
         fold_bn(b->data, nullptr, nullptr, nullptr, VGG[l].cout, npad, ones.data(), host.data() + ctx->vgg_b[l]);
         ctx->vgg_w[l] = reserve((size_t)L.ktiles() * npad * 32);
         pack_conv(W->data, ones.data(), 3, 3, VGG[l].cin, VGG[l].cin, VGG[l].cout, npad, L, host.data() + ctx->vgg_w[l]);
-        if (l == 0) {                                  // conv1_1 also unpacked (HWIO as given) for its store-shaped kernel
-            ctx->vgg_raw0 = reserve((size_t)27 * VGG[0].cout);
-            std::memcpy(host.data() + ctx->vgg_raw0, W->data, sizeof(float) * 27 * VGG[0].cout);
-        }
+        // the filter as given (HWIO): conv1_1's store-shaped kernel reads it, and so do the backward's launchers (vgg_grad_api.cpp)
+        ctx->vgg_raw[l] = reserve((size_t)9 * VGG[l].cin * VGG[l].cout);
+        std::memcpy(host.data() + ctx->vgg_raw[l], W->data, sizeof(float) * 9 * VGG[l].cin * VGG[l].cout);
+        if (l == 0) ctx->vgg_raw0 = ctx->vgg_raw[0];
         ctx->vgg_wino_w[l] = 0;
         if (VGG[l].cin >= 256) {                       // Winograd-domain operand for the layers that may run in that form
             ctx->vgg_wino_w[l] = reserve((size_t)16 * (VGG[l].cin / 32) * VGG[l].cout * 32);
@@ -98,6 +97,7 @@ extern "C" int vstab_vgg16_load(vstab_ctx *ctx, const vstab_tensor *t, int count
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->vgg_weights) { (void)hipFree(ctx->vgg_weights); ctx->vgg_weights = nullptr; }
     ctx->vgg_loaded = false;
+    vgg_backward_free(ctx);                        // operands derived from the previous filters
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->vgg_weights), host.size() * sizeof(float));
     if (e != hipSuccess) return fail(ctx, VSTAB_E_NOMEM, "hipMalloc(%zu bytes of VGG16 weights): %s", host.size() * 4, hipGetErrorString(e));
     HIP_TRY(ctx, hipMemcpy(ctx->vgg_weights, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));

@@ -384,6 +384,19 @@ hipError_t launch_maxpool2x2(const float *x, int B, int H, int W, int C, float *
 // 3x3 SAME conv on a 3-channel image (VGG16 conv1_1): W HWIO [3][3][3][cout] unpacked, cout % 4 == 0, cout <= 64
 hipError_t launch_conv3x3_rgb(const float *x, int B, int H, int W, const float *Wf, const float *bias, int cout, int relu, float *out,
                               hipStream_t stream);
+// ---- backward pieces of the VGG16 trunk (vgg_grad_ops.hip)
+// dy (=, or accumulate: gated +=) the gradient of max_pool(2, 2, SAME) at y [B,H,W,C] routed to each window's first maximum, passed
+// only where y > 0; dpool [B,ceil(H/2),ceil(W/2),C]; C % 4 == 0
+hipError_t launch_maxpool2x2_relu_backward(const float *y, int B, int H, int W, int C, const float *dpool, float *dy, int accumulate,
+                                           hipStream_t stream);
+// dy *= (y > 0) in place over n4 float4s
+hipError_t launch_relu_backward(const float *y, float *dy, long long n4, hipStream_t stream);
+// conv1_1: gout [B,H,W,cout] -> dx [B,H,W,3]; W HWIO [3][3][3][cout], cout % 4 == 0, cout <= 64
+hipError_t launch_conv3x3_rgb_dgrad(const float *gout, int B, int H, int W, const float *Wf, int cout, float *dx, hipStream_t stream);
+// conv1_1: dW [3][3][3][cout] and db [cout] (or NULL) from x [B,H,W,3] and gout; scratch: conv3x3_rgb_wgrad_scratch_bytes(B*H*W)
+size_t conv3x3_rgb_wgrad_scratch_bytes(long long npix);
+hipError_t launch_conv3x3_rgb_wgrad(const float *x, const float *gout, int B, int H, int W, int cout, float *dW, float *db, int accumulate,
+                                    float *scratch, hipStream_t stream);
 // y = x * scale - mean[c]  (NLDF.py:29 preprocessing), C <= 4
 hipError_t launch_scale_shift(const float *x, long long npix, int C, float scale, const float *mean4, float *out,
                               hipStream_t stream);

@@ -421,6 +421,35 @@ VSTAB_API int vstab_scale_shift(const float *x, long long npix, int C, float sca
 /* tf.nn.max_pool(ksize 2, strides 2, SAME) on NHWC, C % 4 == 0 (vgg16.py:51-53). */
 VSTAB_API int vstab_maxpool2x2(const float *x, int B, int H, int W, int C, float *out, void *stream);
 
+/* ---- VGG16 trunk, backward (Vgg16.backward / Vgg16.features) ----------------------------------------
+ * The reverse walk over the 13 convolutions and 5 pools.  outputs18: the activations vstab_vgg16_forward wrote for `input`
+ * (all 18 non-NULL).  douts18: the gradient at each output, NULL = none; the walk starts at the deepest non-NULL one and the
+ * layers above it are not touched.  dinput [B,H,W,3] or NULL.  dparams26: {filter, biases} gradient per layer in the order of
+ * vstab_vgg16_load's layers ([3][3][Cin][Cout], [Cout]), NULL (or NULL entries: that layer's are not computed) = none;
+ * accumulate_params adds into them instead of writing them.  A max-pool window's gradient goes to its first maximum in the order
+ * (0,0), (0,1), (1,0), (1,1) among the taps inside the image, and a gradient passes a ReLU only where its output is > 0.
+ * Batches are processed in vstab_vgg16_forward's chunks; filter gradients accumulate across them.
+ * VSTAB_E_STATE: no loaded weights, a NULL outputs18[i], no gradient at any output, neither dinput nor a parameter gradient;
+ * VSTAB_E_ALIGN: a pointer not 16-byte (workspace: 256-byte) aligned; VSTAB_E_NOMEM: workspace below
+ * vstab_vgg16_backward_workspace_bytes(); VSTAB_E_SHAPE: a size the forward refuses.  Nothing is launched before these checks. */
+VSTAB_API size_t vstab_vgg16_backward_workspace_bytes(int B, int H, int W, int need_weights);
+VSTAB_API int vstab_vgg16_backward(vstab_ctx *ctx, const float *input, int B, int H, int W, float *const *outputs18,
+                                   const float *const *douts18, float *dinput, float *const *dparams26, int accumulate_params,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+/* Backward of vstab_maxpool2x2 fused with the ReLU gate of its input: y [B,H,W,C] (a ReLU's output), dpool
+ * [B,ceil(H/2),ceil(W/2),C] -> dy [B,H,W,C], every element written.  accumulate: dy holds a gradient at y already and becomes
+ * (dy + routed) where y > 0, 0 elsewhere.  C % 4 == 0. */
+VSTAB_API int vstab_maxpool2x2_relu_backward(const float *y, int B, int H, int W, int C, const float *dpool, float *dy,
+                                             int accumulate, void *stream);
+/* dy[i] = y[i] > 0 ? dy[i] : 0 in place, n % 4 == 0. */
+VSTAB_API int vstab_relu_backward(const float *y, float *dy, long long n, void *stream);
+/* conv1_1 (3x3 SAME, 3 -> cout <= 64, cout % 4 == 0; W HWIO on the device): the input gradient dx [B,H,W,3] of gout
+ * [B,H,W,cout], and the filter / bias gradient dW [3][3][3][cout], db [cout] (or NULL) from x [B,H,W,3] and gout. */
+VSTAB_API int vstab_conv3x3_rgb_dgrad(const float *gout, int B, int H, int W, const float *Wf, int cout, float *dx, void *stream);
+VSTAB_API size_t vstab_conv3x3_rgb_wgrad_workspace_bytes(int B, int H, int W);
+VSTAB_API int vstab_conv3x3_rgb_wgrad(const float *x, const float *gout, int B, int H, int W, int cout, float *dW, float *db,
+                                      int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- NLDF saliency head (NLDF.py:24-101; tertiary, never instantiated by the reference) ----------
  * Weights: "<L>/W", "<L>/b" for L in Fea_Global_1, Fea_Global_2, Fea_Global, Fea_P1..Fea_P5, Local_Fea,
  * Local_Score, Global_Score (conv [k][k][Cin][Cout]) and Fea_P2_Deconv..Fea_P5_Deconv ([5][5][Cout][Cin]).
