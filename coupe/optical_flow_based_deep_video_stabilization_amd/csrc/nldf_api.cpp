@@ -2,61 +2,15 @@
 // instantiates this model (no `NLDF.Model(` call anywhere) and the file is Python-2 only, so this is
 // built last and only at the reference's hard-wired geometry: pool1..pool5 of a 352x352 input
 // (176, 88, 44, 22, 11), outputs at 176x176 (NLDF.py:58-64, 74).
+#include <algorithm>
+
 #include "api_internal.h"
 #include "conv_desc.h"
+#include "nldf_plan.h"
 
 using namespace vstab;
 
-namespace {
-
-constexpr int FEA = 128;                      // fea_dim, NLDF.py:33
-const int POOL_C[5] = {64, 128, 256, 512, 512};        // pool1..pool5 channels
-const int POOL_HW[5] = {176, 88, 44, 22, 11};
-// concat buffers: cat_k = [Fea_Pk | Fea_Pk_LC | Fea_P(k+1)_Up]  (NLDF.py:57-66)
-const int CAT_C[5] = {768, 640, 512, 384, 256};        // cat1..cat5
-const int UP_C[4] = {512, 384, 256, 128};              // Fea_P2_Up .. Fea_P5_Up channels (into cat1..cat4)
-
-struct NldfWeights {            // float offsets into ctx->nldf_weights
-    size_t g1_w, g1_b, g2_w, g2_b, g3_w, g3_b;
-    size_t p_w[5], p_b[5];      // Fea_P1..P5
-    size_t d_w[4], d_b[4];      // Fea_P2_Deconv .. Fea_P5_Deconv (index 0 = P2)
-    size_t lf_w, lf_b, ls_w, ls_b, gs_w, gs_b;
-};
-
-enum NBuf { N_G1, N_G2, N_G, N_CAT1, N_CAT2, N_CAT3, N_CAT4, N_CAT5, N_LF, N_LS, N_GS, N_PART, N_NBUF };
-
-struct NldfPlan { size_t off[N_NBUF], bytes[N_NBUF], total; };
-
-// [B][hw][hw][c] per NBuf entry; hw == 0: a flat run of `c` floats whatever the batch (the split-K partial sums).  The one statement
-// of the workspace: nldf_plan sizes the buffers from it, vstab_nldf_workspace_layout reports it.
-struct NBufSpec { const char *name; int hw, c; };
-constexpr NBufSpec NBUFS[N_NBUF] = {
-    {"G1", 7, FEA},        {"G2", 3, FEA},         {"Fea_Global", 1, FEA}, {"cat1", 176, 768},       {"cat2", 88, 640},
-    {"cat3", 44, 512},     {"cat4", 22, 384},      {"cat5", 11, 256},      {"Local_Fea", 176, 640},  {"Local_Score", 176, 2},
-    {"Global_Score", 1, 2}, {"splitk", 0, 32 << 20}};
-
-bool nldf_plan(int B, NldfPlan &pl)
-{
-    if (B < 1 || B > 64) return false;
-    size_t off = 0;
-    for (int i = 0; i < N_NBUF; ++i) {
-        const NBufSpec &s = NBUFS[i];
-        const size_t n = s.hw ? (size_t)B * s.hw * s.hw * s.c : (size_t)s.c;
-        if (n * 4 >= 0x80000000ull) return false;
-        pl.off[i] = off; pl.bytes[i] = n * 4;
-        off += (pl.bytes[i] + 255) / 256 * 256;
-    }
-    pl.total = off;
-    return true;
-}
-
-}  // namespace
-
-struct vstab_nldf {             // lives inside the context (opaque to callers)
-    bool loaded = false;
-    float *w = nullptr;
-    NldfWeights o;
-};
+using namespace nldf;
 
 static vstab_nldf *nldf_of(vstab_ctx *ctx)
 {
@@ -140,6 +94,18 @@ extern "C" int vstab_nldf_load(vstab_ctx *ctx, const vstab_tensor *t, int count)
     if (!conv("Local_Fea", 1, 768, 768, 640, o.lf_w, o.lf_b)) return VSTAB_E_WEIGHTS;
     if (!conv("Local_Score", 1, 640, 640, 2, o.ls_w, o.ls_b)) return VSTAB_E_WEIGHTS;
     if (!conv("Global_Score", 1, FEA, FEA, 2, o.gs_w, o.gs_b)) return VSTAB_E_WEIGHTS;
+    // every variable as given, for the backward (nldf_grad_api.cpp): found and shape-checked above
+    static const char *const LAYERS[L_COUNT] = {"Fea_Global_1", "Fea_Global_2", "Fea_Global", "Fea_P1", "Fea_P2", "Fea_P3", "Fea_P4", "Fea_P5",
+                                                "Fea_P5_Deconv", "Fea_P4_Deconv", "Fea_P3_Deconv", "Fea_P2_Deconv", "Local_Fea", "Local_Score",
+                                                "Global_Score"};
+    for (int i = 0; i < L_COUNT; ++i) {
+        const vstab_tensor *W = find(t, count, std::string(LAYERS[i]) + "/W"), *b = find(t, count, std::string(LAYERS[i]) + "/b");
+        const size_t nw = (size_t)W->shape[0] * W->shape[1] * W->shape[2] * W->shape[3], nb = (size_t)b->shape[0];
+        o.raw_w[i] = reserve(nw);
+        std::copy(W->data, W->data + nw, host.begin() + o.raw_w[i]);
+        o.raw_b[i] = reserve(nb);
+        std::copy(b->data, b->data + nb, host.begin() + o.raw_b[i]);
+    }
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (N->w) { (void)hipFree(N->w); N->w = nullptr; }

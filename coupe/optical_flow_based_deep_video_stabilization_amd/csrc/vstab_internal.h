@@ -646,6 +646,20 @@ hipError_t launch_warp_perspective_u8(const unsigned char *src, int B, int sh, i
 hipError_t launch_contrast(float *buf, int B, int H, int W, int C, int Cs, int c_dst, hipStream_t stream);
 hipError_t launch_nldf_score(const float *local2, const float *global2, int B, int npix, float *score, float *prob,
                              hipStream_t stream);
+// NLDF head, backward (nldf_grad_ops.hip).  part: nldf_score_part_floats(B) floats; the Local_Score filter
+// gradient's scratch: local_score_wgrad_scratch_floats(C) floats.
+size_t nldf_score_part_floats(int B);
+hipError_t launch_nldf_score_grad(const float *dscore, const float *prob, const float *dprob, int B, int npix, float *dls, float *part,
+                                  hipStream_t stream);
+hipError_t launch_nldf_score_fold(const float *part, int B, const float *fg, const float *Wgs, const float *dfea_global, float *dgs, float *dfg,
+                                  float *dW_gs, float *db_gs, float *db_ls, int accumulate, hipStream_t stream);
+hipError_t launch_local_score_dgrad(const float *dls, const float *W, long long npix, int C, const float *dlocal_fea, float *dlf,
+                                    hipStream_t stream);
+size_t local_score_wgrad_scratch_floats(int C);
+hipError_t launch_local_score_wgrad(const float *lf, const float *dls, long long npix, int C, float *dW, int accumulate, float *scratch,
+                                    hipStream_t stream);
+hipError_t launch_contrast_gate_backward(const float *act, float *dcat, int B, int H, int W, int C, int Cs, hipStream_t stream);
+hipError_t launch_slice_gate(const float *act, float *d, long long rows, int Cs, int c_off, int C, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------
 // Host-side weight packing (pack.cpp): pure CPU code.

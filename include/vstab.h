@@ -468,6 +468,45 @@ VSTAB_API int vstab_nldf_forward(vstab_ctx *ctx, const float *const *pools5, int
                                  float *local_fea, float *fea_global, void *workspace, size_t workspace_bytes,
                                  void *stream);
 
+/* ---- NLDF saliency head, backward (NLDF.Model.backward / pools_grad) ------------
+ * The reverse walk of vstab_nldf_forward at the same hard-wired geometry.  vstab_nldf_load keeps every variable as given on the
+ * device; the launchers below it take raw weights.  pools5: as in the forward.  fwd_workspace: the forward's workspace of the same
+ * batch as the forward left it (cat1..cat5, G1, G2, Fea_Global are read, nothing is written); local_fea: the tensor the forward
+ * wrote.  dscore [B,176,176,2] is required; dprob [B,176,176,1] (with prob, the forward's), dlocal_fea [B,176,176,640] and dfea_global
+ * [B,1,1,128] are the optional gradients at the forward's other outputs (NULL = none).  dpools5: five output pointers
+ * [B,hw,hw,C_k] or NULL, each non-NULL one written in full.  dparams30: {W, b} gradient of the 15 layers in the order Fea_Global_1,
+ * Fea_Global_2, Fea_Global, Fea_P1..Fea_P5, Fea_P5_Deconv..Fea_P2_Deconv, Local_Fea, Local_Score, Global_Score, in the variables' own
+ * layouts; NULL, or NULL entries, are skipped (no filter-gradient launch is made for them, and an input gradient nothing asks for is not
+ * launched either); accumulate_params adds into them instead of writing.  A gradient passes a ReLU only where its output is > 0.
+ * No float atomics in the walk's own kernels and none in the launchers it composes: two calls give the same bits.
+ * VSTAB_E_STATE: no loaded head, a required pointer NULL, dprob without prob, a bias gradient without its filter gradient, no
+ * gradient asked for at all; VSTAB_E_ALIGN: a pointer not 16-byte (workspaces: 256-byte) aligned; VSTAB_E_NOMEM: a workspace below
+ * vstab_nldf_workspace_bytes() / vstab_nldf_backward_workspace_bytes(); VSTAB_E_SHAPE: a batch the forward refuses.  Nothing is launched
+ * before these checks. */
+VSTAB_API size_t vstab_nldf_backward_workspace_bytes(int B, int need_weights);
+VSTAB_API int vstab_nldf_backward(vstab_ctx *ctx, const float *const *pools5, int B, const void *fwd_workspace, size_t fwd_workspace_bytes,
+                                  const float *local_fea, const float *prob, const float *dscore, const float *dprob, const float *dlocal_fea,
+                                  const float *dfea_global, float *const *dpools5, float *const *dparams30, int accumulate_params,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+/* The walk's own kernels, one stage at a time (tests).
+ * Score stage at the head's geometry (npix = 176*176, 640 features): dls [B,npix,2] = dscore + Prob's share (p0 (1 - p0) dprob on
+ * channel 0, minus that on channel 1; written only when dprob != NULL, otherwise dscore itself is Local_Score's gradient and dls may
+ * be NULL), dgs [B,2] = its sum over each sample's pixels (Global_Score's gradient), db2 [2] = sum_b dgs (either score bias),
+ * dlf [B,npix,640] = dls[p,0] W[:,0] + dls[p,1] W[:,1] (+ dlocal_fea), dW [640,2] = sum_p local_fea[p,:]^T dls[p,:] (W, dW: Local_Score/W's
+ * layout).  dlf, dW (with local_fea), db2 optional.  workspace: vstab_nldf_score_backward_workspace_bytes(B), 256-byte aligned. */
+VSTAB_API size_t vstab_nldf_score_backward_workspace_bytes(int B);
+VSTAB_API int vstab_nldf_score_backward(const float *dscore, const float *prob, const float *dprob, const float *local_fea, const float *dlocal_fea,
+                                        const float *W, int B, float *dls, float *dgs, float *dlf, float *dW, float *db2, int accumulate,
+                                        void *workspace, size_t workspace_bytes, void *stream);
+/* Contrast_Layer's adjoint (the layer is self-adjoint) fused with Fea_Pk's ReLU gate, in place on a gradient buffer: act, dcat
+ * [B,H,W,cs] with act[..., 0:C] = Fea_Pk, dcat = [dP | dLC | ...]; dcat[..., 0:C] becomes (Fea_Pk > 0) ? dP + dLC - avg3x3_sym(dLC) : 0.
+ * C % 4 == 0, cs % 4 == 0, cs >= 2 C. */
+VSTAB_API int vstab_nldf_contrast_gate_backward(const float *act, float *dcat, int B, int H, int W, int C, int cs, void *stream);
+/* ReLU gate of a channel slice in place, d[row, c_off + c] = act[row, c_off + c] > 0 ? d : 0 for c < C, and (db != NULL) db [C] (+)= the
+ * gated slice's column sums (a transposed convolution's bias gradient).  workspace: vstab_column_sum_scratch_bytes(rows, C). */
+VSTAB_API int vstab_nldf_slice_gate_backward(const float *act, float *d, long long rows, int cs, int c_off, int C, float *db, int accumulate,
+                                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- NLDF's objective (NLDF.py:79-100, :136-171; csrc/nldf_loss_ops.hip states the formulas) -------------------------------
  * Shared refusals: VSTAB_E_STATE for a required pointer that is NULL, VSTAB_E_SHAPE unless every dimension is >= 1 and the tensor has
  * fewer than 2^31 elements, VSTAB_E_ALIGN / VSTAB_E_NOMEM for a workspace that is not 8-byte aligned / too short.  A refused call
