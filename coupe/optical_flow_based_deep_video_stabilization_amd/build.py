@@ -8,8 +8,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvstab_hip.so")
-SOURCES = ("conv_mfma.hip", "conv_rowwin.hip", "conv1_bf16x3.hip", "conv_skinny.hip", "tap_panel.hip", "wino_gemm_stream.hip", "flow_ops.hip", "warp_flow_grad.hip", "sampler_ops.hip", "sampler3d_ops.hip", "nldf_ops.hip", "clip_ops.hip", "train_batch_ops.hip", "train_ops.hip", "wgrad_mfma.hip", "winograd_ops.hip", "homography_ops.hip", "ssim_ops.hip", "cell_ops.hip", "flow_vis_ops.hip", "nldf_loss_ops.hip", "vgg_grad_ops.hip", "nldf_grad_ops.hip", "pack.cpp", "hbm_profile.cpp", "conv_desc.cpp", "api.cpp", "sampler_api.cpp", "flownet_plan.cpp", "flownet_forward.cpp", "vgg_api.cpp", "vgg_grad_api.cpp", "nldf_api.cpp", "nldf_grad_api.cpp", "loss_api.cpp", "train_conv_api.cpp", "train_api.cpp", "ssim_api.cpp", "cell_api.cpp", "flow_vis_api.cpp", "nldf_loss_api.cpp", "wino_gemm_api.cpp", "refine_level_api.cpp")
-HEADERS = ("vstab_internal.h", "api_internal.h", "conv_desc.h", "plan_cache.h", "flownet_plan.h", "vgg_plan.h", "nldf_plan.h", "hbm_profile.h", "tile3.h", "resample_coords.h", "warp_taps.h", "st_axis.h", "rowwin_tile.h", "conv_kloop_gfx950.inc", os.path.join("..", "..", "..", "include", "vstab.h"))
+SOURCES = ("conv_mfma.hip", "conv_rowwin.hip", "conv1_bf16x3.hip", "conv_skinny.hip", "tap_panel.hip", "wino_gemm_stream.hip", "flow_ops.hip", "warp_flow_grad.hip", "sampler_ops.hip", "sampler3d_ops.hip", "nldf_ops.hip", "clip_ops.hip", "train_batch_ops.hip", "train_ops.hip", "wgrad_mfma.hip", "winograd_ops.hip", "homography_ops.hip", "ssim_ops.hip", "cell_ops.hip", "flow_vis_ops.hip", "nldf_loss_ops.hip", "vgg_grad_ops.hip", "nldf_grad_ops.hip", "theta_ops.hip", "pack.cpp", "hbm_profile.cpp", "conv_desc.cpp", "api.cpp", "sampler_api.cpp", "flownet_plan.cpp", "flownet_forward.cpp", "vgg_api.cpp", "vgg_grad_api.cpp", "nldf_api.cpp", "nldf_grad_api.cpp", "loss_api.cpp", "train_conv_api.cpp", "train_api.cpp", "ssim_api.cpp", "cell_api.cpp", "flow_vis_api.cpp", "nldf_loss_api.cpp", "wino_gemm_api.cpp", "refine_level_api.cpp", "theta_api.cpp")
+HEADERS = ("vstab_internal.h", "api_internal.h", "conv_desc.h", "plan_cache.h", "flownet_plan.h", "vgg_plan.h", "nldf_plan.h", "hbm_profile.h", "tile3.h", "resample_coords.h", "warp_taps.h", "st_axis.h", "rowwin_tile.h", "theta_ops.h", "conv_kloop_gfx950.inc", os.path.join("..", "..", "..", "include", "vstab.h"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-result"]
 

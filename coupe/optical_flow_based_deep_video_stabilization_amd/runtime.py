@@ -255,3 +255,6 @@ def reset():
     ts = sys.modules.get(__package__ + ".train_step")
     if ts is not None:
         ts._trainers.clear()
+    tr = sys.modules.get(__package__ + ".theta_runtime")
+    if tr is not None:
+        tr.reset()

@@ -1100,6 +1100,44 @@ VSTAB_API int vstab_host_train_conv_plan(int dgrad, int B, int Hi, int Wi, int c
  * output channel; 16 positions x [cin/32][cout][32] floats to `wpk`.  Returns the number of floats, or a negative error. */
 VSTAB_API long long vstab_host_pack_winograd(const float *W, const double *scale, int cin, int cout, float *wpk, long long cap);
 
+/* ---- theta regressors (model.py:152-184 Localizer, :375-455 dense_homo, :897-1024 flownetS_prehomo / _variableWeight), inference ----
+ * The blocks those graphs need beside vstab_conv_forward (csrc/theta_ops.hip).  Shared refusals, judged in this order and before any
+ * launch: VSTAB_E_STATE for a NULL buffer, VSTAB_E_SHAPE for a size outside the contract, VSTAB_E_ALIGN for a misaligned buffer,
+ * VSTAB_E_NOMEM for a short workspace. */
+
+/* tf.pad(x, [[0,0],[p,p],[p,p],[0,0]], "SYMMETRIC") (PadLayer, model.py:907...): x [B,H,W,C] contiguous, any C >= 1 ->
+ * y [B,H+2p,W+2p,cs_y] with y[i] = x[-i-1] before the edge and x[2H-1-i] after it (the edge sample repeated), channels C..cs_y-1
+ * zeroed.  p = 0 is the channel-padding copy.  0 <= p <= min(H, W), cs_y >= C and cs_y % 4 == 0, B*(H+2p)*(W+2p)*cs_y < 2^31; y 16-byte
+ * aligned (x: 4-byte; 16-byte accesses on x when C % 4 == 0 and x is 16-byte aligned). */
+VSTAB_API int vstab_pad_symmetric(const float *x, int B, int H, int W, int C, int p, float *y, int cs_y, void *stream);
+
+/* BatchNormLayer(act = lrelu(slope), is_train = False, gamma_init = None) IN PLACE on channels c_off..c_off+C of a [rows, cs] view:
+ * y = act((z - moving_mean) * rstd + beta), act(u) = u >= 0 ? u : slope * u, rstd as in vstab_bn_lrelu_inference_forward.
+ * twice != 0: the layer's input passes the activation first, y = act(bn(act(z))) -- DenseLayer(act = lrelu) -> BatchNormLayer(act = lrelu),
+ * model.py:953-956, 409-412.  Refusals as vstab_bn_lrelu_inference_forward. */
+VSTAB_API int vstab_bn_lrelu_slope_inference(float *zy, long long rows, int cs, int c_off, int C, const float *beta, const float *moving_mean,
+                                             const float *moving_var, float eps, float slope, int twice, void *stream);
+/* The same arithmetic fused with MaxPool2d((2,2),(2,2),'SAME'): z [B,H,W,C] contiguous -> out [B,ceil(H/2),ceil(W/2),C], the window clipped
+ * at an odd edge as in vstab_maxpool2x2; z is read once and not written.  C % 4 == 0, B*H*W*C < 2^31, 16-byte aligned buffers. */
+VSTAB_API int vstab_bn_lrelu_slope_pool_inference(const float *z, int B, int H, int W, int C, const float *beta, const float *moving_mean,
+                                                  const float *moving_var, float eps, float slope, int twice, float *out, void *stream);
+
+/* DenseLayer: y [B,N] = act(x [B,K] . W [K,N] + b [N]), W on the device in the reference's layout, read exactly once per call.
+ * act: VSTAB_DENSE_IDENTITY, _LRELU (u >= 0 ? u : slope * u), _TANH, _TANH_AFFINE (tanh(u / 1000) * scale[n] + shift[n], dense_homo's tail,
+ * model.py:381, 413-420; scale and shift are read by that act only).  1 <= B <= 32, K >= 4 and K % 4 == 0, N >= 1, K * N < 2^40.
+ * K is cut into slabs that depend on K and N alone; each slab's partial sums go to the workspace and a second launch adds them in slab
+ * order: no atomics, equal bits from call to call, and a row's bits do not depend on B.
+ * workspace: vstab_dense_forward_workspace_bytes(B, K, N) bytes (0 for a shape the call refuses), 16-byte aligned; x and y 16-byte aligned. */
+#define VSTAB_DENSE_IDENTITY    0
+#define VSTAB_DENSE_LRELU       1
+#define VSTAB_DENSE_TANH        2
+#define VSTAB_DENSE_TANH_AFFINE 3
+VSTAB_API size_t vstab_dense_forward_workspace_bytes(int B, int K, int N);
+VSTAB_API int vstab_dense_forward(const float *x, int B, int K, int N, const float *W, const float *b, int act, float slope, const float *scale,
+                                  const float *shift, float *y, void *workspace, size_t workspace_bytes, void *stream);
+/* The slab plan of vstab_dense_forward for (K, N), without a HIP call: rows of W per slab and the number of slabs (0 when refused). */
+VSTAB_API int vstab_host_dense_plan(int K, int N, int32_t *slab_rows, int32_t *slabs);
+
 #ifdef __cplusplus
 }
 #endif
